@@ -11,6 +11,14 @@ resident in HBM when the timed region starts.  Scaling is STRONG: the global bat
 65 536 and is split over the ranks, as in the reference's published 8-GPU run
 (examples/dlrm/README.MD:38-45).
 
+A plain run sets up, warms up, times the K steps and prints its JSON line (`value` samples/s and `ms_per_step`, the
+wall-clock mean of one timed step).  `--full` adds everything else, measured on the same timed steps or after them: the
+per-kernel roofline (in-library kernel timing on during the timed steps), the on-device copy rate, per-step HIP-event
+times, the correctness checks (losses, parameter checksums, sort give-ups, bounds errors; a faulted run exits 4 and prints
+no line), the model of the binding resource and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step
+returned to its caller (loss, logits, labels) as DIR/<name>.npy in float32 (rank r > 0 of an N-rank run: <name>_rank<r>.npy);
+inputs and initial model are a function of the arguments alone, so two builds can be compared output for output.
+
 Launch: `python bench.py --gpus N --steps K --warmup W` for any N.  With N > 1 and no WORLD_SIZE in
 the environment this process starts N fresh rank processes itself (`python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, the command of examples/dlrm/README.MD:17-28)
@@ -68,7 +76,12 @@ def parse():
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--row-cap", type=int, default=0, help="debug: cap rows per table")
     ap.add_argument("--zipf", type=float, default=0.0, help="Zipf alpha for ids (0 = uniform)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (roofline, copy rate, per-step event "
+                         "times, correctness checks, binding resource, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, logits, labels) as DIR/<name>.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=24.0,
                     help="time budget of the CPU baseline (it runs >= 10 train iterations per batch size whatever this says)")
     ap.add_argument("--num-batches", type=int, default=32, help="distinct pre-generated batches (SURVEY.md §8d: >= 32)")
@@ -155,6 +168,7 @@ def dry_run(args) -> None:
         print(json.dumps({"metric": "samples/sec Criteo-1TB DLRM batch 65536", "dry_run": True, "n_gpus": world,
                           "ranks": dist.get_world_size(), "backend": dist.get_backend(), "steps": args.steps,
                           "warmup": args.warmup, "value": args.global_batch * args.steps / float(t.item()),
+                          "ms_per_step": float(t.item()) / args.steps * 1e3,
                           "launcher": os.environ.get("TORCHREC_AMD_BENCH_LAUNCHER", "external")}), flush=True)
     dist.destroy_process_group()
 
@@ -182,6 +196,18 @@ def measure_copy_GBs(torch, dev) -> float:
         best = min(best, a.elapsed_time(b))
     del src, dst
     return 2 * n * 4 / (best * 1e-3) / 1e9
+
+
+def dump_outputs(out_dir, step_out, rank) -> None:
+    """--dump-outputs: the last timed step's result as its caller receives it from TrainPipelineSparseDist.progress,
+    (loss, logits, labels) of this rank's batch, one float32 .npy each (65 536 samples: 0.5 MB in all)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, x in zip(("loss", "logits", "labels"), step_out):
+        arr = x.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def main(args):
@@ -350,7 +376,8 @@ def main(args):
     pipe = TrainPipelineSparseDist(model, optimizer, dev)
     model.train()
     lib = _lib.load()
-    copy_GBs = measure_copy_GBs(torch, dev) if rank == 0 else None
+    full = args.full
+    copy_GBs = measure_copy_GBs(torch, dev) if full and rank == 0 else None
 
     def sync_all():
         if world > 1:
@@ -360,32 +387,86 @@ def main(args):
     for _ in range(args.warmup):
         pipe.progress(it)
     sync_all()
-    lib.tbe_profile_enable(1)
-    for s in range(4):
-        read_profile(lib, s)
-    stamps = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    if full:  # in-library kernel timing of the TBE launches (the roofline leg) and one HIP event per step
+        lib.tbe_profile_enable(1)
+        for s in range(4):
+            read_profile(lib, s)
+        stamps = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     sync_all()
     t0 = time.perf_counter()
-    stamps[0].record()
-    loss_first = loss_last = None
+    if full:
+        stamps[0].record()
+    out = loss_first = loss_last = None
     for k in range(args.steps):
         out = pipe.progress(it)
-        stamps[k + 1].record()
-        # the loss of the first and the last timed step (a 4-byte device copy each: under HIP graphs the loss lives in
-        # a static buffer the next replay overwrites); read after the timed region
-        if k == 0:
-            loss_first = out[0].detach().clone()
-        if k == args.steps - 1:
-            loss_last = out[0].detach().clone()
+        if full:
+            stamps[k + 1].record()
+            # the loss of the first and the last timed step (a 4-byte device copy each: under HIP graphs the loss lives in
+            # a static buffer the next replay overwrites); read after the timed region
+            if k == 0:
+                loss_first = out[0].detach().clone()
+            if k == args.steps - 1:
+                loss_last = out[0].detach().clone()
     sync_all()
     elapsed = time.perf_counter() - t0
-    lib.tbe_profile_enable(0)
-    prof = [read_profile(lib, s) for s in range(4)]
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     value = args.global_batch * args.steps / elapsed
+    kind = shard._table_kind  # -2 replicated, -1 row-wise, >= 0 owning rank
+    n_tw_per_rank = [sum(1 for i in range(F) if kind[i] == r) for r in range(world)]
+    if args.dump_outputs and out is not None:
+        # nothing has run since the last step: its outputs (static buffers under HIP graphs) still hold what it returned
+        dump_outputs(args.dump_outputs, out, rank)
+    result = {
+        "metric": "samples/sec Criteo-1TB DLRM batch 65536", "value": round(value, 1), "unit": "samples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "strong",
+        # the reference's only published number is 5 497 159.68 samples/s on 8 x A100-40GB
+        # (examples/dlrm/README.MD:45, real Criteo data, end to end) — comparable at N = 8 only
+        "vs_baseline": round(value / 5497159.68, 3) if world == 8 and backend == "nccl" else None,
+        "dtype": "f32", "data": "synthetic", "full": full, "hip_graphs": hip_graphs, "hip_graphs_note": graphs_note,
+        "explicit_backward_steps": int(getattr(train_model, "explicit_steps", 0)),
+        "half_batch_steps": int(getattr(train_model, "half_batch_steps", 0)),
+        "prefetched_lookups": int(getattr(train_model, "prefetched_lookups", 0)),
+        "tuned_gemms": tuned,
+        "rccl_ranks": dist.get_world_size() if dist.is_initialized() and dist.get_backend() == "nccl" else 0,
+        "backend": dist.get_backend() if dist.is_initialized() else None,
+        "rehearsal": (f"{world} ranks on {torch.cuda.device_count()} GPU(s) over gloo, all-to-all staged through the host: "
+                      "NOT a multi-GPU timing" if world > 1 and backend == "gloo" else None),
+        "launcher": os.environ.get("TORCHREC_AMD_BENCH_LAUNCHER", "external torchrun" if world > 1 else "direct"),
+        "env": {k: os.environ[k] for k in ("GPU_MAX_HW_QUEUES", "HSA_ENABLE_IPC_MODE_LEGACY", "TORCHREC_AMD_RW_INPUT_DIST",
+                                           "TORCHREC_AMD_PREFETCH_LOOKUP", "TORCHREC_AMD_FUSED_BCE",
+                                           "TORCHREC_AMD_REHEARSAL_LINK_US", "TORCHREC_AMD_RCCL_HIGH_PRIORITY",
+                                           "TBE_STREAM_PROBE", "TORCHREC_AMD_HALF_BATCHES", "TORCHREC_AMD_WGRAD_LATE_LAYERS") if k in os.environ},
+        "config": {"workload": "DLRM Criteo-1TB shape: 26 tables (177.9M rows, 84.85 GiB fp32, D=128), 13 dense, "
+                               "pooling factor 1, dense 512-256-128, over 1024-1024-512-256-1, fused exact SGD",
+                   "global_batch": args.global_batch, "local_batch": B_local,
+                   "parallelism": (f"mp{world}: {F - n_rw - n_dp} table-wise + {n_rw} row-wise + {n_dp} replicated "
+                                   f"(data-parallel) tables, dense dp{world}"),
+                   "plan": {"table_wise": F - n_rw - n_dp, "row_wise": n_rw, "data_parallel": n_dp,
+                            "table_wise_per_rank": n_tw_per_rank, "row_wise_arg": args.row_wise,
+                            "source": ("pinned mixed plan (BASELINE config 3, SURVEY.md §8d)" if args.row_wise < 0 and world > 1
+                                       else "torchrec_amd planner" if args.row_wise <= 0 else "--row-wise")},
+                   "ids": f"zipf({args.zipf})" if args.zipf else "uniform", "row_cap": args.row_cap or None,
+                   "distinct_batches": args.num_batches, "seed": args.seed, "data_ranks": data_ranks,
+                   "rw_input_dist": shard._rw_mode_active if n_rw else None},
+        # --full only
+        "median_ms_per_step": None, "min_max_ms_per_step": None,
+        "checks": None, "binding": None, "roofline": None, "cpu_baseline": None,
+    }
+    if not full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
+    # ==== --full: everything beyond the headline figure ===========================================================
+    lib.tbe_profile_enable(0)
+    prof = [read_profile(lib, s) for s in range(4)]
     step_ms = sorted(stamps[k].elapsed_time(stamps[k + 1]) for k in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
 
@@ -441,7 +522,6 @@ def main(args):
     # At N > 1 a rank runs TWO lookups per step (the fused one over the global batch for its sharded
     # features, the dense-gradient one over its LOCAL batch for the replicated tiny tables); the
     # profile slots hold both, so everything below is per STEP: summed launch time, summed bytes.
-    kind = shard._table_kind  # -2 replicated, -1 row-wise, >= 0 owning rank
     feat_units = sum((1.0 / world) if kind[i] == -1 else (1.0 if kind[i] == rank else 0.0) for i in range(F))
     feat_units += sum(1.0 for i in range(F) if kind[i] == -2) / world  # local batch = 1/W of the global batch
     # Algorithmic bytes per launch (SURVEY.md §8d general formula, L = 1, fp32 rows, int64 ids):
@@ -522,7 +602,6 @@ def main(args):
         "mfma_f32_frac": round(MFLOP_PER_SAMPLE_TRAIN * 1e6 * value / (world * MFMA_F32_PEAK_TFLOPS * 1e12), 4),
         "mflop_per_sample": MFLOP_PER_SAMPLE_TRAIN,
     }
-    n_tw_per_rank = [sum(1 for i in range(F) if kind[i] == r) for r in range(world)]
     n_rw_feats = sum(1 for i in range(F) if kind[i] == -1)
     # pooled all-to-all: a rank sends [B_local, D] per feature it holds (row-wise features: every rank holds a
     # shard) to EACH peer over that peer's own link, forward; the same volume comes back as gradients
@@ -542,47 +621,14 @@ def main(args):
     if rank == 0:
         if roofline is not None:
             roofline["end_to_end"] = end_to_end
-        out = {
-            "metric": "samples/sec Criteo-1TB DLRM batch 65536", "value": round(value, 1), "unit": "samples/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            # per-step times from HIP events on the compute stream (rank 0), next to the wall-clock mean above
+        result.update({
+            # per-step times from HIP events on the compute stream (rank 0), next to the wall-clock mean `ms_per_step`
             "median_ms_per_step": round(median_ms, 3), "min_max_ms_per_step": [round(step_ms[0], 3), round(step_ms[-1], 3)],
-            "higher_is_better": True, "scaling": "strong",
-            # the reference's only published number is 5 497 159.68 samples/s on 8 x A100-40GB
-            # (examples/dlrm/README.MD:45, real Criteo data, end to end) — comparable at N = 8 only
-            "vs_baseline": round(value / 5497159.68, 3) if world == 8 and backend == "nccl" else None,
-            "dtype": "f32", "data": "synthetic", "hip_graphs": hip_graphs, "hip_graphs_note": graphs_note,
-            "explicit_backward_steps": int(getattr(train_model, "explicit_steps", 0)),
-            "half_batch_steps": int(getattr(train_model, "half_batch_steps", 0)),
-            "prefetched_lookups": int(getattr(train_model, "prefetched_lookups", 0)),
-            "tuned_gemms": tuned,
-            "rccl_ranks": dist.get_world_size() if dist.is_initialized() and dist.get_backend() == "nccl" else 0,
-            "backend": dist.get_backend() if dist.is_initialized() else None,
-            "rehearsal": (f"{world} ranks on {torch.cuda.device_count()} GPU(s) over gloo, all-to-all staged through the host: "
-                          "NOT a multi-GPU timing" if world > 1 and backend == "gloo" else None),
-            "launcher": os.environ.get("TORCHREC_AMD_BENCH_LAUNCHER", "external torchrun" if world > 1 else "direct"),
-            "env": {k: os.environ[k] for k in ("GPU_MAX_HW_QUEUES", "HSA_ENABLE_IPC_MODE_LEGACY", "TORCHREC_AMD_RW_INPUT_DIST",
-                                               "TORCHREC_AMD_PREFETCH_LOOKUP", "TORCHREC_AMD_FUSED_BCE",
-                                               "TORCHREC_AMD_REHEARSAL_LINK_US", "TORCHREC_AMD_RCCL_HIGH_PRIORITY",
-                                               "TBE_STREAM_PROBE", "TORCHREC_AMD_HALF_BATCHES", "TORCHREC_AMD_WGRAD_LATE_LAYERS") if k in os.environ},
-            "config": {"workload": "DLRM Criteo-1TB shape: 26 tables (177.9M rows, 84.85 GiB fp32, D=128), 13 dense, "
-                                   "pooling factor 1, dense 512-256-128, over 1024-1024-512-256-1, fused exact SGD",
-                       "global_batch": args.global_batch, "local_batch": B_local,
-                       "parallelism": (f"mp{world}: {F - n_rw - n_dp} table-wise + {n_rw} row-wise + {n_dp} replicated "
-                                       f"(data-parallel) tables, dense dp{world}"),
-                       "plan": {"table_wise": F - n_rw - n_dp, "row_wise": n_rw, "data_parallel": n_dp,
-                                "table_wise_per_rank": n_tw_per_rank, "row_wise_arg": args.row_wise,
-                                "source": ("pinned mixed plan (BASELINE config 3, SURVEY.md §8d)" if args.row_wise < 0 and world > 1
-                                           else "torchrec_amd planner" if args.row_wise <= 0 else "--row-wise")},
-                       "ids": f"zipf({args.zipf})" if args.zipf else "uniform", "row_cap": args.row_cap or None,
-                       "distinct_batches": args.num_batches, "seed": args.seed, "data_ranks": data_ranks,
-                       "rw_input_dist": shard._rw_mode_active if n_rw else None},
             "checks": checks, "binding": binding, "roofline": roofline, "cpu_baseline": cpu,
-        }
+        })
         # a run whose kernels gave up, saw out-of-range ids or let the replicas drift measured the wrong computation:
         # the line goes to stderr and the exit code says so
-        print(json.dumps(out), file=sys.stderr if bad else sys.stdout, flush=True)
+        print(json.dumps(result), file=sys.stderr if bad else sys.stdout, flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
     if bad:

@@ -26,6 +26,7 @@ def test_launcher_starts_two_ranks_and_relays_one_json_line():
     d = json.loads(lines[0])
     assert d["dry_run"] is True and d["n_gpus"] == 2 and d["ranks"] == 2 and d["backend"] == "gloo"
     assert d["steps"] == 3 and d["warmup"] == 1 and d["launcher"] == "bench.py" and d["value"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 65536) <= 1e-6 * 65536  # one timed step's wall-clock milliseconds
 
 
 def test_launcher_parent_never_imports_torch():

@@ -6,21 +6,24 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(extra_env, *flags, timeout=900):
+def _bench(extra_env, *flags, timeout=900, full=True):
+    """full: the line with the roofline, the checks and the binding resource (--full; CPU baseline skipped)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(extra_env)
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", *flags], env=env,
+    mode = ["--full", "--no-cpu-baseline"] if full else []
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *mode, *flags], env=env,
                           capture_output=True, text=True, timeout=timeout)
 
 
-def _run(extra_env, *flags):
-    out = _bench(extra_env, "--row-cap", "200000", "--steps", "4", "--warmup", "3", "--num-batches", "3", *flags)
+def _run(extra_env, *flags, full=True):
+    out = _bench(extra_env, "--row-cap", "200000", "--steps", "4", "--warmup", "3", "--num-batches", "3", *flags, full=full)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout  # ONE line on stdout
@@ -53,6 +56,30 @@ def test_bench_default_path():
         assert abs(c[k] - e["checks"][k]) <= 2e-4 * abs(c[k]), (k, c[k], e["checks"][k])
     for k in ("dense", "embedding"):
         assert _close(c["param_checksum"][k], e["checks"]["param_checksum"][k], 2e-6), (k, c["param_checksum"], e["checks"])
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full the line holds the headline figure only (nothing else measured or checked); --dump-outputs writes
+    the last timed step's (loss, logits, labels), the same as a --full run of the same arguments computes."""
+    flags = ("--global-batch", "4096", "--dump-outputs")
+    d = _run({}, *flags, str(tmp_path / "plain"), full=False)
+    assert d["metric"].startswith("samples/sec") and d["unit"] == "samples/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["full"] is False and d["steps"] == 4 and d["warmup"] == 3
+    assert d["value"] > 0 and abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) <= 1e-2 * d["value"]
+    assert d["checks"] is None and d["roofline"] is None and d["binding"] is None and d["cpu_baseline"] is None
+    f = _run({}, *flags, str(tmp_path / "full"))
+    assert f["full"] is True and f["checks"]["sort_giveups"] == 0
+    plain = {n: np.load(tmp_path / "plain" / f"{n}.npy") for n in ("loss", "logits", "labels")}
+    full = {n: np.load(tmp_path / "full" / f"{n}.npy") for n in ("loss", "logits", "labels")}
+    assert sorted(p.name for p in (tmp_path / "plain").iterdir()) == ["labels.npy", "logits.npy", "loss.npy"]
+    for n in plain:
+        assert plain[n].dtype == np.float32 and plain[n].shape == full[n].shape, n
+    assert plain["logits"].size == 4096 and np.isfinite(plain["logits"]).all()
+    np.testing.assert_array_equal(plain["labels"], full["labels"])  # the same inputs from run to run
+    assert set(np.unique(plain["labels"])) <= {0.0, 1.0}
+    assert full["loss"].size == 1 and full["loss"].item() == f["checks"]["loss_last"]  # the last timed step's result
+    assert abs(plain["loss"].item() - full["loss"].item()) <= 2e-4 * abs(full["loss"].item())
+    np.testing.assert_allclose(plain["logits"], full["logits"], rtol=1e-3, atol=1e-4)
 
 
 def test_bench_run_with_a_kernel_fault_is_invalid():
