@@ -219,12 +219,6 @@ int tbe_sort_pairs(void* keys, void* keys_tmp, void* payload, void* payload_tmp,
                    int32_t key_bits, int32_t key_bytes, int32_t payload_bytes, void* workspace,
                    size_t workspace_bytes, void* stream);
 int tbe_debug_sort_timeouts(int64_t* count);
-/* Development aid: device buffer of int64 [7 passes][256 segments][8] that tbe_sort_pairs' pass kernels fill
- * with 100 MHz wall-clock stamps per phase (NULL switches it off; tools/sstamps.py). */
-int tbe_debug_set_sort_stamps(void* device_buffer);
-/* Development aid of the same kind for the interaction forward (TBE_INTERACTION_ABLATION=6): 8 workgroups x 4 waves x
- * 32 samples x 6 cycle-counter stamps (uint64), NULL switches it off. */
-int tbe_debug_set_interaction_stamps(void* device_buffer);
 int tbe_backward_apply_f32(const uint64_t* feat_weights, const int32_t* feat_D,
                            const int64_t* feat_out_offset, const int64_t* feat_rows,
                            const int64_t* feat_row_base, const uint64_t* feat_state0,

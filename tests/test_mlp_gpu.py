@@ -110,40 +110,6 @@ def test_weighted_colsum_and_one_output_linear(B, N):
     torch.testing.assert_close(lin.bias.grad, ref_lin.bias.grad, rtol=1e-4, atol=1e-3)
 
 
-def test_wgrad_on_side_stream_matches_inline():
-    """modules/mlp.py _WgradOverlap: weight gradients computed on the side stream and accumulated out of band are
-    bit-identical to the ones autograd accumulates (same kernels, same order), also when a gradient already exists."""
-    from torchrec_amd.modules.mlp import MLP, _WgradOverlap
-
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(3)
-    mlp = MLP(96, [256, 128, 64], device=dev)
-    x = torch.randn(8192, 96, device=dev, requires_grad=True)
-    g = torch.randn(8192, 64, device=dev)
-
-    def run(overlap, passes):
-        for p in mlp.parameters():
-            p.grad = None
-        x.grad = None
-        for _ in range(passes):
-            if overlap:
-                _WgradOverlap.enable(dev)
-            try:
-                mlp(x).backward(g)
-            finally:
-                if overlap:
-                    _WgradOverlap.disable()  # joins
-        torch.cuda.synchronize()
-        return [p.grad.clone() for p in mlp.parameters()] + [x.grad.clone()]
-
-    for passes in (1, 2):
-        want = run(False, passes)
-        got = run(True, passes)
-        assert not _WgradOverlap.on and not _WgradOverlap.pending
-        for a, b in zip(want, got):
-            assert torch.equal(a, b)
-
-
 @pytest.mark.parametrize("B,dtype", [(8192, torch.int64), (65536, torch.int64), (65536, torch.float32), (1, torch.float32),
                                      (3001, torch.int64), (1 << 20, torch.float32)])
 def test_fused_bce_with_logits_matches_torch(B, dtype):
@@ -212,41 +178,3 @@ def test_row_block_partials_sum_to_the_one_pass_results(B, N):
     torch.testing.assert_close(torch.ops.tbe_hip.weighted_colsum_partials(gy, w).double().sum(0).float(),
                                torch.ops.tbe_hip.weighted_colsum(gy, w), rtol=1e-4, atol=1e-3)
 
-
-def test_deferred_finish_of_an_eager_backward_equals_the_plain_path():
-    """modules/mlp.py _DeferredFinish: with the switch on, an eager backward leaves the split-K weight gradients and the
-    bias gradients to ONE launch (segment table by value in the kernel arguments) that also attaches them as .grad
-    (accumulating into an existing one); same values as the plain path to fp32 summation order, nothing pending afterwards,
-    off again after disable()."""
-    from torchrec_amd.modules.mlp import MLP, LinearOut, _DeferredFinish
-
-    def run(deferred):
-        torch.manual_seed(3)
-        mlp = MLP(479, [1024, 512, 256], device=torch.device("cuda"))
-        last = LinearOut(256, 1, device=torch.device("cuda"))
-        x = torch.randn(16384, 479, device="cuda")
-        y = last(mlp(x))
-        if deferred:
-            _DeferredFinish.enable()
-        try:
-            y.sum().backward()
-            if deferred:
-                assert len(_DeferredFinish.pending) >= 6  # 3 split-K weights, 3 biases, the one-output weight
-        finally:
-            if deferred:
-                _DeferredFinish.disable()
-        assert not _DeferredFinish.pending and not _DeferredFinish.on
-        return [p.grad.clone() for p in list(mlp.parameters()) + list(last.parameters())]
-
-    a, b = run(False), run(True)
-    for g0, g1 in zip(a, b):
-        torch.testing.assert_close(g1, g0, rtol=2e-4, atol=2e-3)
-    # accumulation into an existing .grad
-    lin = LinearOut(256, 1, device=torch.device("cuda"))
-    x = torch.randn(4096, 256, device="cuda")
-    lin(x).sum().backward()
-    once = lin.weight.grad.clone()
-    _DeferredFinish.enable()
-    lin(x).sum().backward()
-    _DeferredFinish.disable()
-    torch.testing.assert_close(lin.weight.grad, 2 * once, rtol=2e-4, atol=2e-3)

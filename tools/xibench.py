@@ -1,5 +1,4 @@
-"""Timing of the fused dot-interaction kernels at the Criteo shape (development tool).
-TBE_INTERACTION_ABLATION=1 (no output stores) / 2 (no MFMA) switch the forward kernel's tuning variants."""
+"""Timing of the fused dot-interaction kernels at the Criteo shape (development tool)."""
 import os
 import sys
 
@@ -36,7 +35,7 @@ def main():
     out = _FusedDotInteraction.apply(dense, sparse, pad)
     fb = t(lambda: torch.autograd.grad(_FusedDotInteraction.apply(dense, sparse, pad), (dense, sparse), g))
     rd, wr = B * (F + 1) * D * 4, B * (D + (F + 1) * F // 2) * 4
-    print(f"pad_rows={pad} ablation={os.environ.get('TBE_INTERACTION_ABLATION', '0')}: forward {f:.1f} us ({(rd + wr) / f / 1e6:.2f} TB/s of "
+    print(f"pad_rows={pad}: forward {f:.1f} us ({(rd + wr) / f / 1e6:.2f} TB/s of "
           f"{(rd + wr) / 1e9:.2f} GB), forward+backward {fb:.1f} us")
 
 

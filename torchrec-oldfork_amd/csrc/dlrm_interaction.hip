@@ -29,21 +29,8 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 // Synchronisation of a wave's lanes on wave-private LDS data.  The LDS operations of one wave execute in
 // program order, so only the compiler has to be kept from moving them: a wave barrier.  (A memory fence here
 // would also make the wave wait for every outstanding GLOBAL load — exactly the prefetch of the next sample
-// these kernels want to keep in flight.)  TBE_INTERACTION_FENCE=1 at build time restores full fences.
-__device__ __forceinline__ void wave_lds_fence() {
-#ifdef TBE_INTERACTION_FULL_FENCE
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#else
-  __builtin_amdgcn_wave_barrier();
-#endif
-}
-
-__device__ __forceinline__ float4 ldnt4(const float* p) {  // streaming (non-temporal) 16-B load
-  const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
+// these kernels want to keep in flight.)
+__device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_wave_barrier(); }
 
 // index of pair (i, j), i < j < R, in torch.triu_indices(R, R, offset=1) row-major order
 __device__ __forceinline__ int triu_index(int i, int j, int R) { return i * (2 * R - i - 1) / 2 + (j - i - 1); }
@@ -77,7 +64,7 @@ struct XLoader {
 // the first MFMA.  The summation order over columns is therefore (s, e, q) — the oracle walks the
 // same order (oracle/dlrm_oracle.c), so results stay bit-exact.  LDS only re-stages the 351 pair
 // products for a coalesced store; occupancy is bound by VGPRs (4 waves / SIMD at D = 128), not LDS.
-template <int D, int ABL = 0>  // ABL: ablation for tuning runs only (1 = no output stores, 2 = no MFMA)
+template <int D>
 __global__ __launch_bounds__(256, (D <= 128 ? 4 : 2)) void interaction_fwd_kernel(const float* __restrict__ dense,
                                                                                   const float* __restrict__ sparse,
                                                                                   float* __restrict__ out, int B, int F,
@@ -107,10 +94,10 @@ __global__ __launch_bounds__(256, (D <= 128 ? 4 : 2)) void interaction_fwd_kerne
                                  : sparse + (static_cast<int64_t>(b) * F + (row0 - 1)) * D) + 4 * kq;
     const float* x1 = sparse + (static_cast<int64_t>(b) * F + (row1 - 1)) * D + 4 * kq;  // row1 >= 1 when R >= 2
 #pragma unroll
-    for (int s = 0; s < NS; ++s) xa[s] = (ABL >= 3) ? ldnt4(x0 + 16 * s) : ld4(x0 + 16 * s);
+    for (int s = 0; s < NS; ++s) xa[s] = ld4(x0 + 16 * s);
     if (R > 16) {
 #pragma unroll
-      for (int s = 0; s < NS; ++s) xb[s] = (ABL >= 3) ? ldnt4(x1 + 16 * s) : ld4(x1 + 16 * s);
+      for (int s = 0; s < NS; ++s) xb[s] = ld4(x1 + 16 * s);
     } else {
 #pragma unroll
       for (int s = 0; s < NS; ++s) xb[s] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -127,11 +114,6 @@ __global__ __launch_bounds__(256, (D <= 128 ? 4 : 2)) void interaction_fwd_kerne
       const float a1[4] = {xb[s].x, xb[s].y, xb[s].z, xb[s].w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (ABL == 2) {
-          acc00[0] += a0[e];
-          acc01[0] += a1[e];
-          continue;
-        }
         acc00 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], a0[e], acc00, 0, 0, 0);
         acc01 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], a1[e], acc01, 0, 0, 0);
         acc11 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], a1[e], acc11, 0, 0, 0);
@@ -144,7 +126,7 @@ __global__ __launch_bounds__(256, (D <= 128 ? 4 : 2)) void interaction_fwd_kerne
     // live across the loads, the compiler parks the new value in a second register and copies it at the loop latch
     // behind an `s_waitcnt vmcnt(0)` — a full stop for every load AND store of the iteration.)
     float* orow = out + static_cast<int64_t>(b) * out_stride;
-    if (ABL != 1 && lane < D / 4) {
+    if (lane < D / 4) {
       if (vec_out) {
         st4(orow + lane * 4, dpass);
       } else {  // rows of D + P floats are not 16-B aligned in general: scalar stores
@@ -167,11 +149,6 @@ __global__ __launch_bounds__(256, (D <= 128 ? 4 : 2)) void interaction_fwd_kerne
     // zs is private to the wave and LDS operations of a wave execute in order: a compiler barrier is
     // enough (a memory fence here would also wait for the global loads just issued)
     __builtin_amdgcn_wave_barrier();
-    if (ABL == 1) {  // keep the computation alive without writing the row
-      if (zs[lane] == 1.2345e-31f) orow[0] = zs[lane];
-      __builtin_amdgcn_wave_barrier();
-      continue;
-    }
     // Straight-line stores (fixed trip counts, predicated): inside a loop with a run-time trip count the compiler puts a
     // full `s_waitcnt vmcnt(0)` in front of the stores, i.e. the wave would sit out the whole latency of the next
     // sample's loads it has just issued before it stores this sample (seen in the ISA; cost ~60 of 270 us).
@@ -187,10 +164,7 @@ __global__ __launch_bounds__(256, (D <= 128 ? 4 : 2)) void interaction_fwd_kerne
 #pragma unroll
       for (int t = 0; t < MAXT; ++t) {
         const int p = lane + t * kWave;
-        if (p < P) {
-          if (ABL == 4) __builtin_nontemporal_store(zs[p], orow + D + p);
-          else orow[D + p] = zs[p];
-        }
+        if (p < P) orow[D + p] = zs[p];
       }
     }
     __builtin_amdgcn_wave_barrier();  // zs is rewritten by the next sample
@@ -243,16 +217,11 @@ __device__ __forceinline__ void vm_wait_all_but(int n) {
 //     microseconds under load, per sample and per wave).  The dense [B, D + P] layout therefore stores through
 //     vm_store_dword — a fixed number of store instructions per sample, every lane active (lanes past the end repeat
 //     the last element) — and waits with vmcnt(that number).
-// development aid (tbe_debug_set_interaction_stamps + TBE_INTERACTION_ABLATION=6): the waves of the first 8 workgroups
-// write 6 cycle-counter stamps per sample for their first 32 samples
-static uint64_t* g_interaction_stamps = nullptr;
-constexpr int kStampBlocks = 8, kStampIters = 32, kStampsPerIter = 6;
-
-template <int D, int ABL = 0>  // ABL (tuning runs): 1 = no output stores, 2 = no MFMA, 5 = copies only, 6 = stamps
+template <int D>
 __global__ __launch_bounds__(256, 2) void interaction_fwd_glds_kernel(const float* __restrict__ dense,
                                                                      const float* __restrict__ sparse,
                                                                      float* __restrict__ out, int B, int F,
-                                                                     int64_t out_stride, uint64_t* stamps) {
+                                                                     int64_t out_stride) {
   extern __shared__ float smem[];
   constexpr int NS = D / 16;
   constexpr int PR = D / 4;          // 16-B pieces per row
@@ -299,25 +268,12 @@ __global__ __launch_bounds__(256, 2) void interaction_fwd_glds_kernel(const floa
   constexpr int DS = (D + kWave - 1) / kWave;  // dense pass-through stores per sample
   int stores_behind_copy = 0;
   int b = blockIdx.x * 4 + wave;
-  int iter = 0;
-  auto stamp = [&](int k) {
-    if (ABL == 6 && stamps != nullptr && blockIdx.x < kStampBlocks && iter < kStampIters && lane == 0)
-      stamps[((blockIdx.x * 4 + wave) * kStampIters + iter) * kStampsPerIter + k] = clock64();
-  };
   if (b < B) issue_copy(b);
-  for (; b < B; b += stride_b, ++iter) {
-    stamp(0);
+  for (; b < B; b += stride_b) {
     // the copy of sample b has landed once everything but the stores issued after it has retired (an LDS-DMA counts
     // on the VM counter like a load; operations retire in issue order)
     vm_wait_all_but(stores_behind_copy);
     __builtin_amdgcn_wave_barrier();
-    stamp(1);
-    if (ABL == 5) {
-      if (xs[lane] == 1.2345e-31f) out[b] = 1.f;  // keep the copy alive
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (b + stride_b < B) issue_copy(b + stride_b);
-      continue;
-    }
     float4 xa[NS], xb[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) xa[s] = *reinterpret_cast<const float4*>(xs + row0 * D + 4 * ((4 * s + kq) ^ (row0 & 15)));
@@ -339,9 +295,7 @@ __global__ __launch_bounds__(256, 2) void interaction_fwd_glds_kernel(const floa
     // every read of the image has returned before the next copy may overwrite it
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    stamp(2);
     if (b + stride_b < B) issue_copy(b + stride_b);
-    stamp(3);
     f32x4 acc00 = {0.f, 0.f, 0.f, 0.f}, acc01 = acc00, acc11 = acc00;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -349,22 +303,12 @@ __global__ __launch_bounds__(256, 2) void interaction_fwd_glds_kernel(const floa
       const float a1[4] = {xb[s].x, xb[s].y, xb[s].z, xb[s].w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (ABL == 2) {
-          acc00[0] += a0[e];
-          acc01[0] += a1[e];
-          continue;
-        }
         acc00 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], a0[e], acc00, 0, 0, 0);
         acc01 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], a1[e], acc01, 0, 0, 0);
         acc11 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], a1[e], acc11, 0, 0, 0);
       }
     }
     float* orow = out + static_cast<int64_t>(b) * out_stride;
-    if (ABL == 1) {
-      if (acc00[0] + acc01[1] + acc11[2] + dpass.x + dscal[0] == 1.2345e-31f) orow[0] = 1.f;
-      stores_behind_copy = 0;
-      continue;
-    }
     if (vec_out) {
       if (dense_lane) st4(orow + lane * 4, dpass);
     } else {
@@ -380,10 +324,6 @@ __global__ __launch_bounds__(256, 2) void interaction_fwd_glds_kernel(const floa
       if (i < j && 16 + j < R) zs[triu_index(16 + i, 16 + j, R)] = acc11[q];
     }
     __builtin_amdgcn_wave_barrier();
-    if (ABL == 6) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      stamp(4);
-    }
     constexpr int MAXT = 8;
     constexpr int MAXQ = 2;
     if (vec_out) {
@@ -403,7 +343,6 @@ __global__ __launch_bounds__(256, 2) void interaction_fwd_glds_kernel(const floa
         if (t < T) vm_store_dword(orow + D + min(lane + t * kWave, P - 1), zv[t]);
       stores_behind_copy = DS + T;
     }
-    stamp(5);
     __builtin_amdgcn_wave_barrier();
   }
 }
@@ -589,34 +528,7 @@ extern "C" int tbe_dlrm_interaction_forward_f32(const float* dense, const float*
   // persistent-style: 4 workgroups per CU (2 at D = 256), each wave strides over samples
   const int64_t want = (static_cast<int64_t>(B) + 3) / 4;
   const dim3 grid(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(want, 256 * (D <= 128 ? 4 : 2)))));
-  static const int ablation = [] {
-    const char* e = getenv("TBE_INTERACTION_ABLATION");  // tuning runs only
-    return e ? atoi(e) : 0;
-  }();
-  static const bool reg_form = [] {
-    const char* e = getenv("TBE_INTERACTION_FORM");  // "reg": the register-operand kernel at every D (tuning runs)
-    return e && e[0] == 'r';
-  }();
-  const bool glds_form = (D == 64 || D == 128) && !reg_form;
-  if (!glds_form && ablation == 1 && D == 128) {
-    hipLaunchKernelGGL((interaction_fwd_kernel<128, 1>), grid, dim3(256), lds, st, dense, sparse, out, B, F, out_row_stride);
-    TBE_CHECK_LAUNCH("tbe_dlrm_interaction_forward_f32");
-    return TBE_OK;
-  }
-  if (!glds_form && (ablation == 3 || ablation == 4) && D == 128) {
-    if (ablation == 3)
-      hipLaunchKernelGGL((interaction_fwd_kernel<128, 3>), grid, dim3(256), lds, st, dense, sparse, out, B, F, out_row_stride);
-    else
-      hipLaunchKernelGGL((interaction_fwd_kernel<128, 4>), grid, dim3(256), lds, st, dense, sparse, out, B, F, out_row_stride);
-    TBE_CHECK_LAUNCH("tbe_dlrm_interaction_forward_f32");
-    return TBE_OK;
-  }
-  if (!glds_form && ablation == 2 && D == 128) {
-    hipLaunchKernelGGL((interaction_fwd_kernel<128, 2>), grid, dim3(256), lds, st, dense, sparse, out, B, F, out_row_stride);
-    TBE_CHECK_LAUNCH("tbe_dlrm_interaction_forward_f32");
-    return TBE_OK;
-  }
-  if (glds_form) {
+  if (D == 64 || D == 128) {
     // LDS-DMA form: one [rows, D] image + the pair block per wave, 2 workgroups per CU
     const int rpi = 64 / (D / 4);
     const int rows = (R + rpi - 1) / rpi * rpi;
@@ -624,27 +536,17 @@ extern "C" int tbe_dlrm_interaction_forward_f32(const float* dense, const float*
     static bool glds_attr = false;
     if (!glds_attr) {
       const size_t big = 4 * (static_cast<size_t>(32) * 128 + 496) * sizeof(float);
-      if (!reserve_lds(interaction_fwd_glds_kernel<128>, big) || !reserve_lds(interaction_fwd_glds_kernel<64>, big) ||
-          !reserve_lds(interaction_fwd_glds_kernel<128, 1>, big) || !reserve_lds(interaction_fwd_glds_kernel<128, 2>, big) ||
-          !reserve_lds(interaction_fwd_glds_kernel<128, 5>, big) || !reserve_lds(interaction_fwd_glds_kernel<128, 6>, big)) {
+      if (!reserve_lds(interaction_fwd_glds_kernel<128>, big) || !reserve_lds(interaction_fwd_glds_kernel<64>, big)) {
         set_error("tbe_dlrm_interaction_forward_f32: cannot reserve LDS");
         return TBE_ERR_LAUNCH;
       }
       glds_attr = true;
     }
     const dim3 grid_g(static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(want, 256 * 2))));
-    if (D == 128 && ablation == 1)
-      hipLaunchKernelGGL((interaction_fwd_glds_kernel<128, 1>), grid_g, dim3(256), lds_g, st, dense, sparse, out, B, F, out_row_stride, g_interaction_stamps);
-    else if (D == 128 && ablation == 2)
-      hipLaunchKernelGGL((interaction_fwd_glds_kernel<128, 2>), grid_g, dim3(256), lds_g, st, dense, sparse, out, B, F, out_row_stride, g_interaction_stamps);
-    else if (D == 128 && ablation == 6)
-      hipLaunchKernelGGL((interaction_fwd_glds_kernel<128, 6>), grid_g, dim3(256), lds_g, st, dense, sparse, out, B, F, out_row_stride, g_interaction_stamps);
-    else if (D == 128 && ablation == 5)
-      hipLaunchKernelGGL((interaction_fwd_glds_kernel<128, 5>), grid_g, dim3(256), lds_g, st, dense, sparse, out, B, F, out_row_stride, g_interaction_stamps);
-    else if (D == 128)
-      hipLaunchKernelGGL(interaction_fwd_glds_kernel<128>, grid_g, dim3(256), lds_g, st, dense, sparse, out, B, F, out_row_stride, g_interaction_stamps);
+    if (D == 128)
+      hipLaunchKernelGGL(interaction_fwd_glds_kernel<128>, grid_g, dim3(256), lds_g, st, dense, sparse, out, B, F, out_row_stride);
     else
-      hipLaunchKernelGGL(interaction_fwd_glds_kernel<64>, grid_g, dim3(256), lds_g, st, dense, sparse, out, B, F, out_row_stride, g_interaction_stamps);
+      hipLaunchKernelGGL(interaction_fwd_glds_kernel<64>, grid_g, dim3(256), lds_g, st, dense, sparse, out, B, F, out_row_stride);
     TBE_CHECK_LAUNCH("tbe_dlrm_interaction_forward_f32");
     return TBE_OK;
   }
@@ -652,17 +554,10 @@ extern "C" int tbe_dlrm_interaction_forward_f32(const float* dense, const float*
   switch (D) {
     case 16: TBE_IF(16); break;
     case 32: TBE_IF(32); break;
-    case 64: TBE_IF(64); break;
-    case 128: TBE_IF(128); break;
     default: TBE_IF(256); break;
   }
 #undef TBE_IF
   TBE_CHECK_LAUNCH("tbe_dlrm_interaction_forward_f32");
-  return TBE_OK;
-}
-
-extern "C" int tbe_debug_set_interaction_stamps(void* device_buffer) {
-  g_interaction_stamps = static_cast<uint64_t*>(device_buffer);
   return TBE_OK;
 }
 

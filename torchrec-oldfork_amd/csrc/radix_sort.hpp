@@ -47,14 +47,6 @@ constexpr uint32_t kCountMask = (1u << kTagShift) - 1u;
 constexpr int64_t kSortMaxPairs = 1ll << kTagShift;  // pairs per sort (the count field of a histogram word)
 constexpr int kSpinLimit = 1 << 20;  // polls per thread before it gives up (~1 s)
 
-// development aid: when set (tbe_debug_set_sort_stamps), every segment writes 8 wall-clock stamps (100 MHz) per pass
-static uint64_t* g_sort_stamps = nullptr;
-#define TBE_SORT_STAMP(i)                                                                          \
-  do {                                                                                             \
-    if (a.stamps != nullptr && threadIdx.x == 0)                                                   \
-      a.stamps[(static_cast<size_t>(a.pass) * kSortMaxBlocks + b) * 8 + (i)] = wall_clock64();     \
-  } while (0)
-
 // Spin-wait give-ups (a predecessor never published within kSpinLimit polls): nothing hangs, but the prefix sums — and
 // with them the sorted order — are garbage then.  Every give-up is written to the library's FAULT WORD (error.cpp: a
 // line of GPU-mapped host memory), which the host side reads without a sync (tbe_fault_status) and turns into an
@@ -245,7 +237,6 @@ struct RadixPassArgs {
   const uint32_t* totals;  // [radix] digit totals of this pass
   uint32_t* next_totals;   // [radix] digit totals of the next pass, accumulated by this one (or nullptr)
   uint32_t* ticket;        // this pass's ticket counter
-  uint64_t* stamps;        // debug: [passes][kSortMaxBlocks][8] or nullptr
   uint32_t* fault;         // the library's fault word (never nullptr)
 };
 
@@ -291,7 +282,6 @@ __global__ __launch_bounds__(kSortThreads) void radix_pass_kernel(const RadixPas
   };
 
   // ---- ticket: segment index = arrival order ----------------------------------------------------------
-  const uint64_t t_start = a.stamps != nullptr ? wall_clock64() : 0ull;
   if (tid == 0) s_block = atomicAdd(a.ticket, 1u);
   for (int d = tid; d < radix; d += kSortThreads) {
     s_seg[d] = 0;
@@ -303,8 +293,6 @@ __global__ __launch_bounds__(kSortThreads) void radix_pass_kernel(const RadixPas
   const uint32_t t1 = (2 * tid + 1 < radix) ? a.totals[2 * tid + 1] : 0u;
   __syncthreads();
   const uint32_t b = s_block;
-  TBE_SORT_STAMP(0);
-  if (a.stamps != nullptr && tid == 0) a.stamps[(static_cast<size_t>(a.pass) * kSortMaxBlocks + b) * 8 + 7] = t_start;
   const int64_t seg_begin = static_cast<int64_t>(b) * T * TILE;
   const int64_t seg_end = min(a.N, seg_begin + static_cast<int64_t>(T) * TILE);
   if (T == 1) load_tile(seg_begin, seg_end);
@@ -358,7 +346,6 @@ __global__ __launch_bounds__(kSortThreads) void radix_pass_kernel(const RadixPas
     __syncthreads();
   }
   const uint32_t* seg_hist = (T == 1) ? s_hist : s_seg;
-  TBE_SORT_STAMP(1);
 
   // ---- publish this segment's histogram row: the word is its own ready flag ------------------------
   uint32_t* my_row = a.table + static_cast<size_t>(b) * radix;
@@ -431,7 +418,6 @@ __global__ __launch_bounds__(kSortThreads) void radix_pass_kernel(const RadixPas
     uint32_t a0 = 0, a1 = 0, own0, own1, up0, up1;
     sum_rows(a.table, grp * kSortGroup, in_grp, a0, a1);
     reduce_split(a0, a1, own0, own1);
-    TBE_SORT_STAMP(2);
     if (in_grp == kSortGroup - 1 && 2 * tid < radix) {  // block-uniform condition: this segment closes its group
       uint32_t* grow = a.group_table + static_cast<size_t>(grp) * radix;
       __hip_atomic_store(&grow[2 * tid], (epoch << kTagShift) | (own0 + seg_hist[2 * tid]), __ATOMIC_RELAXED,
@@ -442,7 +428,6 @@ __global__ __launch_bounds__(kSortThreads) void radix_pass_kernel(const RadixPas
     a0 = a1 = 0;
     sum_rows(a.group_table, 0, grp, a0, a1);
     reduce_split(a0, a1, up0, up1);
-    TBE_SORT_STAMP(3);
     // the next pass's digit totals: fire-and-forget integer atomics behind the waits, complete at the end of
     // this launch
     if (count_next) {
@@ -458,7 +443,6 @@ __global__ __launch_bounds__(kSortThreads) void radix_pass_kernel(const RadixPas
       s_gbase[2 * tid + 1] = base0 + t0 + own1 + up1;
     }
     __syncthreads();
-    TBE_SORT_STAMP(4);
   }
 
   // ---- place: tile by tile, LDS-staged so that the global writes are contiguous runs ----------------
@@ -500,7 +484,6 @@ __global__ __launch_bounds__(kSortThreads) void radix_pass_kernel(const RadixPas
       }
     }
     __syncthreads();
-    TBE_SORT_STAMP(5);
     const int count = static_cast<int>(min<int64_t>(TILE, seg_end - tile_begin));
     for (int i = tid; i < count; i += kSortThreads) {
       const KeyT key = stage_k[i];
@@ -511,7 +494,6 @@ __global__ __launch_bounds__(kSortThreads) void radix_pass_kernel(const RadixPas
       }
     }
     __syncthreads();
-    TBE_SORT_STAMP(6);
   }
 }
 
@@ -564,7 +546,6 @@ inline int radix_sort_pairs(KeyT* k0, KeyT* k1, ValT* v0, ValT* v1, int64_t N, i
     a.group_table = ws.group_table;
     a.totals = ws.totals + static_cast<size_t>(radix) * p;
     a.ticket = ws.tickets + p;
-    a.stamps = g_sort_stamps;
     a.fault = fault;
     const dim3 grid(static_cast<unsigned>(g.blocks)), block(kSortThreads);
     bool launched = true;

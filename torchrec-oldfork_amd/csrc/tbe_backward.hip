@@ -191,7 +191,7 @@ __device__ __forceinline__ float group_sum(float v) {
 // Applies the optimizer to one table row.  `g` = coalesced gradient columns held by this lane,
 // `w` = current weight columns (pre-loaded).  Group-uniform control flow.
 // OPTC >= 0 fixes the optimizer at compile time (smaller live state => more waves per SIMD).
-template <int G, int NV, int OPTC = -1, int ABL = 0>
+template <int G, int NV, int OPTC = -1>
 __device__ __forceinline__ void apply_row(const BwdArgs& a, int f, int64_t local_row, int D,
                                           bool vec, int gl, float* wrow, float4 (&w)[NV],
                                           float4 (&g)[NV]) {
@@ -207,7 +207,7 @@ __device__ __forceinline__ void apply_row(const BwdArgs& a, int f, int64_t local
         r.y = fmaf(-lr, g[v].y, w[v].y);
         r.z = fmaf(-lr, g[v].z, w[v].z);
         r.w = fmaf(-lr, g[v].w, w[v].w);
-        if (ABL == 0 || r.x == 1.2345e-31f) stc(wrow, d, D, vec, r);  // ABL: tuning runs without the row write
+        stc(wrow, d, D, vec, r);
       }
     }
   } else if (optimizer == TBE_OPT_EXACT_ROWWISE_ADAGRAD) {
@@ -309,7 +309,7 @@ struct BwdUnroll {
 
 // FAST: every feature has dim a.fast_D (multiple of 4), SUM pooling, no per-sample weights, every
 // row base 16-B aligned (TBE_FLAG_UNIFORM_ALIGNED from the host) — the Criteo configuration.
-template <typename KeyT, typename PayT, int G, int NV, int OPTC, bool FAST, int U, int MINW, int ABL = 0>
+template <typename KeyT, typename PayT, int G, int NV, int OPTC, bool FAST, int U, int MINW>
 __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
   constexpr int NG = kWave / G;
   const int lane = threadIdx.x & 63;
@@ -415,8 +415,8 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
           const int d = (v * G + gl) * 4;
           x[u][v] = (val[u] && d < Du[u]) ? ldc(gp, d, Du[u], gvec) : make_float4(0.f, 0.f, 0.f, 0.f);
           // the current weight row (not needed when the coalesced gradient is only written out: DENSE_GRAD)
-          wr[u][v] = (ABL != 2 && OPTC != TBE_OPT_DENSE_GRAD && lst[u] && d < Du[u]) ? ldc(wp[u], d, Du[u], vecu[u])
-                                                                                        : make_float4(0.f, 0.f, 0.f, 0.f);
+          wr[u][v] = (OPTC != TBE_OPT_DENSE_GRAD && lst[u] && d < Du[u]) ? ldc(wp[u], d, Du[u], vecu[u])
+                                                                          : make_float4(0.f, 0.f, 0.f, 0.f);
         }
       }
 #pragma unroll
@@ -433,7 +433,7 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
           if (lst[u]) {
             if (started_here) {
               ++nrows;
-              apply_row<G, NV, OPTC, ABL>(a, fu[u], lrow[u], Du[u], vecu[u], gl, const_cast<float*>(wp[u]), wr[u], acc);
+              apply_row<G, NV, OPTC>(a, fu[u], lrow[u], Du[u], vecu[u], gl, const_cast<float*>(wp[u]), wr[u], acc);
             } else {
               float* pf = a.partial_first + chunk * a.max_D_pad;
 #pragma unroll
@@ -650,12 +650,6 @@ __global__ __launch_bounds__(256) void bwd_fixup_kernel(BwdArgs a) {
 }
 
 static int pick_chunk(int64_t N) {
-  static const int forced = [] {
-    const char* e = getenv("TBE_BWD_CHUNK");  // tuning knob (multiple of 8 in [8, 1024])
-    const int v = e ? atoi(e) : 0;
-    return (v >= 8 && v <= 1024 && v % 8 == 0) ? v : 0;
-  }();
-  if (forced) return forced;
   int64_t c = (N + 16383) / 16384;
   c = (c + 31) / 32 * 32;
   if (c < 32) c = 32;
@@ -706,35 +700,23 @@ static int launch_update(const BwdArgs& a, hipStream_t st) {
   const unsigned grid = static_cast<unsigned>((nchunks + groups_per_block - 1) / groups_per_block);
   {
     ProfileSpan span(TBE_PROFILE_BWD_UPDATE_KERNEL, st);
-    constexpr int UG = BwdUnroll<NV>::U;
-    static const int variant = [] {
-      const char* e = getenv("TBE_BWD_VARIANT");
-      return e ? atoi(e) : 0;
-    }();
     const bool fast = a.fast_D > 0 && a.pooling_mode == TBE_POOL_SUM && a.psw == nullptr;
     const int oc = a.opt.optimizer;
 #define TBE_UPD(OPTC, FAST_, UU, MW) \
   hipLaunchKernelGGL((bwd_update_kernel<KeyT, PayT, G, NV, OPTC, FAST_, UU, MW>), dim3(grid), dim3(256), 0, st, a)
-    if (fast && G == 32 && NV == 1 && oc == TBE_OPT_EXACT_SGD) {
-      switch (variant) {
-        case 1: TBE_UPD(TBE_OPT_EXACT_SGD, true, 4, 8); break;
-        case 2: TBE_UPD(TBE_OPT_EXACT_SGD, true, 2, 8); break;
-        case 3: TBE_UPD(TBE_OPT_EXACT_SGD, true, 8, 4); break;
-        case 4: TBE_UPD(TBE_OPT_EXACT_SGD, true, 2, 4); break;
-        case 5:  // tuning: no row write
-          hipLaunchKernelGGL((bwd_update_kernel<KeyT, PayT, G, NV, TBE_OPT_EXACT_SGD, true, 4, 4, 1>), dim3(grid), dim3(256), 0, st, a);
-          break;
-        case 6:  // tuning: no row read, no row write (gradient streaming only)
-          hipLaunchKernelGGL((bwd_update_kernel<KeyT, PayT, G, NV, TBE_OPT_EXACT_SGD, true, 4, 4, 2>), dim3(grid), dim3(256), 0, st, a);
-          break;
-        default: TBE_UPD(TBE_OPT_EXACT_SGD, true, 4, 4); break;
+    // the fast kernels exist for the one (G, NV) pair that can reach them
+    if constexpr (G == 32 && NV == 1) {
+      if (fast && oc == TBE_OPT_EXACT_SGD) {
+        TBE_UPD(TBE_OPT_EXACT_SGD, true, 4, 4);
+      } else if (fast && oc == TBE_OPT_EXACT_ROWWISE_ADAGRAD) {
+        TBE_UPD(TBE_OPT_EXACT_ROWWISE_ADAGRAD, true, 4, 4);
+      } else if (fast && oc == TBE_OPT_DENSE_GRAD) {
+        TBE_UPD(TBE_OPT_DENSE_GRAD, true, 4, 4);  // the replicated tiny tables of a sharded collection (dense gradient)
+      } else {
+        TBE_UPD(-1, false, BwdUnroll<NV>::U, 1);
       }
-    } else if (fast && G == 32 && NV == 1 && oc == TBE_OPT_EXACT_ROWWISE_ADAGRAD) {
-      TBE_UPD(TBE_OPT_EXACT_ROWWISE_ADAGRAD, true, 4, 4);
-    } else if (fast && G == 32 && NV == 1 && oc == TBE_OPT_DENSE_GRAD) {
-      TBE_UPD(TBE_OPT_DENSE_GRAD, true, 4, 4);  // the replicated tiny tables of a sharded collection (dense gradient)
     } else {
-      TBE_UPD(-1, false, UG, 1);
+      TBE_UPD(-1, false, BwdUnroll<NV>::U, 1);
     }
 #undef TBE_UPD
   }
@@ -903,8 +885,7 @@ static int backward_entry(
   a.unique_rows = (phase & kPhaseApply) ? profile_unique_rows_counter() : nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // payload width: the bag number alone unless positions are needed (per-sample weights, unpooled rows)
-  static const bool force_wide = getenv("TBE_BWD_WIDE_PAYLOAD") != nullptr;  // development A/B switch
-  const bool wide = force_wide || pooling_mode == TBE_POOL_NONE || (flags & TBE_FLAG_WEIGHTED) != 0;
+  const bool wide = pooling_mode == TBE_POOL_NONE || (flags & TBE_FLAG_WEIGHTED) != 0;
   if (key_bits > 32)
     return wide ? run_backward<uint64_t, uint64_t>(a, w, max_D, st, phase) : run_backward<uint64_t, uint32_t>(a, w, max_D, st, phase);
   return wide ? run_backward<uint32_t, uint64_t>(a, w, max_D, st, phase) : run_backward<uint32_t, uint32_t>(a, w, max_D, st, phase);
@@ -1014,10 +995,5 @@ extern "C" int tbe_debug_inject_sort_giveup(void* stream) {
   TBE_REQUIRE(fault != nullptr, "tbe_debug_inject_sort_giveup: no fault word (no HIP device?)");
   hipLaunchKernelGGL(inject_sort_giveup_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), fault);
   TBE_CHECK_LAUNCH("tbe_debug_inject_sort_giveup");
-  return TBE_OK;
-}
-
-extern "C" int tbe_debug_set_sort_stamps(void* device_buffer) {
-  g_sort_stamps = static_cast<uint64_t*>(device_buffer);
   return TBE_OK;
 }

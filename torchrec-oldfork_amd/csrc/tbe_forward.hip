@@ -451,11 +451,7 @@ extern "C" int tbe_forward_pooled_f32(const uint64_t* feat_weights, const int32_
   const bool weighted = per_sample_weights != nullptr;
   const bool mean = pooling_mode == TBE_POOL_MEAN;
   const double avg_len = static_cast<double>(N) / (static_cast<double>(F) * B);
-  static const double long_min = [] {
-    const char* e = getenv("TBE_FWD_LONG_MIN");  // tuning knob
-    return e ? atof(e) : 3.5;  // measured on MI355X: the wave-per-bag kernel wins from ~4 ids per bag
-  }();
-  const bool long_bags = avg_len >= long_min;
+  const bool long_bags = avg_len >= 3.5;  // measured on MI355X: the wave-per-bag kernel wins from ~4 ids per bag
   if (max_D <= 64) return launch_fwd<16, 1>(a, weighted, mean, long_bags, st);
   if (max_D <= 128) return launch_fwd<32, 1>(a, weighted, mean, long_bags, st);
   if (max_D <= 256) return launch_fwd<64, 1>(a, weighted, mean, long_bags, st);

@@ -84,8 +84,6 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_size, c_void_p],
     ),
     "tbe_debug_sort_timeouts": (ctypes.c_int, [ctypes.POINTER(c_i64)]),
-    "tbe_debug_set_sort_stamps": (ctypes.c_int, [c_void_p]),
-    "tbe_debug_set_interaction_stamps": (ctypes.c_int, [c_void_p]),
     "tbe_backward_apply_f32": (
         ctypes.c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,

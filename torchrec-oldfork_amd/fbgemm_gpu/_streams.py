@@ -7,13 +7,11 @@ holds the compute kernels behind it back.  Which pool stream lands on which queu
 through the HIP API, but it is measurable: `shares_hw_queue` runs a ~0.3-ms spin kernel on one stream and a tiny kernel on
 the other and looks at when the tiny one finished (rocprofv3's kernel trace shows the same in its Queue_Id
 column).  `side_stream` draws pool streams until it finds one on another queue than the device's default stream (and,
-if it can, than the side streams handed out before).  TBE_STREAM_PROBE=0: take the first pool stream, as before."""
-import os
+if it can, than the side streams handed out before)."""
 from typing import Dict, List, Optional
 
 import torch
 
-_PROBE = os.environ.get("TBE_STREAM_PROBE", "1") == "1"
 _cycles: Dict[int, int] = {}
 _handed_out: Dict[int, List[torch.cuda.Stream]] = {}
 _scratch: Dict[int, torch.Tensor] = {}
@@ -58,18 +56,18 @@ def shares_hw_queue(a: torch.cuda.Stream, b: torch.cuda.Stream) -> bool:
         return s0.elapsed_time(e1) > 0.5 * s0.elapsed_time(s1)
 
 
-def side_stream(device: torch.device, priority: int = 0, tries: int = 12) -> torch.cuda.Stream:
+def side_stream(device: torch.device, tries: int = 12) -> torch.cuda.Stream:
     """A stream of the pool that does not share a hardware queue with the device's default stream (where the compute
     runs) nor, if possible, with the side streams handed out before."""
     device = torch.device(device)
-    if not _PROBE or torch.cuda.is_current_stream_capturing():
-        return torch.cuda.Stream(device, priority=priority)
+    if torch.cuda.is_current_stream_capturing():
+        return torch.cuda.Stream(device)
     with torch.cuda.device(device):
         default = torch.cuda.default_stream(device)
         others = _handed_out.setdefault(device.index, [])
         fallback: Optional[torch.cuda.Stream] = None
         for _ in range(tries):
-            s = torch.cuda.Stream(device, priority=priority)
+            s = torch.cuda.Stream(device)
             if shares_hw_queue(s, default):
                 continue
             if fallback is None:
@@ -77,6 +75,6 @@ def side_stream(device: torch.device, priority: int = 0, tries: int = 12) -> tor
             if not any(shares_hw_queue(s, o) for o in others[-2:]):
                 fallback = s
                 break
-        s = fallback if fallback is not None else torch.cuda.Stream(device, priority=priority)
+        s = fallback if fallback is not None else torch.cuda.Stream(device)
         others.append(s)
         return s

@@ -70,13 +70,6 @@ def _gather_rows(mat: torch.Tensor, order: List[int], order_dev: torch.Tensor) -
         return mat.new_empty((0, mat.shape[1]))
     if order == list(range(order[0], order[0] + len(order))):
         return mat[order[0]:order[0] + len(order)]
-    if os.environ.get("TORCHREC_AMD_GATHER") == "cat":
-        runs, start = [], 0
-        for i in range(1, len(order) + 1):
-            if i == len(order) or order[i] != order[i - 1] + 1:
-                runs.append(mat[order[start]:order[i - 1] + 1])
-                start = i
-        return torch.cat(runs, dim=0)
     if mat.is_cuda and mat.is_contiguous() and (mat.shape[1] * mat.element_size()) % 16 == 0 and mat.data_ptr() % 16 == 0:
         from . import _device_ops  # noqa: F401  (registers torch.ops.tbe_hip.*)
         return torch.ops.tbe_hip.copy_rows(mat, order_dev)
@@ -604,15 +597,6 @@ class ShardedEmbeddingBagCollection(nn.Module):
             for t, w in zip(self._dp_table_ids, self._dp_module.split_embedding_weights()):
                 w.uniform_(cfgs[t].get_weight_init_min(), cfgs[t].get_weight_init_max())
             self._dp_out_off = torch.tensor([out_col[g] for g in self._dp_feats], dtype=torch.int64, device=dev)
-
-    def defer_backward_sort(self, on: bool = True) -> None:
-        """Lets the caller choose when the fused lookup's backward sort starts (launch_deferred_backward_sort)."""
-        if self._emb_module is not None:
-            self._emb_module.defer_backward_sort = bool(on)
-
-    def launch_deferred_backward_sort(self) -> bool:
-        m = self._emb_module
-        return bool(m is not None and hasattr(m, "launch_deferred_backward_sort") and m.launch_deferred_backward_sort())
 
     def set_output_buffer(self, buf: Optional[torch.Tensor]) -> None:
         """A persistent float32 buffer of B_local * sum(D) elements that receives the pooled output of every

@@ -52,15 +52,8 @@ class _PipelinedEBC:
 
 class TrainPipelineSparseDist:
     def __init__(self, model: torch.nn.Module, optimizer: Any, device: torch.device, hip_graphs: bool = False,
-                 wgrad_overlap: Optional[bool] = None, prefetch_lookup: Optional[bool] = None) -> None:
+                 prefetch_lookup: Optional[bool] = None) -> None:
         self._model, self._optimizer, self._device = model, optimizer, device
-        # wgrad_overlap: the dense layers' weight-gradient GEMMs of an eager step run on a side stream, joined right
-        # after backward (modules/mlp.py _WgradOverlap).  Opt-in (argument or TORCHREC_AMD_WGRAD_OVERLAP=1), and only
-        # when nothing in the model is wrapped in DistributedDataParallel: measured on MI355X at batch 65 536 the step
-        # gets 3 % SLOWER (8.81 vs 8.56 ms) — two MFMA-bound GEMMs sharing the chip lose more than the HBM-bound passes
-        # beside them gain, and the device offers no stream priority below the default to confine the side stream to
-        # idle CUs.
-        self._setup_wgrad_overlap(wgrad_overlap)
         # hip_graphs: capture the model's collective-free dense segments as HIP graphs on the first
         # batch (models that offer `capture_hip_graphs(batch_size)`, distributed/hip_graph.py)
         # Under DistributedDataParallel the capture must happen BEFORE the DDP wrap (capturing a backward
@@ -91,26 +84,6 @@ class TrainPipelineSparseDist:
         self._sharded = dmp.sharded_modules() if dmp is not None else []
         self._install()
 
-    def _setup_wgrad_overlap(self, want: Optional[bool]) -> None:
-        import os
-
-        from torch.nn.parallel import DistributedDataParallel
-
-        from ..modules.mlp import _WgradOverlap
-
-        root = self._model.module if isinstance(self._model, DistributedModelParallel) else self._model
-        ok = (self._device.type == "cuda" and hasattr(root, "finish_dense_grads")
-              and not any(isinstance(m, DistributedDataParallel) for m in self._model.modules()))
-        if want is None:
-            want = os.environ.get("TORCHREC_AMD_WGRAD_OVERLAP", "0") == "1"
-        self._wgrad_overlap = bool(want and ok)
-        # eager steps: the dense gradients' final reductions in one launch (modules/mlp.py _DeferredFinish): the same
-        # preconditions (this pipeline calls finish_dense_grads() right after backward, no DistributedDataParallel hooks).
-        # Opt-in (TORCHREC_AMD_DEFERRED_FINISH=1): measured neutral at batch 65 536 (8.549 / 8.573 ms with, 8.504 / 8.560
-        # without, same box) — an eager step of that size is bound by bytes, not by its 16 small launches; the graph-mode
-        # counterpart (hip_graph.py write_sinks) is what pays, at the per-rank batches of N > 1.
-        self._deferred_finish = bool(ok and os.environ.get("TORCHREC_AMD_DEFERRED_FINISH", "0") == "1")
-
     def _install(self) -> None:
         self._wrappers: List[_PipelinedEBC] = []
         for s in self._sharded:
@@ -136,18 +109,6 @@ class TrainPipelineSparseDist:
         with label("## prefetch_next_lookup ##"):
             step = w.compute_explicit(nxt.sparse_features, prefetched=True)
         return (nxt.sparse_features, step) if step is not None else None
-
-    def _run_backward(self, losses) -> None:
-        if self._wgrad_overlap:
-            from ..modules.mlp import _WgradOverlap
-
-            _WgradOverlap.enable(self._device)  # for this backward only: joined right below
-            try:
-                torch.sum(losses, dim=0).backward()
-            finally:
-                _WgradOverlap.disable()
-        else:
-            torch.sum(losses, dim=0).backward()
 
     def _to_device(self, batch, non_blocking: bool):
         return batch.to(self._device, non_blocking=non_blocking) if batch is not None else None
@@ -255,16 +216,7 @@ class TrainPipelineSparseDist:
                 self._optimizer.step()
         elif self._model.training:
             with label("## backward ##"):  # train_pipeline.py:546
-                from ..modules.mlp import _DeferredFinish
-
-                deferred = self._deferred_finish
-                if deferred:
-                    _DeferredFinish.enable()
-                try:
-                    self._run_backward(losses)
-                finally:
-                    if deferred:
-                        _DeferredFinish.disable()  # flushes
+                torch.sum(losses, dim=0).backward()
             with label("## optimizer ##"):
                 if hasattr(root, "finish_dense_grads"):
                     root.finish_dense_grads()  # flat-buffer gradient all-reduce of graphed segments (models/dlrm.py)

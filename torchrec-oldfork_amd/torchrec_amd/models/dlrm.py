@@ -46,15 +46,6 @@ class SparseArch(nn.Module):
         return self._sparse_feature_names
 
 
-# Where the embedding backward's side-stream sort starts: "lookup" (default) = right behind the lookup kernel, beside the
-# bottom MLP (measured best at N = 1: 7.62 M samples/s); "head" = behind the interaction forward, beside the over-arch
-# GEMMs (7.58 M: the GEMMs fill every CU, the sort's launches trickle in).  DESIGN.md §3.
-_SORT_PLACEMENT = os.environ.get("TORCHREC_AMD_SORT_PLACEMENT", "lookup")
-
-
-# HIP-graph + flat-gradient mode: run forward and backward of a step by hand instead of through the autograd engine
-# (DLRMTrain._explicit_step); TORCHREC_AMD_EXPLICIT_STEP=0 keeps the autograd path.
-_EXPLICIT_STEP = os.environ.get("TORCHREC_AMD_EXPLICIT_STEP", "1") != "0"
 # flat mode: capture the head segment's weight-gradient GEMMs into a second backward graph (0: one graph as before)
 _DEFER_WGRAD = os.environ.get("TORCHREC_AMD_DEFER_WGRAD", "1") != "0"
 # Two half-batches per step when the pooled embeddings cross links (DLRMTrain.capture_hip_graphs(half_batches=)):
@@ -101,16 +92,6 @@ _HALF_BATCH_MIN = int(os.environ.get("TORCHREC_AMD_HALF_BATCH_MIN", "32768"))
 
 def _pad64(n: int) -> int:
     return (n + 63) // 64 * 64
-
-
-def _sort_hooks(ebc: nn.Module):
-    """(defer, launch) callables of a collection that lets its caller place the backward sort, or (None, None)."""
-    if _SORT_PLACEMENT != "head":
-        return None, None
-    inner = getattr(ebc, "sharded", ebc)  # (a wrapper object that carries the collection as `.sharded`, if any)
-    if hasattr(inner, "defer_backward_sort") and hasattr(inner, "launch_deferred_backward_sort"):
-        return inner.defer_backward_sort, inner.launch_deferred_backward_sort
-    return None, None
 
 
 class DenseArch(nn.Module):
@@ -250,24 +231,15 @@ class DLRM(nn.Module):
         # The reference runs dense_arch, then sparse_arch (models/dlrm.py:400-401).  Here the lookup and
         # the pooled all-to-all are issued first so that the exchange overlaps the bottom MLP on the
         # collective's own HIP stream; the two branches are independent, results are identical.
-        # The embedding backward's sort (side stream, gradient-independent) is started AFTER the HBM-bound part of the
-        # forward (lookup, interaction) and runs beside the over-arch GEMMs, which are MFMA-bound and leave the
-        # vector units, LDS and memory queues it needs mostly idle.
-        defer, launch = _sort_hooks(self.sparse_arch.embedding_bag_collection)
-        if defer is not None:
-            defer(self.training and torch.is_grad_enabled())
         pending = self.sparse_arch.start(sparse_features)
         embedded_dense = self.dense_arch(dense_features)
         embedded_sparse = self.sparse_arch.finish(pending)
         concatenated = self.inter_arch(dense_features=embedded_dense, sparse_features=embedded_sparse)
-        if launch is not None:
-            launch()
         return self.over_arch(concatenated)
 
 
 # nn.BCEWithLogitsLoss (mean) as ONE kernel for loss + gradient (csrc/mlp_epilogue.hip bce_with_logits_kernel) instead of 8
-# element-wise / reduce kernels forward and 5 backward; TORCHREC_AMD_FUSED_BCE=0 keeps torch's
-_FUSED_BCE = os.environ.get("TORCHREC_AMD_FUSED_BCE", "1") != "0"
+# element-wise / reduce kernels forward and 5 backward
 
 
 class _FusedBCEWithLogits(torch.autograd.Function):
@@ -288,7 +260,7 @@ class _FusedBCEWithLogits(torch.autograd.Function):
 def bce_with_logits_mean(loss_fn: nn.Module, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     """`loss_fn(logits, labels.float())` for the train wrapper's nn.BCEWithLogitsLoss (examples/dlrm/modules/dlrm_train.py);
     on a HIP device, for the plain mean-reduced loss over float32 logits [B], one fused kernel (labels int64 or float)."""
-    if (_FUSED_BCE and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 1 and labels.shape == logits.shape
+    if (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 1 and labels.shape == logits.shape
             and type(loss_fn) is nn.BCEWithLogitsLoss and loss_fn.reduction == "mean" and loss_fn.weight is None
             and loss_fn.pos_weight is None and logits.numel() > 0 and labels.dtype in (torch.float32, torch.int64)):
         return _FusedBCEWithLogits.apply(logits, labels)
@@ -371,7 +343,7 @@ class DLRMTrain(nn.Module):
         if half_batches is None:
             half_batches = _HALF_BATCHES == "1" or (_HALF_BATCHES == "auto" and B >= _HALF_BATCH_MIN)
         halves = bool(half_batches and flat_grads and B % 2 == 0 and getattr(ebc, "_exchange", False)
-                      and hasattr(ebc, "set_half_batch_exchange") and _EXPLICIT_STEP)
+                      and hasattr(ebc, "set_half_batch_exchange"))
         g_dense = GraphedSegment(m.dense_arch, [torch.randn(B, dense_in, device=dev)])
         if halves and hasattr(ebc, "set_graph_exchange"):
             ebc.set_graph_exchange(None)
@@ -400,7 +372,7 @@ class DLRMTrain(nn.Module):
             # all-to-all's receive buffer is the FIRST kernel of the head's forward graph and the pack of the gradient
             # into the send buffer the LAST of its backward graph, instead of two eager launches per step
             hooks = None
-            if (flat_grads and _EXPLICIT_STEP and _GRAPH_EXCHANGE and getattr(ebc, "_exchange", False)
+            if (flat_grads and _GRAPH_EXCHANGE and getattr(ebc, "_exchange", False)
                     and hasattr(ebc, "set_graph_exchange")):
                 pooled = torch.zeros(B, F, D, device=dev)
                 ebc.set_output_buffer(pooled)
@@ -479,7 +451,7 @@ class DLRMTrain(nn.Module):
             g_dense.after_backward = dense_done
             object.__setattr__(self, "_flat_dense", state)
         late = 0
-        if flat_grads and _DEFER_WGRAD and _EXPLICIT_STEP and getattr(ebc, "_exchange", False):
+        if flat_grads and _DEFER_WGRAD and getattr(ebc, "_exchange", False):
             # (weight, bias) of the over arch's first layers: the leading parameters of the head segment
             n_lin = sum(1 for q in g_head._params if q.dim() == 2)
             late = 2 * min(_late_layers(B, halves), max(n_lin - 1, 0))
@@ -589,10 +561,6 @@ class DLRMTrain(nn.Module):
         """After backward: folds the autograd gradients of the non-graphed dense parameters into the flat
         buffer, all-reduces the rest of it (bottom segment + those), waits, and attaches the slices as
         `.grad` (every rank then holds the rank-averaged gradient, as under DistributedDataParallel)."""
-        from ..modules.mlp import _DeferredFinish, _WgradOverlap
-
-        _WgradOverlap.join()  # weight gradients computed on the side stream (eager steps; modules/mlp.py)
-        _DeferredFinish.flush()  # eager steps: every split-K / bias gradient of this backward finished by one launch
         st = getattr(self, "_flat_dense", None)
         if st is None:
             return
@@ -822,8 +790,7 @@ class DLRMTrain(nn.Module):
         if (g is not None and self.training and torch.is_grad_enabled()
                 and batch.dense_features.shape[0] == g[0] and batch.dense_features.is_cuda):
             _, g_dense, g_head = g
-            if (getattr(self, "_flat_dense", None) is not None and getattr(self, "_between", None) is not None
-                    and _EXPLICIT_STEP):
+            if getattr(self, "_flat_dense", None) is not None and getattr(self, "_between", None) is not None:
                 # only under an owner that asked for it (set_between_forward_and_backward) and will skip loss.backward()
                 out = self._explicit_step(batch, g_dense, g_head)
                 object.__setattr__(self, "_between", None)
@@ -836,14 +803,9 @@ class DLRMTrain(nn.Module):
             if getattr(self, "_graph_exchange", False):
                 raise RuntimeError("DLRMTrain: these graphs unpack / pack the pooled exchange themselves and serve the explicit "
                                    "step only (run the model under TrainPipelineSparseDist, or set TORCHREC_AMD_GRAPH_EXCHANGE=0)")
-            defer, launch = _sort_hooks(self.model.sparse_arch.embedding_bag_collection)
-            if defer is not None:
-                defer(True)
             pending = self.model.sparse_arch.start(batch.sparse_features)
             embedded_dense = g_dense(batch.dense_features)
             embedded_sparse = self.model.sparse_arch.finish(pending)
-            if launch is not None:
-                launch()  # beside the head segment (interaction + over arch), after the lookup and the exchange
             object.__setattr__(self, "_loss_grad_ready", False)  # autograd writes whatever d(loss) the caller backpropagates
             loss, logits = g_head(embedded_dense, embedded_sparse, batch.labels.to(g_head.static_inputs[2].dtype))
             return loss, (loss.detach(), logits.detach(), batch.labels.detach())

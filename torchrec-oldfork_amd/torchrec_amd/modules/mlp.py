@@ -6,55 +6,6 @@ import torch
 from torch import nn
 
 
-class _WgradOverlap:
-    """Weight-gradient GEMMs on a side stream (eager steps only).
-
-    dW = dY^T X of a Linear is needed by nobody until the optimizer runs, while the chain the backward waits for —
-    dX = dY W, the ReLU-backward pass, the interaction backward, the embedding backward — alternates MFMA-bound GEMMs
-    with HBM-bound passes.  With this switch on, `_LinearSplitKWgrad.backward` enqueues dW on a second stream (ordered
-    after dY by an event), accumulates it into `weight.grad` there and hands autograd no weight gradient; the GEMM then
-    shares the chip with whatever the main stream runs next.  The OWNER of the train loop must call `join()` after
-    backward and before the optimizer reads the gradients (TrainPipelineSparseDist does, through
-    DLRMTrain.finish_dense_grads) — hence opt-in.  Not for modules wrapped in DistributedDataParallel (its hooks
-    never see these gradients) and not inside a HIP-graph capture (the graphed segments keep their own order)."""
-
-    stream: Optional[torch.cuda.Stream] = None
-    on: bool = False
-    pending: List[torch.cuda.Event] = []
-
-    @classmethod
-    def enable(cls, device: torch.device) -> None:
-        """Switch on for backward passes started from now on (the caller brackets ONE backward: enable, backward,
-        join / disable)."""
-        if cls.stream is None or cls.stream.device != device:
-            import os
-
-            # numerically larger = lower priority; the runtime clamps to what the device offers
-            from fbgemm_gpu._streams import side_stream
-
-            cls.stream = side_stream(device, priority=int(os.environ.get("TORCHREC_AMD_WGRAD_PRIORITY", "0")))
-        cls.on = True
-
-    @classmethod
-    def disable(cls) -> None:
-        cls.join()
-        cls.on = False
-
-    @classmethod
-    def join(cls) -> None:
-        """The current stream waits for every weight gradient enqueued so far."""
-        if cls.pending:
-            cur = torch.cuda.current_stream()
-            for ev in cls.pending:
-                cur.wait_event(ev)
-            cls.pending = []
-
-    @classmethod
-    def active_for(cls, t: torch.Tensor) -> bool:
-        return (cls.on and cls.stream is not None and t.is_cuda and t.device == cls.stream.device
-                and not torch.cuda.is_current_stream_capturing())
-
-
 class _DeferredWgrad:
     """Weight gradients set aside while a backward is being CAPTURED (distributed/hip_graph.py capture_backward(defer_wgrad=
     True)): the capture of the input-gradient chain ends first, and the weight-gradient GEMMs are captured into a second
@@ -87,74 +38,6 @@ class _DeferredWgrad:
     @classmethod
     def stashing(cls, t: torch.Tensor) -> bool:
         return cls.pending is not None and t.is_cuda and torch.cuda.is_current_stream_capturing()
-
-
-class _DeferredFinish:
-    """EAGER steps: finish every dense gradient of one backward with ONE launch.
-
-    The split-K weight gradient of a layer ends in a reduce kernel over its batch slices, the bias gradient in a second-stage
-    column-sum launch: 16 launches per DLRM step whose combined work is ~50 MB (≈ 140 us per step at batch 65 536).  With this
-    switch on, `backward` returns NO gradient for those parameters and records (parameter, partial sums [chunks, numel]);
-    `flush()` adds every parameter's chunks in fixed order with one `multi_chunk_sum` launch (segment table by value in the
-    kernel arguments) and attaches the results as `.grad` itself (accumulating into an existing `.grad`), the way
-    `_WgradOverlap` does — handing autograd an unfinished tensor does not work: AccumulateGrad clones a gradient somebody
-    else still references.  Only for an owner that calls flush() after backward and before anything reads the gradients —
-    TrainPipelineSparseDist does, through DLRMTrain.finish_dense_grads — and enables it for the duration of one backward;
-    never under DistributedDataParallel (its hooks wait for gradients autograd never delivers) and never inside a HIP-graph
-    capture (captures have their own stash: _DeferredWgrad)."""
-
-    on: bool = False
-    pending: list = []  # (parameter, partials [chunks, numel] fp32 contiguous)
-    MAX_SEGMENTS = 32
-
-    @classmethod
-    def enable(cls) -> None:
-        cls.on = True
-
-    @classmethod
-    def disable(cls) -> None:
-        cls.flush()
-        cls.on = False
-
-    @classmethod
-    def active_for(cls, t: torch.Tensor, param) -> bool:
-        return (cls.on and param is not None and t.is_cuda and t.dtype == torch.float32 and param.dtype == torch.float32
-                and not torch.cuda.is_current_stream_capturing())
-
-    @classmethod
-    def add(cls, param, partials: torch.Tensor) -> None:
-        cls.pending.append((param, partials.contiguous().view(partials.shape[0], -1)))
-        if len(cls.pending) >= cls.MAX_SEGMENTS:
-            cls.flush()
-
-    @classmethod
-    def flush(cls) -> None:
-        if not cls.pending:
-            return
-        import ctypes
-
-        from fbgemm_gpu import _lib
-        from fbgemm_gpu._lib import check, stream_ptr
-
-        items, cls.pending = cls.pending, []
-        dev = items[0][1].device
-        table = (ctypes.c_int64 * (4 * len(items)))()
-        outs = []
-        for i, (prm, part) in enumerate(items):
-            if part.shape[1] != prm.numel() or part.device != dev:
-                raise RuntimeError("_DeferredFinish: partial sums do not match their parameter")
-            dst = torch.empty(prm.shape, dtype=torch.float32, device=dev)
-            outs.append(dst)
-            table[4 * i:4 * i + 4] = [part.data_ptr(), part.shape[0], dst.numel(), dst.data_ptr() // 4]
-        with torch.cuda.device(dev):
-            check(_lib.load().tbe_multi_chunk_sum_host_table_f32(table, len(items), max(d.numel() for d in outs), None, 1.0,
-                                                                 stream_ptr(dev)), "tbe_multi_chunk_sum_host_table_f32")
-        with torch.no_grad():
-            for (prm, _), dst in zip(items, outs):
-                if prm.grad is None:
-                    prm.grad = dst
-                else:
-                    prm.grad.add_(dst)
 
 
 class _LinearSplitKWgrad(torch.autograd.Function):
@@ -196,10 +79,6 @@ class _LinearSplitKWgrad(torch.autograd.Function):
                     gy, part = torch.ops.tbe_hip.relu_backward_bias_partials(gy, out)
                     _DeferredWgrad.pending.append(("p", ctx.bias_param, part))
                     gb_deferred = True
-                elif ctx.needs_input_grad[2] and _DeferredFinish.active_for(gy, ctx.bias_param):
-                    gy, part = torch.ops.tbe_hip.relu_backward_bias_partials(gy, out)
-                    _DeferredFinish.add(ctx.bias_param, part)  # .grad attached by _DeferredFinish.flush()
-                    gb_deferred = True
                 else:
                     gy, gb = torch.ops.tbe_hip.relu_backward_bias_grad(gy, out)
             else:
@@ -216,40 +95,13 @@ class _LinearSplitKWgrad(torch.autograd.Function):
                 torch.mm(gy, weight, out=gx)
             else:
                 gx = gy @ weight
-        B = x.shape[0]
         c = ctx.chunks
-
-        def wgrad():
-            return _DeferredWgrad.compute(gy, x, c)
-
         w = ctx.weight_param
         if w is not None and ctx.needs_input_grad[1] and _DeferredWgrad.stashing(gy):
             _DeferredWgrad.pending.append(("w", w, gy, x, c))  # captured later, into the segment's second backward graph
             gw = None
-        elif w is not None and ctx.needs_input_grad[1] and _WgradOverlap.active_for(gy):
-            side, cur = _WgradOverlap.stream, torch.cuda.current_stream()
-            ready = torch.cuda.Event()
-            ready.record(cur)  # dY (and the step's earlier work on this stream) is complete for the side stream
-            side.wait_event(ready)
-            with torch.cuda.stream(side):
-                gw = wgrad()
-                if w.grad is None:
-                    w.grad = gw
-                else:
-                    w.grad.add_(gw)
-                done = torch.cuda.Event()
-                done.record(side)
-            for t in (gy, x):
-                t.record_stream(side)  # freed by autograd on `cur` while the side stream may still read them
-            gw.record_stream(cur)      # read by the optimizer on the main stream after join()
-            _WgradOverlap.pending.append(done)
-            gw = None
-        elif ctx.needs_input_grad[1] and c > 1 and B % c == 0 and _DeferredFinish.active_for(gy, w):
-            # [c, out, in]: the batched GEMM without its reduction; .grad attached by _DeferredFinish.flush()
-            _DeferredFinish.add(w, _DeferredWgrad.compute_partials(gy, x, c))
-            gw = None
         else:
-            gw = wgrad()
+            gw = _DeferredWgrad.compute(gy, x, c)
         if gb is None and ctx.has_bias and not gb_deferred:
             gb = gy.sum(dim=0)
         return gx, gw, gb, None, None
@@ -277,9 +129,6 @@ class _LinearOneOutput(torch.autograd.Function):
         if _DeferredWgrad.partials_ok and ctx.weight_param is not None and _DeferredWgrad.stashing(gy):
             part = torch.ops.tbe_hip.weighted_colsum_partials(x, gy.view(-1))  # [row blocks, in]
             _DeferredWgrad.pending.append(("p", ctx.weight_param, part.view(part.shape[0], 1, -1)))
-            gw = None
-        elif ctx.needs_input_grad[1] and _DeferredFinish.active_for(gy, ctx.weight_param):
-            _DeferredFinish.add(ctx.weight_param, torch.ops.tbe_hip.weighted_colsum_partials(x, gy.view(-1)))
             gw = None
         else:
             gw = torch.ops.tbe_hip.weighted_colsum(x, gy.view(-1)).view(1, -1)
