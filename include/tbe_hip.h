@@ -397,6 +397,26 @@ int tbe_dlrm_interaction_backward_f32(const float* dense, const float* sparse,
                                       const float* grad_out, int64_t grad_row_stride, int32_t B, int32_t F, int32_t D,
                                       float* grad_dense, float* grad_sparse, void* stream);
 
+/* The two calls above with the pooled lookup folded in, for a pooling factor of exactly 1 (Criteo): the lookup is then
+ * a copy of one table row per (sample, feature) into `sparse`, which the interaction reads straight back; here the
+ * interaction kernels fetch the rows from the tables themselves and the pooled buffer does not exist.
+ *   feat_weights / feat_rows / feat_window: the [F] / [F] / [2F] layout arrays of tbe_forward_pooled_f32 (every table
+ *   of dim D, bases 16-B aligned); indices [F*B] int64, feature-major, ONE id per bag: bag (f, b) owns indices[f*B + b].
+ *   X[0] = dense[b], X[r] = W_{r-1}[indices[(r-1)*B + b]] for r >= 1; an id outside the feature's window, TBE_ID_SKIP or
+ *   out of range gives a zero row.  out / grad_dense / grad_sparse [B, F*D] are bit-identical to
+ *   tbe_forward_pooled_f32 (SUM, no weights) followed by the calls above.
+ * bounds_errors: optional device int32 counter, incremented once per id outside [0, global rows).  The backward gathers
+ *   the same ids again: pass NULL there so that an id is counted once per step, as on the two-kernel path.
+ * 1 <= F <= 27, D in {64, 128}. */
+int tbe_dlrm_interaction_gather_forward_f32(const float* dense, const uint64_t* feat_weights, const int64_t* feat_rows,
+                                            const int64_t* feat_window, const int64_t* indices, int32_t B, int32_t F,
+                                            int32_t D, float* out, int64_t out_row_stride, int32_t* bounds_errors,
+                                            void* stream);
+int tbe_dlrm_interaction_gather_backward_f32(const float* dense, const uint64_t* feat_weights, const int64_t* feat_rows,
+                                             const int64_t* feat_window, const int64_t* indices, const float* grad_out,
+                                             int64_t grad_row_stride, int32_t B, int32_t F, int32_t D, float* grad_dense,
+                                             float* grad_sparse, int32_t* bounds_errors, void* stream);
+
 /* ReLU backward + bias gradient of one MLP layer in one pass (torchrec/modules/mlp.py:14-170 Perceptron
  * trained through autograd: threshold_backward + sum(0)):
  *   grad_in[b, c] = act[b, c] > 0 ? grad_out[b, c] : 0;   bias_grad[c] = sum_b grad_in[b, c]

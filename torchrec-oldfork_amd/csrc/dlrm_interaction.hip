@@ -495,6 +495,377 @@ __global__ __launch_bounds__(256, 2) void interaction_bwd_kernel(const float* __
   }
 }
 
+// ---- pooling factor 1: the interaction kernels fetch the table rows themselves -------------------------------------
+// With exactly one id per bag the pooled buffer is a copy of table rows that the lookup writes and these kernels read
+// back.  The two kernels below are interaction_fwd_glds_kernel / interaction_bwd_kernel with ONE change: row r >= 1 of
+// sample b comes from feat_weights[r-1] + local_id * D instead of sparse + (b*F + r-1)*D.  Contraction orders, LDS
+// images and store paths are untouched, so the results are bit-identical to the lookup + interaction pair.
+//
+// Who knows which row: lane f < F is the "feature lane" of feature f.  It keeps the feature's window and table base in
+// registers, classifies the one id of (f, sample) with classify_id — exactly as tbe_fwd_short_kernel does — and holds the
+// resulting row ADDRESS; the lanes that fetch pieces of row r read it from lane r-1 (two ds_bpermute, no LDS memory).
+
+// What a non-local or bad id reads instead of a table row (an LDS-DMA lane that is masked off would leave stale LDS).
+__device__ __attribute__((aligned(16))) float g_zero_row[256];
+
+struct GatherLane {
+  RowWindow win;
+  uint64_t base;  // table base address of this lane's feature
+  bool counts;    // lane < F: bad ids are counted once, by their feature lane
+};
+__device__ __forceinline__ GatherLane load_gather_lane(const uint64_t* feat_weights, const int64_t* feat_rows,
+                                                       const int64_t* feat_window, int lane, int F) {
+  GatherLane g;
+  const int f = min(lane, F - 1);
+  g.win = load_window(feat_rows, feat_window, f);
+  g.base = feat_weights[f];
+  g.counts = lane < F;
+  return g;
+}
+// Address of the row `id` selects (`miss` for a non-local or bad id); counts bad ids into nbad.
+template <int D>
+__device__ __forceinline__ uint64_t gather_row_address(const GatherLane& g, int64_t id, uint64_t miss, int& nbad) {
+  int64_t local;
+  const int cls = classify_id(g.win, id, local);
+  if (cls == kIdBad && g.counts) ++nbad;
+  return cls == kIdLocal ? g.base + static_cast<uint64_t>(local) * (D * sizeof(float)) : miss;
+}
+__device__ __forceinline__ void report_bad_ids(int nbad, int32_t* bounds_errors) {
+  if (bounds_errors == nullptr) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nbad += __shfl_xor(nbad, o, kWave);
+  if ((threadIdx.x & 63) == 0 && nbad > 0) atomicAdd(bounds_errors, nbad);
+}
+
+// Forward.  Everything a sample needs from global memory arrives by LDS-DMA, so the kernel still has no load the compiler
+// would wait for (see vm_wait_all_but above: the only waits are the counted ones):
+//   * the F ids of a sample — one per feature, B entries apart — by ONE global_load_lds_dword (lane l copies half l & 1 of
+//     the id of feature l / 2) into a 256-B slot of the wave, issued right behind the row copy of the sample before it and
+//     therefore covered by the same counted wait;
+//   * the rows by the parent's copy instructions, whose per-lane source is now dense (row 0), a table row or g_zero_row.
+// The copy issue is a rolled loop (one address in flight): the 64 fragment registers are live across it.
+template <int D>
+__global__ __launch_bounds__(256, 2) void interaction_gather_fwd_kernel(const float* __restrict__ dense,
+                                                                       const uint64_t* __restrict__ feat_weights,
+                                                                       const int64_t* __restrict__ feat_rows,
+                                                                       const int64_t* __restrict__ feat_window,
+                                                                       const int64_t* __restrict__ indices,
+                                                                       float* __restrict__ out,
+                                                                       int32_t* __restrict__ bounds_errors, int B, int F,
+                                                                       int64_t out_stride) {
+  extern __shared__ float smem[];
+  constexpr int NS = D / 16;
+  constexpr int PR = D / 4;          // 16-B pieces per row
+  constexpr int RPI = kWave / PR;    // rows per copy instruction
+  constexpr int IDS = 64;            // floats of the id slot: 32 ids of 8 B
+  static_assert(PR >= 16 && PR <= kWave, "LDS-DMA form needs 64 <= D <= 256");
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int R = F + 1;
+  const int P = R * (R - 1) / 2;
+  const int P4 = (P + 3) & ~3;
+  const int NI = (R + RPI - 1) / RPI;
+  float* xs = smem + wave * (NI * RPI * D + P4 + IDS);
+  float* zs = xs + NI * RPI * D;
+  float* ids = zs + P4;  // 8-B aligned: every term above is a multiple of 4 floats
+  const bool vec_out = (out_stride & 3) == 0 && out_stride >= D + P4 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  if (lane < P4 - P) zs[P + lane] = 0.f;
+  const int r16 = lane & 15;
+  const int kq = lane >> 4;
+  const int row0 = min(r16, R - 1);       // rows >= R alias row R-1 (their products are never stored)
+  const int row1 = min(16 + r16, R - 1);
+  const int stride_b = gridDim.x * 4;
+  const GatherLane gl = load_gather_lane(feat_weights, feat_rows, feat_window, lane, F);
+  const uint64_t zero_row = reinterpret_cast<uint64_t>(&g_zero_row[0]);
+  int nbad = 0;
+  // id of (feature min(lane / 2, F-1), sample b), half lane & 1 -> the wave's id slot
+  const uint32_t* id_words = reinterpret_cast<const uint32_t*>(indices) +
+                             2 * static_cast<int64_t>(min(lane >> 1, F - 1)) * B + (lane & 1);
+  auto issue_ids = [&](int b) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(id_words + 2 * static_cast<int64_t>(b)),
+                                     (__attribute__((address_space(3))) void*)ids, 4, 0, 0);
+  };
+  // copy instruction i: row min(i * RPI + lane / PR, R - 1), piece (lane % PR) ^ (row & 15); `row_addr` is the feature
+  // lanes' row address for sample b
+  auto issue_copy = [&](int b, uint64_t row_addr) {
+    const uint64_t dn = reinterpret_cast<uint64_t>(dense + static_cast<int64_t>(b) * D);
+#pragma unroll 1
+    for (int i = 0; i < NI; ++i) {
+      const int row = min(i * RPI + lane / PR, R - 1);
+      const int piece = (lane % PR) ^ (row & 15);
+      uint64_t src = shflu64(row_addr, max(row - 1, 0));
+      if (row == 0) src = dn;
+      src += 16 * piece;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                       (__attribute__((address_space(3))) void*)(xs + i * (kWave * 4)), 16, 0, 0);
+    }
+  };
+  auto read_id = [&]() { return *reinterpret_cast<const int64_t*>(ids + 2 * min(lane, F - 1)); };
+  const bool dense_lane = lane < PR;
+  const int T = (P + kWave - 1) / kWave;  // pair stores per sample
+  constexpr int DS = (D + kWave - 1) / kWave;  // dense pass-through stores per sample
+  int stores_behind_copy = 0;
+  int b = blockIdx.x * 4 + wave;
+  if (b < B) {
+    issue_ids(b);
+    vm_wait_all_but<0>();
+    __builtin_amdgcn_wave_barrier();
+    const int64_t id = read_id();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    issue_copy(b, gather_row_address<D>(gl, id, zero_row, nbad));
+    if (b + stride_b < B) issue_ids(b + stride_b);
+  }
+  for (; b < B; b += stride_b) {
+    // the copy of sample b and the ids of the next sample have landed once everything but the stores issued after them
+    // has retired
+    vm_wait_all_but(stores_behind_copy);
+    __builtin_amdgcn_wave_barrier();
+    float4 xa[NS], xb[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) xa[s] = *reinterpret_cast<const float4*>(xs + row0 * D + 4 * ((4 * s + kq) ^ (row0 & 15)));
+    if (R > 16) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) xb[s] = *reinterpret_cast<const float4*>(xs + row1 * D + 4 * ((4 * s + kq) ^ (row1 & 15)));
+    } else {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) xb[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float4 dpass = make_float4(0.f, 0.f, 0.f, 0.f);
+    float dscal[DS];  // row 0 is stored unswizzled
+    if (vec_out) {
+      if (dense_lane) dpass = *reinterpret_cast<const float4*>(xs + 4 * lane);
+    } else {
+#pragma unroll
+      for (int t = 0; t < DS; ++t) dscal[t] = xs[min(lane + t * kWave, D - 1)];
+    }
+    const int64_t next_id = read_id();  // of sample b + stride_b (stale when there is none: not used then)
+    // every read of the image and of the id slot has returned before the next copies may overwrite them
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    if (b + stride_b < B) {
+      issue_copy(b + stride_b, gather_row_address<D>(gl, next_id, zero_row, nbad));
+      if (b + 2 * stride_b < B) issue_ids(b + 2 * stride_b);
+    }
+    f32x4 acc00 = {0.f, 0.f, 0.f, 0.f}, acc01 = acc00, acc11 = acc00;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const float a0[4] = {xa[s].x, xa[s].y, xa[s].z, xa[s].w};
+      const float a1[4] = {xb[s].x, xb[s].y, xb[s].z, xb[s].w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc00 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], a0[e], acc00, 0, 0, 0);
+        acc01 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], a1[e], acc01, 0, 0, 0);
+        acc11 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], a1[e], acc11, 0, 0, 0);
+      }
+    }
+    float* orow = out + static_cast<int64_t>(b) * out_stride;
+    if (vec_out) {
+      if (dense_lane) st4(orow + lane * 4, dpass);
+    } else {
+#pragma unroll
+      for (int t = 0; t < DS; ++t) vm_store_dword(orow + min(lane + t * kWave, D - 1), dscal[t]);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = kq * 4 + q;
+      const int j = r16;
+      if (i < j && j < R) zs[triu_index(i, j, R)] = acc00[q];
+      if (16 + j < R && i < R) zs[triu_index(i, 16 + j, R)] = acc01[q];
+      if (i < j && 16 + j < R) zs[triu_index(16 + i, 16 + j, R)] = acc11[q];
+    }
+    __builtin_amdgcn_wave_barrier();
+    constexpr int MAXT = 8;
+    constexpr int MAXQ = 2;
+    if (vec_out) {
+#pragma unroll
+      for (int t = 0; t < MAXQ; ++t) {
+        const int q = lane + t * kWave;
+        if (q < P4 / 4) st4(orow + D + 4 * q, *reinterpret_cast<const float4*>(zs + 4 * q));
+      }
+      stores_behind_copy = 0;  // compiler-generated stores: their number is not ours to count, wait for everything
+    } else {
+      float zv[MAXT];
+#pragma unroll
+      for (int t = 0; t < MAXT; ++t)
+        if (t < T) zv[t] = zs[min(lane + t * kWave, P - 1)];
+#pragma unroll
+      for (int t = 0; t < MAXT; ++t)
+        if (t < T) vm_store_dword(orow + D + min(lane + t * kWave, P - 1), zv[t]);
+      stores_behind_copy = DS + T;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  report_bad_ids(nbad, bounds_errors);
+}
+
+// Backward.  The rows are staged through registers as in interaction_bwd_kernel; the feature lanes load the ids one
+// sample further ahead than the rows (one 8-B load per lane and sample), so a row load never waits for its id.
+template <int NT>  // NT = D / 16 column tiles
+__global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const float* __restrict__ dense,
+                                                                       const uint64_t* __restrict__ feat_weights,
+                                                                       const int64_t* __restrict__ feat_rows,
+                                                                       const int64_t* __restrict__ feat_window,
+                                                                       const int64_t* __restrict__ indices,
+                                                                       const float* __restrict__ grad_out,
+                                                                       float* __restrict__ grad_dense,
+                                                                       float* __restrict__ grad_sparse,
+                                                                       int32_t* __restrict__ bounds_errors, int B, int F,
+                                                                       int64_t grad_stride) {
+  extern __shared__ float smem[];
+  constexpr int D = NT * 16;
+  constexpr int XS = D + 16;
+  constexpr int GS = 34;
+  constexpr int XROWS = 28;
+  constexpr int LOG_V = XLoader<D>::LOG_V;
+  constexpr int MAXV = (XROWS * D / 4 + kWave - 1) / kWave;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int R = F + 1;
+  const int P = R * (R - 1) / 2;
+  float* xs = smem + wave * (XROWS * XS + 32 * GS);
+  float* gs = xs + XROWS * XS;
+  const int r16 = lane & 15;
+  const int kq = lane >> 4;
+  const int nvec = R * (D / 4);
+  const int ksteps = (R + 3) / 4;
+  const int stride_b = gridDim.x * 4;
+  for (int e = lane; e < XROWS * XS; e += kWave) xs[e] = 0.f;
+  for (int e = lane; e < 32 * GS; e += kWave) gs[e] = 0.f;
+  constexpr int MAXP = (28 * 27 / 2 + kWave - 1) / kWave;  // 6
+  int pij[MAXP];
+#pragma unroll
+  for (int t = 0; t < MAXP; ++t) {
+    const int p = lane + t * kWave;
+    int i = 0, j = 1;
+    if (p < P) {
+      i = triu_row(p, R);
+      j = i + 1 + (p - i * (2 * R - i - 1) / 2);
+    }
+    pij[t] = (i << 8) | j;
+  }
+  wave_lds_fence();
+
+  const GatherLane gl = load_gather_lane(feat_weights, feat_rows, feat_window, lane, F);
+  const int64_t* my_ids = indices + static_cast<int64_t>(min(lane, F - 1)) * B;
+  int nbad = 0;
+  float4 pre[MAXV];
+  float gpre[MAXP];
+  // X of sample s: row 0 from dense, row r >= 1 from the address lane r-1 holds (0 = a zero row)
+  auto load_x = [&](int s, uint64_t row_addr) {
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+      const int v = lane + i * kWave;
+      const int r = min(v >> LOG_V, R - 1);
+      const int c = (v & ((1 << LOG_V) - 1)) * 4;
+      const uint64_t src = shflu64(row_addr, max(r - 1, 0));
+      if (v < nvec) {
+        if (r == 0)
+          pre[i] = ld4(dense + static_cast<int64_t>(s) * D + c);
+        else
+          pre[i] = src != 0 ? ld4(reinterpret_cast<const float*>(src) + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+  };
+  int b = blockIdx.x * 4 + wave;
+  int64_t next_id = 0;  // this lane's id of the sample AFTER the one whose rows are in flight
+  if (b < B) {
+    load_x(b, gather_row_address<D>(gl, my_ids[b], 0, nbad));
+    if (b + stride_b < B) next_id = my_ids[b + stride_b];
+#pragma unroll
+    for (int t = 0; t < MAXP; ++t) {
+      const int p = lane + t * kWave;
+      gpre[t] = p < P ? grad_out[static_cast<int64_t>(b) * grad_stride + D + p] : 0.f;
+    }
+  }
+  for (; b < B; b += stride_b) {
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+      const int v = lane + i * kWave;
+      if (v < nvec) st4(xs + (v >> LOG_V) * XS + (v & ((1 << LOG_V) - 1)) * 4, pre[i]);
+    }
+#pragma unroll
+    for (int t = 0; t < MAXP; ++t) {
+      if (lane + t * kWave < P) {
+        const int i = pij[t] >> 8, j = pij[t] & 255;
+        gs[i * GS + j] = gpre[t];
+        gs[j * GS + i] = gpre[t];
+      }
+    }
+    const float* grow = grad_out + static_cast<int64_t>(b) * grad_stride;
+    float4 gdense = make_float4(0.f, 0.f, 0.f, 0.f);  // d(out)[:, :D] slice this lane adds to row 0
+    if (lane < D / 4) {
+      if (((grad_stride & 3) | (reinterpret_cast<uintptr_t>(grad_out) & 15)) == 0) {
+        gdense = ld4(grow + lane * 4);
+      } else {
+        gdense.x = grow[lane * 4 + 0];
+        gdense.y = grow[lane * 4 + 1];
+        gdense.z = grow[lane * 4 + 2];
+        gdense.w = grow[lane * 4 + 3];
+      }
+    }
+    const int nb = b + stride_b;
+    if (nb < B) {
+      load_x(nb, gather_row_address<D>(gl, next_id, 0, nbad));
+      if (nb + stride_b < B) next_id = my_ids[nb + stride_b];
+#pragma unroll
+      for (int t = 0; t < MAXP; ++t) {
+        const int p = lane + t * kWave;
+        gpre[t] = p < P ? grad_out[static_cast<int64_t>(nb) * grad_stride + D + p] : 0.f;
+      }
+    }
+    wave_lds_fence();
+    f32x4 acc[2][NT];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < ksteps; ++ks) {
+      const int k = ks * 4 + kq;
+      const float a0 = gs[r16 * GS + k];
+      const float a1 = gs[(16 + r16) * GS + k];
+      const float* xrow = xs + k * XS + r16;
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        const float bn = xrow[16 * n];
+        acc[0][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bn, acc[0][n], 0, 0, 0);
+        acc[1][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bn, acc[1][n], 0, 0, 0);
+      }
+    }
+    wave_lds_fence();  // every lane is done reading X before it is overwritten with dX
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int row = 16 * m + 4 * kq + q;
+          if (row < R) xs[row * XS + 16 * n + r16] = acc[m][n][q];
+        }
+    wave_lds_fence();
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+      const int v = lane + i * kWave;
+      if (v < nvec) {
+        const int r = v >> LOG_V;
+        const int c = (v & ((1 << LOG_V) - 1)) * 4;
+        float4 x = ld4(xs + r * XS + c);
+        if (r == 0) {  // v == lane < D/4 here
+          x.x += gdense.x;
+          x.y += gdense.y;
+          x.z += gdense.z;
+          x.w += gdense.w;
+          st4(grad_dense + static_cast<int64_t>(b) * D + c, x);
+        } else {
+          st4(grad_sparse + (static_cast<int64_t>(b) * F + (r - 1)) * D + c, x);
+        }
+      }
+    }
+    wave_lds_fence();
+  }
+  report_bad_ids(nbad, bounds_errors);
+}
+
 }  // namespace tbe
 
 using namespace tbe;
@@ -595,5 +966,84 @@ extern "C" int tbe_dlrm_interaction_backward_f32(const float* dense, const float
   }
 #undef TBE_IB
   TBE_CHECK_LAUNCH("tbe_dlrm_interaction_backward_f32");
+  return TBE_OK;
+}
+
+// ---- pooling factor 1: lookup fused into the interaction (kernels above) ------------------------------------------
+static int check_gather_args(const char* what, int32_t B, int32_t F, int32_t D, int64_t row_stride) {
+  TBE_REQUIRE(B >= 0 && F >= 1 && F <= 27, "%s: F=%d outside [1, 27]", what, F);
+  TBE_REQUIRE(D == 64 || D == 128, "%s: D=%d not in {64,128}", what, D);
+  TBE_REQUIRE(row_stride >= D + (F + 1) * F / 2, "%s: row stride %lld < D + F(F+1)/2", what, (long long)row_stride);
+  return TBE_OK;
+}
+
+extern "C" int tbe_dlrm_interaction_gather_forward_f32(const float* dense, const uint64_t* feat_weights,
+                                                       const int64_t* feat_rows, const int64_t* feat_window,
+                                                       const int64_t* indices, int32_t B, int32_t F, int32_t D, float* out,
+                                                       int64_t out_row_stride, int32_t* bounds_errors, void* stream) {
+  const char* what = "tbe_dlrm_interaction_gather_forward_f32";
+  if (int rc = check_gather_args(what, B, F, D, out_row_stride)) return rc;
+  TBE_REQUIRE(dense && feat_weights && feat_rows && indices && out, "%s: null pointer", what);
+  TBE_REQUIRE((reinterpret_cast<uintptr_t>(dense) & 15) == 0 && (reinterpret_cast<uintptr_t>(indices) & 7) == 0,
+              "%s: dense must be 16-B aligned, indices 8-B aligned", what);
+  if (B == 0) return TBE_OK;
+  const int R = F + 1, P = R * (R - 1) / 2;
+  const int rpi = 64 / (D / 4);
+  const int rows = (R + rpi - 1) / rpi * rpi;
+  const size_t lds = 4 * (static_cast<size_t>(rows) * D + ((P + 3) & ~3) + 64) * sizeof(float);
+  static bool attr_set = false;
+  if (!attr_set) {
+    const size_t big = 4 * (static_cast<size_t>(28) * 128 + 380 + 64) * sizeof(float);
+    if (!reserve_lds(interaction_gather_fwd_kernel<128>, big) || !reserve_lds(interaction_gather_fwd_kernel<64>, big)) {
+      set_error("%s: cannot reserve LDS", what);
+      return TBE_ERR_LAUNCH;
+    }
+    attr_set = true;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(interaction_grid(B));
+  if (D == 128)
+    hipLaunchKernelGGL(interaction_gather_fwd_kernel<128>, grid, dim3(256), lds, st, dense, feat_weights, feat_rows,
+                       feat_window, indices, out, bounds_errors, B, F, out_row_stride);
+  else
+    hipLaunchKernelGGL(interaction_gather_fwd_kernel<64>, grid, dim3(256), lds, st, dense, feat_weights, feat_rows,
+                       feat_window, indices, out, bounds_errors, B, F, out_row_stride);
+  TBE_CHECK_LAUNCH(what);
+  return TBE_OK;
+}
+
+extern "C" int tbe_dlrm_interaction_gather_backward_f32(const float* dense, const uint64_t* feat_weights,
+                                                        const int64_t* feat_rows, const int64_t* feat_window,
+                                                        const int64_t* indices, const float* grad_out,
+                                                        int64_t grad_row_stride, int32_t B, int32_t F, int32_t D,
+                                                        float* grad_dense, float* grad_sparse, int32_t* bounds_errors,
+                                                        void* stream) {
+  const char* what = "tbe_dlrm_interaction_gather_backward_f32";
+  if (int rc = check_gather_args(what, B, F, D, grad_row_stride)) return rc;
+  TBE_REQUIRE(dense && feat_weights && feat_rows && indices && grad_out && grad_dense && grad_sparse, "%s: null pointer",
+              what);
+  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(dense) | reinterpret_cast<uintptr_t>(grad_dense) |
+                reinterpret_cast<uintptr_t>(grad_sparse)) & 15) == 0 && (reinterpret_cast<uintptr_t>(indices) & 7) == 0,
+              "%s: tensors must be 16-B aligned, indices 8-B aligned", what);
+  if (B == 0) return TBE_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t lds = 4 * (static_cast<size_t>(28) * (D + 16) + 32 * 34) * sizeof(float);
+  static bool attr_set = false;
+  if (!attr_set) {
+    const size_t big = 4 * (28 * (128 + 16) + 32 * 34) * sizeof(float);
+    if (!reserve_lds(interaction_gather_bwd_kernel<8>, big) || !reserve_lds(interaction_gather_bwd_kernel<4>, big)) {
+      set_error("%s: cannot reserve LDS", what);
+      return TBE_ERR_LAUNCH;
+    }
+    attr_set = true;
+  }
+  const dim3 grid(interaction_grid(B));
+  if (D == 128)
+    hipLaunchKernelGGL(interaction_gather_bwd_kernel<8>, grid, dim3(256), lds, st, dense, feat_weights, feat_rows,
+                       feat_window, indices, grad_out, grad_dense, grad_sparse, bounds_errors, B, F, grad_row_stride);
+  else
+    hipLaunchKernelGGL(interaction_gather_bwd_kernel<4>, grid, dim3(256), lds, st, dense, feat_weights, feat_rows,
+                       feat_window, indices, grad_out, grad_dense, grad_sparse, bounds_errors, B, F, grad_row_stride);
+  TBE_CHECK_LAUNCH(what);
   return TBE_OK;
 }

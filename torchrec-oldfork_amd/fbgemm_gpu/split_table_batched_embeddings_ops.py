@@ -1054,6 +1054,34 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         self._enforce_bounds_check_mode()
         return out, rec
 
+    def gather_layout(self):
+        """(feat_weights, feat_rows, feat_window) device arrays for a consumer that fetches the rows itself
+        (tbe_dlrm_interaction_gather_*), or None when this module's lookup is more than one row copy per id: anything but
+        SUM pooling of fp32 DEVICE tables of one dim (a multiple of 4, so every table base is 16-B aligned), a row cache,
+        or BoundsCheckMode.FATAL (which must see a lookup's bad ids before the lookup returns)."""
+        if (self._cache is not None or self.pooling_mode != PoolingMode.SUM or self._feature_pooling is not None
+                or any(p != "dev" for p in self.placement) or len(set(self.dims_per_table)) != 1 or self.max_D % 4 != 0
+                or self.bounds_check_mode == BoundsCheckMode.FATAL or self.current_device.type != "cuda"
+                or self.weights_dev.dtype != torch.float32 or self.weights_dev.data_ptr() % 16 != 0):
+            return None
+        lay = self._get_layout()
+        return lay.feat_weights, lay.feat_rows, lay.feat_window
+
+    def lookup_deferred(self, indices: torch.Tensor, offsets: torch.Tensor) -> "LookupRecord":
+        """A training lookup whose rows the CONSUMER fetches (see gather_layout): the input checks and the side-stream
+        sort of the backward as in forward(), no forward kernel, no output.  The caller owes one
+        backward_no_autograd(record, grad) with the gradient of the pooled output it never materialised."""
+        if self._cache is not None:
+            raise RuntimeError("lookup_deferred: not available with MANAGED_CACHING tables (the cache rewrites the ids)")
+        indices, offsets, _, B = self._check_inputs(indices, offsets, None)
+        rec = LookupRecord(indices, offsets, None, B, None)
+        mode = self.overlap_backward_sort
+        if torch.is_grad_enabled() and (
+                mode in (True, "1") or (mode == "auto" and indices.numel() <= self.overlap_backward_sort_max_ids)):
+            rec.prepared = self._prepare_or_defer(rec, indices, offsets, B, False)
+        self._enforce_bounds_check_mode()
+        return rec
+
     def backward_no_autograd(self, rec: "LookupRecord", grad_out: torch.Tensor) -> None:
         """Coalesced gradient + fused optimizer update for the lookup `rec` describes (what _FusedLookup.backward does)."""
         self.iter += 1

@@ -1115,8 +1115,48 @@ class ShardedEmbeddingBagCollection(nn.Module):
             raise RuntimeError("compute_explicit: not available for this configuration (explicit_step_supported())")
         return ExplicitLookupStep(self, dist_input, halves=self.half_batch_exchange, early_replicated_lookup=not prefetched)
 
+    def deferred_lookup_supported(self, features: KeyedJaggedTensor) -> bool:
+        """Whether compute_deferred() can serve this batch: the pooled output would be a plain copy of one table row per
+        (sample, feature), in the collection's feature order, on this rank — so a consumer can fetch the rows itself.
+        One rank without exchange, replicated tables or row cache; SUM-pooled fp32 DEVICE tables of one dim; no per-sample
+        weights; exactly one id per bag.  Everything is known on the host without a sync."""
+        m = self._emb_module
+        if (self._exchange or self._world_size != 1 or self._dp_module is not None or m is None
+                or not hasattr(m, "lookup_deferred") or self._is_weighted
+                or self._local_feats[self._rank] != list(range(len(self._feature_names)))):
+            return False
+        fixed = features.fixed_lengths()
+        F = len(self._feature_names)
+        if (fixed is None or len(fixed) != F or any(n != 1 for n in fixed)
+                or features.values().numel() != F * features.stride() or features.weights_or_none() is not None):
+            return False
+        return m.gather_layout() is not None
+
+    def compute_deferred(self, dist_input: SparseFeaturesDist) -> "DeferredLookup":
+        """compute_and_output_dist for a consumer that gathers the table rows itself (models/dlrm.py: the dot interaction):
+        input checks and the backward's side-stream sort now, no lookup kernel, no pooled buffer.  Check
+        deferred_lookup_supported() first."""
+        m = self._emb_module
+        with label("## tbe_lookup ##"):
+            rec = m.lookup_deferred(dist_input.values, dist_input.offsets)
+        return DeferredLookup(m, rec, len(self._feature_names), self._lengths_per_embedding[0])
+
     def forward(self, features: KeyedJaggedTensor) -> Awaitable[KeyedTensor]:
         return self.compute_and_output_dist(self.input_dist(features).wait())
+
+
+class DeferredLookup:
+    """A pooling-factor-1 lookup that has not been (and will not be) materialised: the ids, the tables' layout arrays for
+    tbe_dlrm_interaction_gather_* and the record its fused backward needs (ShardedEmbeddingBagCollection.compute_deferred)."""
+
+    def __init__(self, module: nn.Module, rec: Any, F: int, D: int) -> None:
+        self.module, self.rec, self.F, self.D, self.B = module, rec, F, D, rec.B
+        self.feat_weights, self.feat_rows, self.feat_window = module.gather_layout()
+
+    def backward(self, grad_sparse: torch.Tensor) -> None:
+        """grad_sparse [B, F * D]: coalesced gradient + fused optimizer update of the tables."""
+        with label("## tbe_backward_fused_optimizer ##"):
+            self.module.backward_no_autograd(self.rec, grad_sparse)
 
 
 class ExplicitLookupStep:

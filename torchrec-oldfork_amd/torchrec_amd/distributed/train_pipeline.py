@@ -50,6 +50,14 @@ class _PipelinedEBC:
         return self.sharded.compute_explicit(self._dist_input(features), prefetched=prefetched)
 
 
+    def compute_deferred(self, features):
+        """The lookup whose rows the consumer gathers itself (embeddingbag.py DeferredLookup) on this batch's queued input
+        dist, or None when the collection cannot serve it that way (nothing is consumed then)."""
+        if not hasattr(self.sharded, "compute_deferred") or not self.sharded.deferred_lookup_supported(features):
+            return None
+        return self.sharded.compute_deferred(self._dist_input(features))
+
+
 class TrainPipelineSparseDist:
     def __init__(self, model: torch.nn.Module, optimizer: Any, device: torch.device, hip_graphs: bool = False,
                  prefetch_lookup: Optional[bool] = None) -> None:

@@ -160,6 +160,60 @@ class _FusedDotInteraction(torch.autograd.Function):
         return gd, gs, None, None
 
 
+class _FusedGatherInteraction(torch.autograd.Function):
+    """_FusedDotInteraction with the pooling-factor-1 lookup folded in (csrc/dlrm_interaction.hip gather kernels): the
+    interaction reads the table rows itself, the pooled [B, F, D] buffer is neither written nor read.  `lookup` is the
+    collection's DeferredLookup; backward hands the rows' gradient to its fused backward and returns d(dense).
+    `placeholder` (the embedding module's zero-size leaf) keeps this node in the graph when `dense` needs no gradient."""
+
+    @staticmethod
+    def forward(ctx, dense, placeholder, lookup, pad_rows=False):
+        from fbgemm_gpu import _lib
+        from fbgemm_gpu._lib import check, ptr, stream_ptr
+
+        dense = dense.contiguous()
+        B, F, D = lookup.B, lookup.F, lookup.D
+        if dense.shape != (B, D) or dense.dtype != torch.float32 or dense.device != lookup.module.current_device:
+            raise RuntimeError(f"dot interaction: dense {tuple(dense.shape)} {dense.dtype} on {dense.device} does not match "
+                               f"the lookup (batch {B}, dim {D}, float32 on {lookup.module.current_device})")
+        width = D + (F + 1) * F // 2
+        stride = (D + ((F + 1) * F // 2 + 3) // 4 * 4) if pad_rows else width
+        buf = torch.empty((B, stride), dtype=torch.float32, device=dense.device)
+        with torch.cuda.device(dense.device):
+            check(_lib.load().tbe_dlrm_interaction_gather_forward_f32(
+                ptr(dense), ptr(lookup.feat_weights), ptr(lookup.feat_rows), ptr(lookup.feat_window),
+                ptr(lookup.rec.indices), B, F, D, ptr(buf), stride, lookup.module._errors_ptr(), stream_ptr(dense.device)),
+                "tbe_dlrm_interaction_gather_forward_f32")
+        ctx.save_for_backward(dense)
+        ctx.lookup = lookup
+        return buf if stride == width else buf[:, :width]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from fbgemm_gpu import _lib
+        from fbgemm_gpu._lib import check, ptr, stream_ptr
+
+        (dense,) = ctx.saved_tensors
+        lookup, ctx.lookup = ctx.lookup, None
+        B, F, D = lookup.B, lookup.F, lookup.D
+        width = D + (F + 1) * F // 2
+        if grad_out.shape != (B, width):
+            raise RuntimeError(f"dot interaction backward: grad_out {tuple(grad_out.shape)} has the wrong shape")
+        if grad_out.dtype != torch.float32 or grad_out.stride(1) != 1 or grad_out.stride(0) < width:
+            grad_out = grad_out.float().contiguous()  # padded rows (stride >= width) are read in place
+        gd = torch.empty_like(dense)
+        gs = torch.empty((B, F * D), dtype=torch.float32, device=dense.device)
+        with torch.cuda.device(dense.device):
+            # the ids were counted by the forward: no counter here (include/tbe_hip.h)
+            check(_lib.load().tbe_dlrm_interaction_gather_backward_f32(
+                ptr(dense), ptr(lookup.feat_weights), ptr(lookup.feat_rows), ptr(lookup.feat_window),
+                ptr(lookup.rec.indices), ptr(grad_out), grad_out.stride(0), B, F, D, ptr(gd), ptr(gs), None,
+                stream_ptr(dense.device)),
+                "tbe_dlrm_interaction_gather_backward_f32")
+        lookup.backward(gs)
+        return gd, None, None, None
+
+
 def _fused_interaction_ok(dense: torch.Tensor, sparse: torch.Tensor) -> bool:
     F, D = sparse.shape[1], sparse.shape[2]
     return (dense.is_cuda and dense.dtype == torch.float32 and sparse.dtype == torch.float32
@@ -226,8 +280,36 @@ class DLRM(nn.Module):
         self.over_arch = OverArch(over_in, over_arch_layer_sizes, device=dense_device)
         if dense_device is not None:
             self.inter_arch.to(dense_device)
+        # At a pooling factor of 1 the lookup is a copy of table rows into a buffer the interaction reads straight back:
+        # the interaction then gathers the rows itself (_FusedGatherInteraction) whenever the collection can hand out a
+        # DeferredLookup (one rank, no exchange: embeddingbag.py deferred_lookup_supported).  False = always materialise.
+        self.fused_lookup = True
+        self.fused_lookup_steps = 0  # forwards that took the gather path (tests)
+
+    def _deferred_lookup(self, dense_features: torch.Tensor, sparse_features: KeyedJaggedTensor):
+        """The collection's DeferredLookup for this batch, or None (nothing consumed) when the gather path cannot serve it."""
+        sa = self.sparse_arch
+        ebc = sa.embedding_bag_collection
+        if not (self.fused_lookup and self.inter_arch.fused and 1 <= sa.F <= 27 and sa.D in (64, 128)
+                and dense_features.is_cuda and dense_features.dtype == torch.float32
+                and hasattr(ebc, "deferred_lookup_supported")
+                and list(getattr(ebc, "_feature_names", ())) == list(sa.sparse_feature_names)):
+            return None
+        piped = getattr(ebc, "_pipelined", None)  # a train pipeline's forward on this collection (queued input dist)
+        if piped is not None:
+            return piped.compute_deferred(sparse_features)
+        if not ebc.deferred_lookup_supported(sparse_features):
+            return None
+        return ebc.compute_deferred(ebc.input_dist(sparse_features).wait())
 
     def forward(self, dense_features: torch.Tensor, sparse_features: KeyedJaggedTensor) -> torch.Tensor:
+        lookup = self._deferred_lookup(dense_features, sparse_features)
+        if lookup is not None:
+            embedded_dense = self.dense_arch(dense_features)
+            concatenated = _FusedGatherInteraction.apply(embedded_dense, lookup.module.placeholder_autograd_tensor, lookup,
+                                                         self.inter_arch.pad_rows)
+            self.fused_lookup_steps += 1
+            return self.over_arch(concatenated)
         # The reference runs dense_arch, then sparse_arch (models/dlrm.py:400-401).  Here the lookup and
         # the pooled all-to-all are issued first so that the exchange overlaps the bottom MLP on the
         # collective's own HIP stream; the two branches are independent, results are identical.
