@@ -230,6 +230,68 @@ int tbe_backward_apply_f32(const uint64_t* feat_weights, const int32_t* feat_D,
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * FP16 tables (EmbeddingBagConfig.data_type = DataType.FP16 -> weights_precision = SparseType.FP16:
+ * torchrec/distributed/batched_embedding_kernel.py:406-417, 625-636).  Storage of the tables only:
+ * feat_weights holds base addresses of _Float16 rows with a row stride of feat_D[f] halves; accumulation,
+ * pooled outputs, gradients and optimizer state stay float, and every other argument means what it means
+ * for the _f32 twin.  The arithmetic is the _f32 arithmetic on float(w16), so the forward output is
+ * bit-identical to the _f32 kernels run on the up-cast table; only the final store of an updated row
+ * converts.  Rows move as 8 B per lane when feat_D[f] is a multiple of 4 and the table base is 8-B
+ * aligned, element by element otherwise.  TBE_FLAG_UNIFORM_ALIGNED asserts 16-B aligned row bases here
+ * too, i.e. a dim that is a multiple of 8.  tbe_backward_workspace_bytes, tbe_backward_prepare and the
+ * pair sort do not touch the tables and are shared.
+ *
+ * rounding (backward): how the float result x of a row update becomes a half.
+ *   TBE_ROUND_NEAREST_EVEN  the IEEE conversion.
+ *   TBE_ROUND_STOCHASTIC    with lo <= x <= hi the FP16 neighbours of a finite x (equal when x is
+ *                           representable), the stored value is hi with probability (x - lo) / (hi - lo)
+ *                           in steps of 2^-13, else lo.  The random bits are a counter-based hash of
+ *                           (seed, opt.iteration, global row key = feat_row_base[f] + row, column) and nothing
+ *                           else: the stored table is a pure function of the call's inputs.
+ * TBE_OPT_DENSE_GRAD with FP16 tables returns TBE_ERR_UNSUPPORTED before anything is launched
+ * (DenseTableBatchedEmbeddingBagsCodegen keeps float parameters: batched_embedding_kernel.py:677-704).
+ * ---------------------------------------------------------------------------------- */
+#define TBE_ROUND_NEAREST_EVEN 0
+#define TBE_ROUND_STOCHASTIC 1
+
+/* batched_embedding_kernel.py:546-554 with weights_precision FP16 (pooled lookup) */
+int tbe_forward_pooled_f16w(const uint64_t* feat_weights, const int32_t* feat_D,
+                            const int64_t* feat_out_offset, const int64_t* feat_rows, int32_t F,
+                            int32_t B, int32_t max_D, const int64_t* indices,
+                            int64_t N, const int64_t* offsets, const float* per_sample_weights,
+                            int32_t pooling_mode, const int32_t* feat_pooling, float* out, int64_t out_row_stride,
+                            int32_t* bounds_errors, const int64_t* feat_window, void* stream);
+
+/* batched_embedding_kernel.py:332-335 with weights_precision FP16 (sequence lookup) */
+int tbe_forward_nobag_f16w(const uint64_t* feat_weights, const int64_t* feat_rows, int32_t F,
+                           int32_t B, int32_t D, const int64_t* indices, int64_t N,
+                           const int64_t* offsets, float* out, int32_t* bounds_errors,
+                           void* stream);
+
+/* batched_embedding_kernel.py:604-665 with weights_precision FP16: prepare + apply on one stream */
+int tbe_backward_fused_f16w(const uint64_t* feat_weights, const int32_t* feat_D,
+                            const int64_t* feat_out_offset, const int64_t* feat_rows,
+                            const int64_t* feat_row_base, const uint64_t* feat_state0,
+                            const uint64_t* feat_state1, int32_t F, int32_t B,
+                            int32_t max_D, int32_t key_bits, const int64_t* indices, int64_t N,
+                            const int64_t* offsets, const float* per_sample_weights,
+                            int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+                            int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags,
+                            void* workspace, size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window,
+                            int32_t rounding, uint64_t seed, void* stream);
+
+/* the apply phase after tbe_backward_prepare (same wiring, side-stream sort) for FP16 tables */
+int tbe_backward_apply_f16w(const uint64_t* feat_weights, const int32_t* feat_D,
+                            const int64_t* feat_out_offset, const int64_t* feat_rows,
+                            const int64_t* feat_row_base, const uint64_t* feat_state0,
+                            const uint64_t* feat_state1, int32_t F, int32_t B,
+                            int32_t max_D, int32_t key_bits, const int64_t* indices, int64_t N,
+                            const int64_t* offsets, const float* per_sample_weights,
+                            int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+                            int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags,
+                            void* workspace, size_t workspace_bytes, int32_t rounding, uint64_t seed, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * HBM row cache for EmbeddingLocation.MANAGED_CACHING tables (the `batched_fused_uvm_caching`
  * compute kernel: torchrec/distributed/embedding_types.py:57-76; `flush()` before weights are
  * read: batched_embedding_kernel.py:563,664; default cache_load_factor 0.2:

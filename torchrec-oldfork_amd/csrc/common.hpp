@@ -108,4 +108,18 @@ __device__ __forceinline__ void st4(float* p, float4 v) {
   *reinterpret_cast<float4*>(p) = v;
 }
 
+// _Float16 rows move as 4 halves = 8 B per lane (packed; never as scalar half accesses on the vector path).
+struct alignas(8) half4 {
+  _Float16 x, y, z, w;
+};
+__device__ __forceinline__ half4 ldh4(const _Float16* p) {
+  return *reinterpret_cast<const half4*>(p);
+}
+__device__ __forceinline__ void sth4(_Float16* p, half4 v) {
+  *reinterpret_cast<half4*>(p) = v;
+}
+// Alignment a row base needs for the one-load-per-lane path: 4 elements of the table type.
+template <typename WT>
+constexpr uintptr_t kRowAlignMask = 4 * sizeof(WT) - 1;
+
 }  // namespace tbe

@@ -17,6 +17,7 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libtbe_hip.so"))
 c_void_p = ctypes.c_void_p
 c_i32 = ctypes.c_int32
 c_i64 = ctypes.c_int64
+c_u64 = ctypes.c_uint64
 c_size = ctypes.c_size_t
 c_float = ctypes.c_float
 
@@ -89,6 +90,28 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
          c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
          c_i32, c_void_p, c_size, c_void_p],
+    ),
+    "tbe_forward_pooled_f16w": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64,
+         c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p],
+    ),
+    "tbe_forward_nobag_f16w": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
+         c_void_p],
+    ),
+    "tbe_backward_fused_f16w": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
+         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
+         c_i32, c_void_p, c_size, c_void_p, c_void_p, c_i32, c_u64, c_void_p],
+    ),
+    "tbe_backward_apply_f16w": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
+         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
+         c_i32, c_void_p, c_size, c_i32, c_u64, c_void_p],
     ),
     "tbe_cache_prefetch_workspace_bytes": (c_size, [c_i64, c_i32]),
     "tbe_cache_prefetch": (

@@ -303,8 +303,10 @@ class _TBEBase(nn.Module):
         feature_table_map: Optional[List[int]],
         pooling_mode: PoolingMode,
         device: Optional[torch.device],
+        weights_dtype: torch.dtype = torch.float32,
     ) -> None:
         T = len(rows)
+        self.weights_dtype = weights_dtype  # element type of the tables (optimizer state is always float32)
         if T == 0:
             raise ValueError("embedding_specs is empty")
         self.pooling_mode = PoolingMode(pooling_mode)
@@ -352,8 +354,9 @@ class _TBEBase(nn.Module):
                 )
             p = "dev" if loc == EmbeddingLocation.DEVICE else "uvm"
             self.placement.append(p)
-            # keep every table 16-B aligned inside the flat buffer
-            sizes[p] = (sizes[p] + 3) // 4 * 4
+            # keep every table 16-B aligned inside the flat buffer (4 floats / 8 halves)
+            pad = 16 // weights_dtype.itemsize
+            sizes[p] = (sizes[p] + pad - 1) // pad * pad
             self.weights_offsets.append(sizes[p])
             self.state_row_offsets.append(row_sizes[p])
             sizes[p] += r * d
@@ -387,14 +390,14 @@ class _TBEBase(nn.Module):
         return d
 
     # -- storage helpers ------------------------------------------------------------------
-    def _alloc(self, placement: str, numel: int) -> torch.Tensor:
+    def _alloc(self, placement: str, numel: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
         if self.current_device.type == "meta":
-            return torch.empty(numel, dtype=torch.float32, device="meta")
+            return torch.empty(numel, dtype=dtype, device="meta")
         if placement == "dev":
-            return torch.zeros(numel, dtype=torch.float32, device=self.current_device)
+            return torch.zeros(numel, dtype=dtype, device=self.current_device)
         # MANAGED / MANAGED_CACHING: pinned host memory, GPU-mapped at the same address
         # (HIP unified addressing); the kernels read it over the host link.
-        return torch.zeros(numel, dtype=torch.float32).pin_memory()
+        return torch.zeros(numel, dtype=dtype).pin_memory()
 
     def _flat_weights(self, placement: str) -> torch.Tensor:
         raise NotImplementedError
@@ -454,7 +457,8 @@ class _TBEBase(nn.Module):
         s0, s1 = self._state_ptrs()
         dev = self.current_device
         base = {p: self._flat_weights(p).data_ptr() for p in ("dev", "uvm")}
-        wptr = [base[self.placement[t]] + 4 * self.weights_offsets[t] for t in range(self.T)]
+        esz = self.weights_dtype.itemsize
+        wptr = [base[self.placement[t]] + esz * self.weights_offsets[t] for t in range(self.T)]
         ftm = self.feature_table_map
 
         def i64(vals):
@@ -590,20 +594,26 @@ class _TBEBase(nn.Module):
             self._a2a_cache[B] = hit
         return hit
 
+    def _fp16_tables(self) -> bool:
+        """Which kernel family serves this module (_f16w or _f32): decided by the tables' element type at construction."""
+        return self.weights_dtype == torch.float16
+
     def _forward_impl(self, indices, offsets, per_sample_weights, B: int, into=None) -> torch.Tensor:
         lay = self._get_layout()
         dev = self.current_device
         lib = _lib.load()
         N = indices.numel()
+        f16 = self._fp16_tables()
         with torch.cuda.device(dev):
             if self.pooling_mode == PoolingMode.NONE:
                 D = self.dims_per_table[0]
                 out = torch.empty((N, D), dtype=torch.float32, device=dev)
+                nobag = lib.tbe_forward_nobag_f16w if f16 else lib.tbe_forward_nobag_f32
                 check(
-                    lib.tbe_forward_nobag_f32(ptr(lay.feat_weights), ptr(lay.feat_rows), self.F, B,
-                                              D, ptr(indices), N, ptr(offsets), ptr(out),
-                                              self._errors_ptr(), stream_ptr(dev)),
-                    "tbe_forward_nobag_f32",
+                    nobag(ptr(lay.feat_weights), ptr(lay.feat_rows), self.F, B,
+                          D, ptr(indices), N, ptr(offsets), ptr(out),
+                          self._errors_ptr(), stream_ptr(dev)),
+                    "tbe_forward_nobag_f16w" if f16 else "tbe_forward_nobag_f32",
                 )
                 return out
             if into is not None:
@@ -617,13 +627,14 @@ class _TBEBase(nn.Module):
             else:
                 out_off, stride, shape = self._pooled_layout(B)
                 out = torch.empty(shape, dtype=torch.float32, device=dev)
+            pooled = lib.tbe_forward_pooled_f16w if f16 else lib.tbe_forward_pooled_f32
             check(
-                lib.tbe_forward_pooled_f32(ptr(lay.feat_weights), ptr(lay.feat_D),
-                                           ptr(out_off), ptr(lay.feat_rows), self.F, B,
-                                           self.max_D, ptr(indices), N, ptr(offsets),
-                                           ptr(per_sample_weights), int(self.pooling_mode), ptr(lay.feat_pooling), ptr(out),
-                                           stride, self._errors_ptr(), ptr(lay.feat_window), stream_ptr(dev)),
-                "tbe_forward_pooled_f32",
+                pooled(ptr(lay.feat_weights), ptr(lay.feat_D),
+                       ptr(out_off), ptr(lay.feat_rows), self.F, B,
+                       self.max_D, ptr(indices), N, ptr(offsets),
+                       ptr(per_sample_weights), int(self.pooling_mode), ptr(lay.feat_pooling), ptr(out),
+                       stride, self._errors_ptr(), ptr(lay.feat_window), stream_ptr(dev)),
+                "tbe_forward_pooled_f16w" if f16 else "tbe_forward_pooled_f32",
             )
         return out
 
@@ -704,22 +715,27 @@ class _TBEBase(nn.Module):
         # out 16-B aligned by _init_tables; out offsets are then multiples of 4 as well)
         # (with state0_override — the dense-gradient backward — the state bases are rows of a gradient buffer laid out like
         # the weights: aligned iff that buffer is, which the caller asserts through `state0_aligned`)
-        flags = 1 if (len(set(self.dims_per_table)) == 1 and self.max_D % 4 == 0 and stride % 4 == 0
+        # (FP16 tables: 16-B aligned row bases need a dim that is a multiple of 8)
+        f16 = self._fp16_tables()
+        flags = 1 if (len(set(self.dims_per_table)) == 1 and self.max_D % (8 if f16 else 4) == 0 and stride % 4 == 0
                       and (state0_override is None or state0_aligned)) else 0
+        # FP16 tables: how the float result of a row update is rounded (include/tbe_hip.h TBE_ROUND_*)
+        rounding = (int(getattr(self, "_rounding", 0)), int(getattr(self, "_sr_seed", 0))) if f16 else ()
         if per_sample_weights is not None:
             flags |= _FLAG_WEIGHTED  # the sort payload then carries positions too (set in prepare as well)
         with torch.cuda.device(dev):
             if prepared is not None:
                 ws, ev = prepared
                 torch.cuda.current_stream(dev).wait_event(ev)
+                apply = lib.tbe_backward_apply_f16w if f16 else lib.tbe_backward_apply_f32
                 check(
-                    lib.tbe_backward_apply_f32(ptr(lay.feat_weights), ptr(lay.feat_D), ptr(out_off),
-                                               ptr(lay.feat_rows), ptr(lay.feat_row_base), ptr(feat_state0),
-                                               ptr(lay.feat_state1), self.F, B, self.max_D, self.key_bits,
-                                               ptr(indices), N, ptr(offsets), ptr(per_sample_weights),
-                                               int(self.pooling_mode), ptr(lay.feat_pooling), ptr(grad_out), stride, opt, flags,
-                                               ptr(ws), ws.numel(), stream_ptr(dev)),
-                    "tbe_backward_apply_f32",
+                    apply(ptr(lay.feat_weights), ptr(lay.feat_D), ptr(out_off),
+                          ptr(lay.feat_rows), ptr(lay.feat_row_base), ptr(feat_state0),
+                          ptr(lay.feat_state1), self.F, B, self.max_D, self.key_bits,
+                          ptr(indices), N, ptr(offsets), ptr(per_sample_weights),
+                          int(self.pooling_mode), ptr(lay.feat_pooling), ptr(grad_out), stride, opt, flags,
+                          ptr(ws), ws.numel(), *rounding, stream_ptr(dev)),
+                    "tbe_backward_apply_f16w" if f16 else "tbe_backward_apply_f32",
                 )
                 return
             nbytes = lib.tbe_backward_workspace_bytes(N, self.F, B, self.max_D, self.key_bits)
@@ -727,16 +743,17 @@ class _TBEBase(nn.Module):
                 raise RuntimeError(f"TBE backward: {N} ids in one call is beyond the limit of 2^29 - 1 (include/tbe_hip.h): "
                                    "split the batch")
             ws = workspace(nbytes, dev)
+            fused = lib.tbe_backward_fused_f16w if f16 else lib.tbe_backward_fused_f32
             check(
-                lib.tbe_backward_fused_f32(ptr(lay.feat_weights), ptr(lay.feat_D),
-                                           ptr(out_off), ptr(lay.feat_rows),
-                                           ptr(lay.feat_row_base), ptr(feat_state0),
-                                           ptr(lay.feat_state1), self.F, B,
-                                           self.max_D, self.key_bits, ptr(indices), N, ptr(offsets),
-                                           ptr(per_sample_weights), int(self.pooling_mode), ptr(lay.feat_pooling),
-                                           ptr(grad_out), stride, opt, flags, ptr(ws), ws.numel(),
-                                           self._errors_ptr(), ptr(lay.feat_window), stream_ptr(dev)),
-                "tbe_backward_fused_f32",
+                fused(ptr(lay.feat_weights), ptr(lay.feat_D),
+                      ptr(out_off), ptr(lay.feat_rows),
+                      ptr(lay.feat_row_base), ptr(feat_state0),
+                      ptr(lay.feat_state1), self.F, B,
+                      self.max_D, self.key_bits, ptr(indices), N, ptr(offsets),
+                      ptr(per_sample_weights), int(self.pooling_mode), ptr(lay.feat_pooling),
+                      ptr(grad_out), stride, opt, flags, ptr(ws), ws.numel(),
+                      self._errors_ptr(), ptr(lay.feat_window), *rounding, stream_ptr(dev)),
+                "tbe_backward_fused_f16w" if f16 else "tbe_backward_fused_f32",
             )
 
 
@@ -866,8 +883,15 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
                 "ComputeDevice.CPU is not provided by the MI355X build (no CPU fallback); "
                 "use the reference's `dense`/`sparse` compute kernels on CPU"
             )
-        if weights_precision != SparseType.FP32 or output_dtype != SparseType.FP32:
-            raise NotImplementedError("only FP32 tables / outputs are implemented")
+        if weights_precision not in (SparseType.FP32, SparseType.FP16):
+            raise NotImplementedError(f"weights_precision {weights_precision}: only FP32 and FP16 tables are implemented")
+        if output_dtype != SparseType.FP32:
+            raise NotImplementedError(f"output_dtype {output_dtype}: only FP32 outputs are implemented (FP16 is a storage "
+                                      "format of the tables; pooled outputs and gradients stay FP32)")
+        fp16 = weights_precision == SparseType.FP16
+        if fp16 and any(EmbeddingLocation(loc) == EmbeddingLocation.MANAGED_CACHING for loc in locations):
+            raise NotImplementedError("weights_precision FP16 with EmbeddingLocation.MANAGED_CACHING is not implemented: the "
+                                      "HBM row cache stores float rows (use MANAGED or DEVICE)")
         if optimizer not in _OPT_CODE:
             raise NotImplementedError(f"optimizer {optimizer} is not implemented")
         if gradient_clipping:
@@ -885,8 +909,14 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
                                           "WeightDecayMode.L2 is not implemented")
             if optimizer in (OptimType.EXACT_SGD, OptimType.EXACT_ADAGRAD):
                 raise NotImplementedError(f"weight_decay is not implemented for {optimizer}")
+        wdtype = torch.float16 if fp16 else torch.float32
         self._init_tables(list(rows), list(dims), list(locations), feature_table_map,
-                          pooling_mode, device)
+                          pooling_mode, device, weights_dtype=wdtype)
+        self.weights_precision = weights_precision
+        # FP16 tables: the update's float result is rounded to half stochastically (the fbgemm default) or to nearest
+        # even; the stream of random bits is keyed by a seed drawn once here and by self.iter.  Ignored for FP32.
+        self._rounding = 1 if (fp16 and stochastic_rounding) else 0
+        self._sr_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF if fp16 else 0
         self.optimizer = optimizer
         self.bounds_check_mode = bounds_check_mode
         self.cache_load_factor = cache_load_factor
@@ -904,8 +934,8 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
             momentum=momentum,
         )
         self.iter = 0
-        self.register_buffer("weights_dev", self._alloc("dev", self._flat_sizes["dev"]), persistent=False)
-        self.register_buffer("weights_uvm", self._alloc("uvm", self._flat_sizes["uvm"]), persistent=False)
+        self.register_buffer("weights_dev", self._alloc("dev", self._flat_sizes["dev"], wdtype), persistent=False)
+        self.register_buffer("weights_uvm", self._alloc("uvm", self._flat_sizes["uvm"], wdtype), persistent=False)
         code = _OPT_CODE[optimizer]
         rowwise = code == 1
         elementwise = code in (2, 3)

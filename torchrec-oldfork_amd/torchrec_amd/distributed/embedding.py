@@ -30,7 +30,7 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
-from ..modules.embedding_configs import EmbeddingConfig
+from ..modules.embedding_configs import EmbeddingConfig, sharded_tables_precision
 from ..sparse.jagged_tensor import JaggedTensor, KeyedJaggedTensor
 from .planner import rw_block_size, rw_shard_rows
 from .types import Awaitable, LazyAwaitable, NoWait, ParameterSharding, ShardingEnv, ShardingType
@@ -128,6 +128,10 @@ class ShardedEmbeddingCollection(nn.Module):
         Fg = len(self._feature_names)
         self._tw_feats = [g for g in range(Fg) if owner[g_table[g]] >= 0]
         self._rw_feats = [g for g in range(Fg) if owner[g_table[g]] < 0]
+        # cfg.data_type -> weights_precision of both lookups (batched_embedding_kernel.py:406-417); FP32 adds nothing
+        precision = sharded_tables_precision(tables, [], "ShardedEmbeddingCollection")
+        if precision is not None:
+            fused_params = dict(fused_params or {}, weights_precision=precision)
         self._init_row_wise(tables, g_table, fused_params, tbe_factory)
         self._local_feats = [[g for g in range(Fg) if owner[g_table[g]] == r] for r in range(self._W)]
         self._send_order = [g for lf in self._local_feats for g in lf]

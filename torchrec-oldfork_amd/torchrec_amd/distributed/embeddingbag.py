@@ -42,7 +42,7 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
-from ..modules.embedding_configs import EmbeddingBagConfig, pooling_type_to_pooling_mode
+from ..modules.embedding_configs import EmbeddingBagConfig, pooling_type_to_pooling_mode, sharded_tables_precision
 from ..modules.embedding_modules import EmbeddingBagCollection
 from ..profiling import label
 from ..sparse.jagged_tensor import KeyedJaggedTensor, KeyedTensor
@@ -555,6 +555,12 @@ class ShardedEmbeddingBagCollection(nn.Module):
         win_global = [self._local_tables[i].cfg.num_embeddings for i in ftm_local]
         self._has_rw = any(lt.row_wise for lt in self._local_tables)
         fused_params = dict(fused_params or {})
+        # cfg.data_type of the sharded tables -> the TBE's weights_precision (batched_embedding_kernel.py:406-417); the key
+        # is added for FP16 only, so FP32 collections hand a custom factory exactly the caller's fused_params
+        precision = sharded_tables_precision([c for c, k in zip(cfgs, kind) if k != -2],
+                                             [c for c, k in zip(cfgs, kind) if k == -2], "ShardedEmbeddingBagCollection")
+        if precision is not None:
+            fused_params["weights_precision"] = precision
         factory = tbe_factory or _default_tbe_factory
         self._emb_module = None
         self._row_windows = None

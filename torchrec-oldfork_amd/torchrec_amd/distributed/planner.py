@@ -28,7 +28,7 @@ import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
-from ..modules.embedding_configs import EmbeddingBagConfig
+from ..modules.embedding_configs import EmbeddingBagConfig, data_type_to_bits
 from .types import EmbeddingComputeKernel, ParameterSharding, ShardingPlan, ShardingType, ShardMetadata
 
 GiB = 1 << 30
@@ -80,7 +80,7 @@ class EmbeddingShardingPlanner:
     def plan_tables(self, tables: List[EmbeddingBagConfig]) -> Dict[str, ParameterSharding]:
         W = self.topology.world_size
         cap = int(self.topology.hbm_cap * (1.0 - self.topology.hbm_reserve_fraction))
-        size = {t.name: t.num_embeddings * t.embedding_dim * 4 for t in tables}
+        size = {t.name: t.num_embeddings * t.embedding_dim * data_type_to_bits(t.data_type) // 8 for t in tables}
         by_size = sorted(tables, key=lambda t: (-size[t.name], t.name))
         st_of = {n: (c.sharding_types if isinstance(c, ParameterConstraints) else c) for n, c in self.constraints.items()}
         ck_of = {n: c.compute_kernels for n, c in self.constraints.items()
@@ -124,7 +124,8 @@ class EmbeddingShardingPlanner:
             return shard_bytes
 
         def rw_hbm(r):
-            return sum(hbm_bytes(t, rw_shard_rows(t.num_embeddings, W)[r] * t.embedding_dim * 4) for t in tables if t.name in rw)
+            return sum(hbm_bytes(t, rw_shard_rows(t.num_embeddings, W)[r] * t.embedding_dim * data_type_to_bits(t.data_type) // 8)
+                       for t in tables if t.name in rw)
 
         for t in by_size:  # largest first
             if max(rw_hbm(r) for r in range(W)) <= cap:
