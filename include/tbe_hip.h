@@ -230,6 +230,47 @@ int tbe_backward_apply_f32(const uint64_t* feat_weights, const int32_t* feat_D,
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Gradient of the pooled lookup with respect to per_sample_weights (fbgemm's grad_indice_weights): what
+ * trains the position weights of torchrec/modules/feature_processor.py:29-74 (PositionWeightedModule) in
+ * front of a weighted EmbeddingBagCollection, whose unsharded form gets it from nn.EmbeddingBag's
+ * per_sample_weights gradient (torchrec/modules/embedding_modules.py:165-193).  Arguments that share a name
+ * with tbe_forward_pooled_* mean the same; grad_out is addressed like the forward output.
+ *
+ *   position i of a well-formed bag (f, b):
+ *   giw[i] = s * sum_d grad_out[b * grad_row_stride + feat_out_offset[f] + d] * float(W_f[local row of indices[i], d])
+ *
+ *  - s = 1 for SUM, 1 / len(bag) for a MEAN feature (uniform / per-feature rule of pooling_mode and
+ *    feat_pooling as in the forward; applied as one correctly rounded division of the dot by the length).
+ *    s does not contain the weight itself, so the weights are not an argument.
+ *  - giw[i] = 0, with no table memory touched through it, when the id is TBE_ID_SKIP, outside the feature's
+ *    feat_window or out of range; when feat_requires_grad[f] == 0 (feat_requires_grad: optional [F] int32,
+ *    NULL = every feature, fbgemm's feature_requires_grad); when i lies in no well-formed bag (malformed
+ *    offsets are classified exactly as in the forward: start < 0, end > N, start > end).
+ *  - Every element of giw[0..N) is written by the call.  No bounds-error counter: the forward has already
+ *    counted these ids and bags.
+ *  - TBE_POOL_NONE returns TBE_ERR_UNSUPPORTED; the size and null checks are the forward's and return
+ *    TBE_ERR_INVALID_ARGUMENT before anything is launched; N == 0 or B == 0 is TBE_OK.
+ *  - Only enqueues (one memset node + one kernel): no allocation, no host synchronisation, capturable.
+ *    Tables are read-only, so on a stream the call must precede a fused backward that rewrites them.
+ *  - Deterministic: every summation order is fixed by the launch shape (max_D, F, B, N); no atomics.
+ * _f16w reads _Float16 tables (8 B per lane) and is bit-identical to _f32 on the up-cast table.
+ * ---------------------------------------------------------------------------------- */
+int tbe_backward_indice_weights_f32(const uint64_t* feat_weights, const int32_t* feat_D,
+                                    const int64_t* feat_out_offset, const int64_t* feat_rows, int32_t F,
+                                    int32_t B, int32_t max_D, const int64_t* indices, int64_t N,
+                                    const int64_t* offsets, int32_t pooling_mode, const int32_t* feat_pooling,
+                                    const float* grad_out, int64_t grad_row_stride,
+                                    const int32_t* feat_requires_grad, float* grad_indice_weights,
+                                    const int64_t* feat_window, void* stream);
+int tbe_backward_indice_weights_f16w(const uint64_t* feat_weights, const int32_t* feat_D,
+                                     const int64_t* feat_out_offset, const int64_t* feat_rows, int32_t F,
+                                     int32_t B, int32_t max_D, const int64_t* indices, int64_t N,
+                                     const int64_t* offsets, int32_t pooling_mode, const int32_t* feat_pooling,
+                                     const float* grad_out, int64_t grad_row_stride,
+                                     const int32_t* feat_requires_grad, float* grad_indice_weights,
+                                     const int64_t* feat_window, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * FP16 tables (EmbeddingBagConfig.data_type = DataType.FP16 -> weights_precision = SparseType.FP16:
  * torchrec/distributed/batched_embedding_kernel.py:406-417, 625-636).  Storage of the tables only:
  * feat_weights holds base addresses of _Float16 rows with a row stride of feat_D[f] halves; accumulation,

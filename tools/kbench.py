@@ -1,6 +1,7 @@
 """Kernel-level timing of the TBE hot path at the Criteo-1TB shape (development tool;
 bench.py is the judged harness).
-Usage: python tools/kbench.py [--batch 65536[,4096]] [--cap ROWS] [--precision fp32|fp16] [--rounding stochastic|nearest] [--repeats N] [--json FILE]"""
+Usage: python tools/kbench.py [--batch 65536[,4096]] [--cap ROWS] [--precision fp32|fp16] [--rounding stochastic|nearest] [--repeats N] [--json FILE]
+       python tools/kbench.py --indice-weights-grad [--pooling L] ...   the per-sample-weight gradient next to the weighted forward"""
 import argparse
 import json
 import os
@@ -34,6 +35,9 @@ def main():
                     help="fp16 tables: rounding of the updated rows (stochastic is the module's default)")
     ap.add_argument("--repeats", type=int, default=1, help="repeat every measurement this often (run-to-run spread)")
     ap.add_argument("--json", default="", help="append one JSON record per (batch, repeat) to this file")
+    ap.add_argument("--indice-weights-grad", action="store_true",
+                    help="time tbe_backward_indice_weights_* (HIP events) next to the WEIGHTED forward on the same tables and "
+                         "batches, instead of the forward / backward measurement")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     rows = [min(r, args.cap) if args.cap else r for r in CRITEO_ROWS]
@@ -51,7 +55,7 @@ def main():
           flush=True)
     for B in [int(b) for b in str(args.batch).split(",")]:
         for rep in range(args.repeats):
-            rec = measure(mod, rows, B, D, esz, args)
+            rec = (measure_indice_weights_grad if args.indice_weights_grad else measure)(mod, rows, B, D, esz, args)
             rec.update(batch=B, dim=D, pooling=args.pooling, opt=args.opt, precision=args.precision,
                        rounding=args.rounding if args.precision == "fp16" else None, repeat=rep)
             if args.json:
@@ -148,6 +152,54 @@ def measure(mod, rows, B, D, esz, args):
     print(f"train-step TBE samples/s: {B / ms_fb * 1e3:.3e}", flush=True)
     rec.update(fwd_call_us=ms_f * 1e3, fwd_bwd_call_us=ms_fb * 1e3)
     return rec
+
+
+def measure_indice_weights_grad(mod, rows, B, D, esz, args):
+    """HIP-event time per call of the weighted forward and of the per-sample-weight gradient (memset + gather kernel):
+    blocks of --iters back-to-back calls between one event pair (the queue stays full, so the host's launch path is not
+    part of the reading), the two alternating block by block over the same batches; the value is the median of 5 block
+    means.  The two read the same rows, ids and [B, F*D] block; the forward writes that block, the gradient 4 B per id."""
+    dev = torch.device("cuda", 0)
+    F, L = len(rows), args.pooling
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    batches = [torch.cat([torch.randint(0, r, (B * L,), generator=g, device=dev, dtype=torch.int64) for r in rows])
+               for _ in range(args.nbatches)]
+    offsets = torch.arange(F * B + 1, dtype=torch.int64, device=dev) * L
+    N = F * B * L
+    psw = torch.rand(N, device=dev) + 0.5
+    grad = torch.randn(B, F * D, device=dev)
+    keep = {}
+
+    def fwd(i):
+        keep["out"] = mod._forward_impl(batches[i % len(batches)], offsets, psw, B)
+
+    def giw(i):
+        keep["giw"] = mod._indice_weights_grad(grad, batches[i % len(batches)], offsets, B)
+
+    times = {"fwd": [], "giw": []}
+    for i in range(3):
+        fwd(i)
+        giw(i)
+    torch.cuda.synchronize()
+    for block in range(5):
+        for name, fn in (("fwd", fwd), ("giw", giw)):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for i in range(args.iters):
+                fn(i)
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.iters)
+    f_us, g_us = float(np.median(times["fwd"])), float(np.median(times["giw"]))
+    common = N * (D * esz + 8) + F * B * (D * 4 + 8)  # rows + ids, the [B, F*D] block + offsets
+    fwd_bytes, giw_bytes = common + N * 4, common + 2 * N * 4  # + weights read ; + giw zeroed and written
+    print(f"[B={B} L={L} {args.precision}] weighted fwd: {f_us:.1f} us ({fwd_bytes / f_us / 1e6:.2f} TB/s)   "
+          f"indice_weights_grad: {g_us:.1f} us ({giw_bytes / g_us / 1e6:.2f} TB/s)   ratio {g_us / f_us:.3f}", flush=True)
+    return {"weighted_fwd_us": f_us, "indice_weights_grad_us": g_us, "ratio": g_us / f_us,
+            "weighted_fwd_us_min_max": [min(times["fwd"]), max(times["fwd"])],
+            "indice_weights_grad_us_min_max": [min(times["giw"]), max(times["giw"])],
+            "weighted_fwd_bytes": fwd_bytes, "indice_weights_grad_bytes": giw_bytes}
 
 
 if __name__ == "__main__":

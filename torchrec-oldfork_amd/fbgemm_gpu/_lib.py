@@ -113,6 +113,16 @@ SIGNATURES = {
          c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
          c_i32, c_void_p, c_size, c_i32, c_u64, c_void_p],
     ),
+    "tbe_backward_indice_weights_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64,
+         c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "tbe_backward_indice_weights_f16w": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64,
+         c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "tbe_cache_prefetch_workspace_bytes": (c_size, [c_i64, c_i32]),
     "tbe_cache_prefetch": (
         ctypes.c_int,

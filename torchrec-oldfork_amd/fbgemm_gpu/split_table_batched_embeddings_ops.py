@@ -756,6 +756,56 @@ class _TBEBase(nn.Module):
                 "tbe_backward_fused_f16w" if f16 else "tbe_backward_fused_f32",
             )
 
+    def _indice_weights_grad(self, grad_out, indices, offsets, B: int, layout=None,
+                             feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The gradient of a pooled lookup with respect to its per_sample_weights (fbgemm's grad_indice_weights;
+        include/tbe_hip.h `tbe_backward_indice_weights_*`): a float32 [N] tensor, 0 at the positions of features that
+        `feature_requires_grad` ([F], non-zero = wanted; None = all) masks.  Reads the tables through the layout of the
+        forward — behind the row cache that is the cache pseudo-table with the remapped ids — so it has to be enqueued
+        before a fused backward of the same lookup, which rewrites those rows in place."""
+        if self.pooling_mode == PoolingMode.NONE:
+            raise RuntimeError("PoolingMode.NONE takes no per_sample_weights: there is no gradient for them")
+        lay = self._get_layout()
+        dev = self.current_device
+        lib = _lib.load()
+        N = indices.numel()
+        giw = torch.empty(N, dtype=torch.float32, device=dev)
+        if N == 0:
+            return giw
+        if B == 0:
+            return giw.zero_()
+        grad_out = grad_out.contiguous()
+        if grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()
+        if layout is not None:
+            out_off, stride = layout
+        else:
+            out_off, stride, _ = self._pooled_layout(B)
+        frg = None
+        if feature_requires_grad is not None:
+            frg = feature_requires_grad.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+            if frg.numel() != self.F:
+                raise RuntimeError(f"feature_requires_grad has {frg.numel()} entries; expected F={self.F}")
+        f16 = self._fp16_tables()
+        with torch.cuda.device(dev):
+            fn = lib.tbe_backward_indice_weights_f16w if f16 else lib.tbe_backward_indice_weights_f32
+            check(
+                fn(ptr(lay.feat_weights), ptr(lay.feat_D), ptr(out_off), ptr(lay.feat_rows), self.F, B, self.max_D,
+                   ptr(indices), N, ptr(offsets), int(self.pooling_mode), ptr(lay.feat_pooling), ptr(grad_out), stride,
+                   ptr(frg), ptr(giw), ptr(lay.feat_window), stream_ptr(dev)),
+                "tbe_backward_indice_weights_f16w" if f16 else "tbe_backward_indice_weights_f32",
+            )
+        return giw
+
+    def indice_weights_grad(self, rec: "LookupRecord", grad_out: torch.Tensor,
+                            feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Explicit path: the per_sample_weights gradient of the lookup `rec` describes, given the gradient of its pooled
+        output.  Must be called BEFORE backward_no_autograd(rec, ...) on the same stream: the fused update rewrites in
+        place the rows this reads."""
+        if rec.per_sample_weights is None:
+            raise RuntimeError("indice_weights_grad: the lookup had no per_sample_weights")
+        return self._indice_weights_grad(grad_out, rec.indices, rec.offsets, rec.B, rec.layout, feature_requires_grad)
+
 
 class LookupRecord:
     """What a lookup made through `lookup_no_autograd` leaves for `backward_no_autograd` (the explicit counterpart of an
@@ -773,8 +823,9 @@ class _FusedLookupInto(torch.autograd.Function):
     """Like _FusedLookup, but writes its column blocks into a caller-provided [B, stride] buffer."""
 
     @staticmethod
-    def forward(ctx, out, placeholder, module, indices, offsets, per_sample_weights, B, out_off, stride, prepare):
-        ctx.module, ctx.B, ctx.layout = module, B, (out_off, stride)
+    def forward(ctx, out, placeholder, module, indices, offsets, per_sample_weights, B, out_off, stride, prepare,
+                feature_requires_grad=None):
+        ctx.module, ctx.B, ctx.layout, ctx.frg = module, B, (out_off, stride), feature_requires_grad
         ctx.save_for_backward(indices, offsets, per_sample_weights)
         module._forward_impl(indices, offsets, per_sample_weights, B, into=(out, out_off, stride))
         ctx.prepared = module._prepare_or_defer(ctx, indices, offsets, B, per_sample_weights is not None) if prepare else None
@@ -785,19 +836,23 @@ class _FusedLookupInto(torch.autograd.Function):
     def backward(ctx, grad_out):
         indices, offsets, psw = ctx.saved_tensors
         module = ctx.module
+        # before the update: it reads the rows the update rewrites (same stream)
+        giw = (module._indice_weights_grad(grad_out, indices, offsets, ctx.B, ctx.layout, ctx.frg)
+               if ctx.needs_input_grad[5] else None)
         module.iter += 1
         module._backward_impl(grad_out, indices, offsets, psw, ctx.B, module._optimizer_struct(),
                               prepared=ctx.prepared, layout=ctx.layout)
         ctx.prepared = None
         if module._cache is not None:
             module._cache.after_backward()
-        return (grad_out,) + (None,) * 9
+        return (grad_out, None, None, None, None, giw) + (None,) * 5
 
 
 class _DenseLookupInto(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, out, weights, module, indices, offsets, per_sample_weights, B, out_off, stride):
-        ctx.module, ctx.B, ctx.layout = module, B, (out_off, stride)
+    def forward(ctx, out, weights, module, indices, offsets, per_sample_weights, B, out_off, stride,
+                feature_requires_grad=None):
+        ctx.module, ctx.B, ctx.layout, ctx.frg = module, B, (out_off, stride), feature_requires_grad
         ctx.save_for_backward(indices, offsets, per_sample_weights)
         module._forward_impl(indices, offsets, per_sample_weights, B, into=(out, out_off, stride))
         ctx.mark_dirty(out)
@@ -812,16 +867,20 @@ class _DenseLookupInto(torch.autograd.Function):
         opt = OptimizerArgs(_OPT_DENSE_GRAD, 0.0, 0.0, 0.0, 0.0, 0.0, 1)
         module._backward_impl(grad_out, indices, offsets, psw, ctx.B, opt, state0_override=state0, layout=ctx.layout,
                               state0_aligned=grad_w.data_ptr() % 16 == 0)
-        return (grad_out, grad_w) + (None,) * 7
+        giw = (module._indice_weights_grad(grad_out, indices, offsets, ctx.B, ctx.layout, ctx.frg)
+               if ctx.needs_input_grad[5] else None)
+        return (grad_out, grad_w, None, None, None, giw) + (None,) * 4
 
 
 class _FusedLookup(torch.autograd.Function):
-    """forward = TBE gather/pool; backward = coalesce + fused optimizer (no weight grad)."""
+    """forward = TBE gather/pool; backward = coalesce + fused optimizer (no table grad), plus the per_sample_weights
+    gradient when those require grad."""
 
     @staticmethod
-    def forward(ctx, placeholder, module, indices, offsets, per_sample_weights, B, prepare):
+    def forward(ctx, placeholder, module, indices, offsets, per_sample_weights, B, prepare, feature_requires_grad=None):
         ctx.module = module
         ctx.B = B
+        ctx.frg = feature_requires_grad
         ctx.save_for_backward(indices, offsets, per_sample_weights)
         out = module._forward_impl(indices, offsets, per_sample_weights, B)
         ctx.prepared = module._prepare_or_defer(ctx, indices, offsets, B, per_sample_weights is not None) if prepare else None
@@ -831,13 +890,16 @@ class _FusedLookup(torch.autograd.Function):
     def backward(ctx, grad_out):
         indices, offsets, psw = ctx.saved_tensors
         module = ctx.module
+        # before the update: it reads the rows the update rewrites (same stream)
+        giw = (module._indice_weights_grad(grad_out, indices, offsets, ctx.B, None, ctx.frg)
+               if ctx.needs_input_grad[4] else None)
         module.iter += 1
         module._backward_impl(grad_out, indices, offsets, psw, ctx.B, module._optimizer_struct(),
                               prepared=ctx.prepared)
         ctx.prepared = None
         if module._cache is not None:
             module._cache.after_backward()
-        return None, None, None, None, None, None, None
+        return None, None, None, None, giw, None, None, None
 
 
 class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
@@ -1049,12 +1111,13 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         prepare = torch.is_grad_enabled() and (
             mode in (True, "1") or (mode == "auto" and indices.numel() <= self.overlap_backward_sort_max_ids))
         out = _FusedLookup.apply(self.placeholder_autograd_tensor, self, indices, offsets,
-                                 per_sample_weights, B, prepare)
+                                 per_sample_weights, B, prepare, feature_requires_grad)
         self._enforce_bounds_check_mode()
         return out
 
     def forward_into(self, out: torch.Tensor, out_offsets: torch.Tensor, row_stride: int, indices: torch.Tensor,
-                     offsets: torch.Tensor, per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     offsets: torch.Tensor, per_sample_weights: Optional[torch.Tensor] = None,
+                     feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Pooled lookup whose feature blocks land at `out[b * row_stride + out_offsets[f] + d]` of the
         given buffer (returned, marked dirty for autograd)."""
         indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
@@ -1064,7 +1127,7 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         prepare = torch.is_grad_enabled() and (
             mode in (True, "1") or (mode == "auto" and indices.numel() <= self.overlap_backward_sort_max_ids))
         out = _FusedLookupInto.apply(out, self.placeholder_autograd_tensor, self, indices, offsets,
-                                     per_sample_weights, B, out_offsets, int(row_stride), prepare)
+                                     per_sample_weights, B, out_offsets, int(row_stride), prepare, feature_requires_grad)
         self._enforce_bounds_check_mode()
         return out
 
@@ -1124,9 +1187,10 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
 
 class _DenseLookup(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, weights, module, indices, offsets, per_sample_weights, B):
+    def forward(ctx, weights, module, indices, offsets, per_sample_weights, B, feature_requires_grad=None):
         ctx.module = module
         ctx.B = B
+        ctx.frg = feature_requires_grad
         ctx.save_for_backward(indices, offsets, per_sample_weights)
         return module._forward_impl(indices, offsets, per_sample_weights, B)
 
@@ -1139,7 +1203,9 @@ class _DenseLookup(torch.autograd.Function):
         opt = OptimizerArgs(_OPT_DENSE_GRAD, 0.0, 0.0, 0.0, 0.0, 0.0, 1)
         module._backward_impl(grad_out, indices, offsets, psw, ctx.B, opt, state0_override=state0,
                               state0_aligned=grad_w.data_ptr() % 16 == 0)
-        return grad_w, None, None, None, None, None
+        giw = (module._indice_weights_grad(grad_out, indices, offsets, ctx.B, None, ctx.frg)
+               if ctx.needs_input_grad[4] else None)
+        return grad_w, None, None, None, giw, None, None
 
 
 class DenseTableBatchedEmbeddingBagsCodegen(_TBEBase):
@@ -1193,13 +1259,14 @@ class DenseTableBatchedEmbeddingBagsCodegen(_TBEBase):
                 per_sample_weights: Optional[torch.Tensor] = None,
                 feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
         indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
-        return _DenseLookup.apply(self.weights, self, indices, offsets, per_sample_weights, B)
+        return _DenseLookup.apply(self.weights, self, indices, offsets, per_sample_weights, B, feature_requires_grad)
 
     def forward_into(self, out: torch.Tensor, out_offsets: torch.Tensor, row_stride: int, indices: torch.Tensor,
-                     offsets: torch.Tensor, per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     offsets: torch.Tensor, per_sample_weights: Optional[torch.Tensor] = None,
+                     feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
         indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
         return _DenseLookupInto.apply(out, self.weights, self, indices, offsets, per_sample_weights, B, out_offsets,
-                                      int(row_stride))
+                                      int(row_stride), feature_requires_grad)
 
     def lookup_no_autograd(self, indices: torch.Tensor, offsets: torch.Tensor,
                            per_sample_weights: Optional[torch.Tensor] = None, into=None):

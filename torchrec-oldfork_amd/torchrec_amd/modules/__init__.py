@@ -1,0 +1,1 @@
+from .feature_processor import BaseFeatureProcessor, PositionWeightedModule  # noqa: F401

@@ -237,8 +237,16 @@ class KeyedJaggedTensor:
         lpk = self.length_per_key()
         keys = [self._keys[i] for i in indices]
         new_lpk = [lpk[i] for i in indices]
+        w = self._weights
+        # permute_2D_sparse_data has no autograd.  Weights that are being trained (PositionWeightedModule) travel as their
+        # positions instead and are gathered by a differentiable index_select: a key listed twice accumulates both uses.
+        trained = w is not None and w.requires_grad and torch.is_grad_enabled()
+        if trained:
+            w = torch.arange(w.numel(), dtype=torch.int64, device=w.device)
         lengths, values, weights = torch.ops.fbgemm.permute_2D_sparse_data(
-            indices_tensor, self.lengths().view(len(self._keys), -1), self._values, self._weights, sum(new_lpk))
+            indices_tensor, self.lengths().view(len(self._keys), -1), self._values, w, sum(new_lpk))
+        if trained:
+            weights = self._weights.view(-1).index_select(0, weights)
         return KeyedJaggedTensor(
             keys=keys, values=values, weights=weights, lengths=lengths.view(-1), stride=self._stride,
             length_per_key=new_lpk if keys else None,
