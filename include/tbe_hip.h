@@ -481,6 +481,28 @@ int tbe_pooled_exchange_pack(const float* grad, float* send, const int32_t* feat
                              int32_t all_multiple_of_4, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * permute_pooled_embs: reorders the column segments of a pooled-embedding matrix — the op behind
+ * fbgemm_gpu.permute_pooled_embedding_modules.PermutePooledEmbeddings, which the reference's column-wise
+ * sharding installs as the callback of its pooled all-to-all
+ * (torchrec/distributed/sharding/cw_sharding.py:221-231) to put a table's column shards, which arrive
+ * grouped by rank, back next to each other.
+ *   in / out [B, D_total] float32, contiguous, distinct buffers; T segments
+ *   offset_dim_list [T+1]     int64 device: complete cumsum of the input segments' dims
+ *   permute_list [T]          int64 device: output segment i is input segment permute_list[i]
+ *   inv_offset_dim_list [T+1] int64 device: complete cumsum of dims[permute_list[i]]
+ *   out[:, inv_offset[i]:inv_offset[i+1]] = in[:, offset[permute[i]]:offset[permute[i]+1]]
+ * The backward is the same call with (inv_offset_dim_list, inv_permute_list, offset_dim_list).
+ * all_multiple_of_4 != 0 asserts every dim is a multiple of 4 (16-B accesses when both pointers are
+ * 16-B aligned too; a scalar kernel otherwise).  One launch on `stream`, no synchronisation (capturable
+ * into a HIP graph); B * D_total == 0 is TBE_OK without a launch; a T beyond the LDS budget of the
+ * staged lists (about 7 000 segments) returns TBE_ERR_UNSUPPORTED.  Inconsistent lists never make the
+ * kernel touch memory outside the two matrices: such segments are left unwritten.
+ * ---------------------------------------------------------------------------------- */
+int tbe_permute_pooled_embs_f32(const float* in, float* out, const int64_t* offset_dim_list,
+                                const int64_t* permute_list, const int64_t* inv_offset_dim_list, int32_t T,
+                                int32_t B, int32_t D_total, int32_t all_multiple_of_4, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Fused DLRM dot interaction (the path's only MFMA user): InteractionArch.forward,
  * torchrec/models/dlrm.py:193-219 — cat + bmm(X, X^T) + triu gather + cat — and its autograd
  * backward, each as one kernel on v_mfma_f32_16x16x4_f32 (exact f32).

@@ -162,6 +162,8 @@ SIGNATURES = {
         ctypes.c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32,
          c_i32, c_i32, c_float, c_void_p]),
+    "tbe_permute_pooled_embs_f32": (
+        ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p]),
     "tbe_dlrm_interaction_forward_f32": (
         ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p]),
     "tbe_dlrm_interaction_backward_f32": (

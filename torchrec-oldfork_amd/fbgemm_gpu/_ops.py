@@ -8,12 +8,15 @@ Schemas are the ones the reference calls:
   * block_bucketize_sparse_features     torchrec/distributed/embedding_sharding.py:160-168
   * offsets_range                       torchrec/modules/feature_processor.py:65
   * jagged_2d_to_dense                  examples/bert4rec/models/bert4rec.py:394-400
+  * permute_pooled_embs(_auto_grad)     fbgemm_gpu/permute_pooled_embedding_modules.py, the callback of
+                                        torchrec/distributed/sharding/cw_sharding.py:221-231
 Only the CUDA (= HIP on ROCm) dispatch key is registered: a CPU tensor raises
 ``NotImplementedError`` from the dispatcher — there is no CPU fallback in the product.
 """
 from typing import Optional, Tuple
 
 import torch
+from torch.utils.weak import WeakIdKeyDictionary
 
 from . import _lib
 from ._lib import check, ptr, require_gpu, stream_ptr, workspace
@@ -33,6 +36,10 @@ _DEFS = [
     "(Tensor, Tensor, Tensor?, Tensor?, Tensor?)",
     "offsets_range(Tensor offsets, int range_size) -> Tensor",
     "jagged_2d_to_dense(Tensor values, Tensor offsets, int max_sequence_length) -> Tensor",
+    "permute_pooled_embs(Tensor pooled_embs, Tensor offset_dim_list, Tensor permute_list, "
+    "Tensor inv_offset_dim_list, Tensor inv_permute_list) -> Tensor",
+    "permute_pooled_embs_auto_grad(Tensor pooled_embs, Tensor offset_dim_list, Tensor permute_list, "
+    "Tensor inv_offset_dim_list, Tensor inv_permute_list) -> Tensor",
 ]
 
 _def_lib = torch.library.Library("fbgemm", "DEF")
@@ -217,6 +224,64 @@ def _jagged_2d_to_dense_backward(ctx, grad_dense):
     return grad_values, None, None
 
 
+# offset list -> (tensor version, every entry a multiple of 4): the 16-B path's precondition is a property of the list's
+# CONTENTS, which live on the device; it is read back once per list (PermutePooledEmbeddings seeds it from the host lists,
+# so a module's calls never synchronise and can be captured into a HIP graph)
+_offsets_multiple_of_4 = WeakIdKeyDictionary()
+
+
+def note_offsets_multiple_of_4(offsets: torch.Tensor, value: bool) -> None:
+    _offsets_multiple_of_4[offsets] = (offsets._version, bool(value))
+
+
+def _multiple_of_4(offsets: torch.Tensor) -> bool:
+    hit = _offsets_multiple_of_4.get(offsets)
+    if hit is None or hit[0] != offsets._version:
+        hit = (offsets._version, bool((offsets % 4 == 0).all().item()))
+        _offsets_multiple_of_4[offsets] = hit
+    return hit[1]
+
+
+def permute_pooled_embs(pooled_embs: torch.Tensor, offset_dim_list: torch.Tensor, permute_list: torch.Tensor,
+                        inv_offset_dim_list: torch.Tensor, inv_permute_list: torch.Tensor) -> torch.Tensor:
+    """out[:, inv_offset[i]:inv_offset[i+1]] = pooled_embs[:, offset[permute[i]]:offset[permute[i]+1]]
+    (csrc/permute_pooled.hip).  `inv_permute_list` is the backward's permutation; the forward does not read it."""
+    dev = require_gpu(pooled_embs, offset_dim_list, permute_list, inv_offset_dim_list, inv_permute_list)
+    if pooled_embs.dim() != 2 or pooled_embs.dtype != torch.float32:
+        raise RuntimeError("permute_pooled_embs: pooled_embs must be float32 [B, D_total]")
+    T = permute_list.numel()
+    for name, t, n in (("offset_dim_list", offset_dim_list, T + 1), ("permute_list", permute_list, T),
+                       ("inv_offset_dim_list", inv_offset_dim_list, T + 1), ("inv_permute_list", inv_permute_list, T)):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"permute_pooled_embs: {name} must be a contiguous int64 vector of {n} entries")
+    x = pooled_embs.contiguous()
+    B, D_total = x.shape
+    out = torch.empty_like(x)
+    vec = _multiple_of_4(offset_dim_list) and _multiple_of_4(inv_offset_dim_list)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_permute_pooled_embs_f32(ptr(x), ptr(out), ptr(offset_dim_list), ptr(permute_list),
+                                                      ptr(inv_offset_dim_list), T, B, D_total, int(vec), stream_ptr(dev)),
+              "tbe_permute_pooled_embs_f32")
+    return out
+
+
+def _permute_pooled_setup(ctx, inputs, output):
+    _, offset_dim_list, permute_list, inv_offset_dim_list, inv_permute_list = inputs
+    ctx.save_for_backward(offset_dim_list, permute_list, inv_offset_dim_list, inv_permute_list)
+
+
+def _permute_pooled_backward(ctx, grad_out):
+    offset_dim_list, permute_list, inv_offset_dim_list, inv_permute_list = ctx.saved_tensors
+    if not grad_out.is_cuda:
+        raise RuntimeError("permute_pooled_embs backward: no CPU fallback in the MI355X build")
+    # the same copy with the roles swapped: the gradient's segments are laid out by inv_offset_dim_list
+    grad_in = torch.ops.fbgemm.permute_pooled_embs_auto_grad(grad_out, inv_offset_dim_list, inv_permute_list,
+                                                              offset_dim_list, permute_list)
+    return grad_in, None, None, None, None
+
+
+torch.library.register_autograd("fbgemm::permute_pooled_embs_auto_grad", _permute_pooled_backward,
+                                setup_context=_permute_pooled_setup)
 torch.library.register_autograd("fbgemm::jagged_2d_to_dense", _jagged_2d_to_dense_backward,
                                 setup_context=_jagged_2d_to_dense_setup)
 
@@ -227,5 +292,8 @@ _impl_lib.impl("permute_2D_sparse_data", permute_2D_sparse_data)
 _impl_lib.impl("block_bucketize_sparse_features", block_bucketize_sparse_features)
 _impl_lib.impl("offsets_range", offsets_range)
 _impl_lib.impl("jagged_2d_to_dense", jagged_2d_to_dense_forward)
+# permute_pooled_embs is the plain op (no gradient: autograd raises on it); _auto_grad is the differentiable one
+_impl_lib.impl("permute_pooled_embs", permute_pooled_embs)
+_impl_lib.impl("permute_pooled_embs_auto_grad", permute_pooled_embs)
 # permute_1D_sparse_data / expand_into_jagged_permute: schema only (variable-batch path,
 # SURVEY.md §2a "OUT OF SCOPE"); calling them raises from the dispatcher.

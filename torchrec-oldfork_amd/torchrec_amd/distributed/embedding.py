@@ -124,7 +124,8 @@ class ShardedEmbeddingCollection(nn.Module):
             elif ps.sharding_type == ShardingType.ROW_WISE.value:
                 owner.append(-1)
             else:
-                raise NotImplementedError("sequence embeddings: table_wise and row_wise sharding are implemented")
+                raise NotImplementedError(f"table {c.name}: sequence embeddings: table_wise and row_wise sharding are "
+                                          f"implemented (the plan asks for {ps.sharding_type})")
         Fg = len(self._feature_names)
         self._tw_feats = [g for g in range(Fg) if owner[g_table[g]] >= 0]
         self._rw_feats = [g for g in range(Fg) if owner[g_table[g]] < 0]

@@ -31,6 +31,11 @@ Tiny tables can be DATA_PARALLEL (replicated): a dense-gradient TBE looks them u
 batch and writes straight into its columns of the output matrix (no exchange, no cat); their
 gradient is all-reduced by DDP like any dense parameter (sharding/dp_sharding.py in the reference).
 
+Column-wise tables (COLUMN_WISE / TABLE_COLUMN_WISE, the same thing on one node; sharding/cw_sharding.py in the reference):
+every list of this module is in units of PIECES — (feature, column shard); other tables have one piece per feature.  A local
+column shard is its own [rows, width] table of the rank's one lookup, the ids of a feature go to every rank holding one of
+its shards, and the exchange kernels see one descriptor entry per piece.
+
 Forward issues the lookup and the a2a before the caller's dense work and waits afterwards
 (`forward()` returns an awaitable), so the exchange overlaps the bottom MLP; autograd replays
 the same overlap in reverse for the gradient exchange.
@@ -120,6 +125,69 @@ def wrap_sharded(local: Optional[torch.Tensor], global_size: List[int], shards: 
     return ShardedTensor._init_from_local_shards_and_global_metadata(mine, meta, process_group=pg)
 
 
+def wrap_sharded_pieces(local: List[Tuple[int, torch.Tensor]], global_size: List[int],
+                        shards: List[Tuple[List[int], List[int], int]], pg, me: int, device: torch.device):
+    """wrap_sharded for a rank that may hold SEVERAL shards of the tensor (the column shards of a column-wise table):
+    `local` = [(index into `shards`, tensor)]."""
+    from torch.distributed._shard.metadata import ShardMetadata as TorchShardMetadata
+    from torch.distributed._shard.sharded_tensor import Shard, ShardedTensor, ShardedTensorMetadata, TensorProperties
+
+    metas = [TorchShardMetadata(shard_offsets=list(o), shard_sizes=list(z), placement=_placement(r, me, device))
+             for o, z, r in shards]
+    mine = [Shard(t, metas[i]) for i, t in local]
+    dtype = local[0][1].dtype if local else torch.float32
+    meta = ShardedTensorMetadata(shards_metadata=metas, size=torch.Size(global_size),
+                                 tensor_properties=TensorProperties(dtype=dtype, requires_grad=False))
+    return ShardedTensor._init_from_local_shards_and_global_metadata(mine, meta, process_group=pg)
+
+
+def load_pieces(pieces: List[Tuple[torch.Tensor, List[int]]], value, global_size: List[int], what: str) -> None:
+    """Copies `value` into `pieces` = [(destination view, its offsets inside the global tensor)]: a ShardedTensor whose local
+    shards sit at exactly the pieces' offsets, or a whole tensor of `global_size`, which is cut at every piece's offsets."""
+    if hasattr(value, "local_shards") and hasattr(value, "metadata"):
+        have = {tuple(sh.metadata.shard_offsets): sh.tensor for sh in value.local_shards()}
+        for dst, off in pieces:
+            src = have.get(tuple(off))
+            if src is None or tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"{what}: no local shard of shape {tuple(dst.shape)} at offsets {list(off)} "
+                                 f"(found {[(list(k), tuple(v.shape)) for k, v in have.items()]})")
+            dst.copy_(src)
+        return
+    if list(value.shape) != list(global_size):
+        raise ValueError(f"{what}: expected a ShardedTensor over the local pieces or a whole tensor of shape "
+                         f"{list(global_size)}, got {list(value.shape)}")
+    for dst, off in pieces:
+        dst.copy_(value[tuple(slice(o, o + n) for o, n in zip(off, dst.shape))])
+
+
+class ColumnShardedState:
+    """The fused optimizer's state of ONE column-wise table on this rank: every column shard keeps its own state, computed
+    over its own columns (fbgemm's behaviour: row-wise Adagrad of a column-wise table is NOT the unsharded table's).
+    Exposed as the reference does (batched_embedding_kernel.py:71-96): a per-row state is a 1-D tensor of rows x shards with
+    shard i (column order) at offset i x rows; a per-element state is [rows, D] with the shard at its columns."""
+
+    def __init__(self, pieces: List[Tuple[int, int, torch.Tensor]], n_shards: int, rows: int, dim: int) -> None:
+        self.pieces, self.n_shards, self.rows, self.dim = pieces, n_shards, rows, dim  # pieces: (shard, first column, view)
+        self.per_row = pieces[0][2].dim() == 1
+
+    def global_size(self) -> List[int]:
+        return [self.rows * self.n_shards] if self.per_row else [self.rows, self.dim]
+
+    def offsets(self) -> List[Tuple[torch.Tensor, List[int]]]:
+        return [(t, [i * self.rows] if self.per_row else [0, c]) for i, c, t in self.pieces]
+
+    def full(self) -> torch.Tensor:
+        """A COPY of global shape; shards other ranks hold are zero."""
+        first = self.pieces[0][2]
+        out = first.new_zeros(self.global_size())
+        for t, off in self.offsets():
+            out[tuple(slice(o, o + n) for o, n in zip(off, t.shape))] = t
+        return out
+
+    def load(self, value, what: str) -> None:
+        load_pieces(self.offsets(), value, self.global_size(), what)
+
+
 def unwrap_local(value):
     """A tensor out of a state_dict value: the local shard of a ShardedTensor, the tensor itself otherwise."""
     if hasattr(value, "local_shards") and hasattr(value, "metadata"):
@@ -131,10 +199,45 @@ def unwrap_local(value):
 
 
 class _LocalTable:
+    """One table of this rank's fused lookup: a whole table (table-wise), a row block (row-wise) or ONE column shard of a
+    column-wise table (`column_shard` = (shard number in column order, shards of the table); columns
+    [col_offset, col_offset + cols) of every row)."""
+
     def __init__(self, cfg: EmbeddingBagConfig, local_rows: int, row_offset: int, row_wise: bool,
-                 compute_kernel: str = "batched_fused") -> None:
+                 compute_kernel: str = "batched_fused", col_offset: int = 0, cols: Optional[int] = None,
+                 column_shard: Optional[Tuple[int, int]] = None) -> None:
         self.cfg, self.local_rows, self.row_offset, self.row_wise = cfg, local_rows, row_offset, row_wise
         self.compute_kernel = compute_kernel
+        self.col_offset, self.cols = col_offset, (cfg.embedding_dim if cols is None else cols)
+        self.column_shard = column_shard
+
+
+def _column_shards(name: str, cfg: EmbeddingBagConfig, ps: ParameterSharding, W: int) -> List[Tuple[int, int, int]]:
+    """[(first column, width, rank)] of a column-wise table in column order, validated: the shards tile [0, D) without
+    gaps or overlap, every shard has all rows, every rank exists.  ValueError names the table otherwise."""
+    spec, ranks = ps.sharding_spec, ps.ranks
+    if not spec or ranks is None or len(ranks) != len(spec):
+        raise ValueError(f"table {name}: a column-wise plan needs one rank per shard of its sharding_spec "
+                         f"({0 if ranks is None else len(ranks)} ranks, {len(spec or [])} shards)")
+    shards = []
+    for sm, r in zip(spec, ranks):
+        if list(sm.shard_offsets)[0] != 0 or list(sm.shard_sizes)[0] != cfg.num_embeddings:
+            raise ValueError(f"table {name}: column shard at {list(sm.shard_offsets)} of size {list(sm.shard_sizes)} does not "
+                             f"hold all {cfg.num_embeddings} rows")
+        if not 0 <= int(r) < W:
+            raise ValueError(f"table {name}: column shard at column {sm.shard_offsets[1]} is placed on rank {r}, "
+                             f"outside the world of {W}")
+        shards.append((int(sm.shard_offsets[1]), int(sm.shard_sizes[1]), int(r)))
+    shards.sort(key=lambda x: x[0])
+    col = 0
+    for c, w, _ in shards:
+        if c != col or w <= 0:
+            raise ValueError(f"table {name}: column shards {[(c, w) for c, w, _ in shards]} do not tile [0, {cfg.embedding_dim}) "
+                             f"(gap or overlap at column {col})")
+        col += w
+    if col != cfg.embedding_dim:
+        raise ValueError(f"table {name}: column shards {[(c, w) for c, w, _ in shards]} do not tile [0, {cfg.embedding_dim})")
+    return shards
 
 
 class SparseFeaturesDist:
@@ -354,8 +457,13 @@ class EmbeddingFusedOptimizer:
     nested under the parameter key (:241-249).  Tensors are views of the module's storage; for MANAGED_CACHING
     tables the HBM row cache is written back before they are handed out."""
 
-    def __init__(self, emb_module, table_names: List[str], key_prefix: str = "", wrap=None) -> None:
+    def __init__(self, emb_module, table_names: List[str], key_prefix: str = "", wrap=None, column_shards=None,
+                 wrap_columns=None) -> None:
         self._wrap = wrap  # (table name, local tensor) -> ShardedTensor | tensor; None = plain tensors
+        # column-wise tables: per local table (shard number, shards, first column, D) or None; their state is one
+        # ColumnShardedState per table, handed out through wrap_columns(name, state) -> ShardedTensor | assembled copy
+        self._column_shards = column_shards or [None] * len(table_names)
+        self._wrap_columns = wrap_columns
         self._emb_module = emb_module
         self._table_names = list(table_names)
         self._key_prefix = key_prefix
@@ -366,10 +474,25 @@ class EmbeddingFusedOptimizer:
     def _refresh(self) -> None:
         """(Re)reads the weight / state views: split_* write the row cache back and empty it first."""
         m, pre = self._emb_module, self._key_prefix
-        self._params = {f"{pre}{n}.weight": w for n, w in zip(self._table_names, m.split_embedding_weights())}
-        self._state = {f"{pre}{n}.weight": {f"{n}.momentum{i + 1}": s for i, s in enumerate(st)}
-                       for n, st in zip(self._table_names, m.split_optimizer_states())}
-        self.param_groups[0]["params"] = list(self._params.values())
+        weights, states = m.split_embedding_weights(), m.split_optimizer_states()
+        self._params, self._state = {}, {}
+        cw: Dict[str, List[int]] = {}
+        for i, (n, w, st) in enumerate(zip(self._table_names, weights, states)):
+            if self._column_shards[i] is not None:
+                cw.setdefault(n, []).append(i)
+                continue
+            self._params[f"{pre}{n}.weight"] = w
+            self._state[f"{pre}{n}.weight"] = {f"{n}.momentum{k + 1}": s for k, s in enumerate(st)}
+        for n, idx in cw.items():  # a column-wise table: the parameter is the list of this rank's piece views, column order
+            idx.sort(key=lambda i: self._column_shards[i][0])
+            _, n_shards, _, dim = self._column_shards[idx[0]]
+            self._params[f"{pre}{n}.weight"] = [weights[i] for i in idx]
+            self._state[f"{pre}{n}.weight"] = {
+                f"{n}.momentum{k + 1}": ColumnShardedState(
+                    [(self._column_shards[i][0], self._column_shards[i][2], states[i][k]) for i in idx], n_shards,
+                    weights[idx[0]].shape[0], dim)
+                for k in range(len(states[idx[0]]))}
+        self.param_groups[0]["params"] = list(weights)
 
     def _cached(self) -> bool:
         return getattr(self._emb_module, "_cache", None) is not None
@@ -396,8 +519,14 @@ class EmbeddingFusedOptimizer:
         self._save_param_groups = save
 
     def state_dict(self) -> Dict[str, Any]:
-        w = self._wrap
-        out: Dict[str, Any] = {"state": {k: {kk: (w(kk.rsplit(".", 1)[0], vv) if w is not None else vv) for kk, vv in v.items()}
+        w, wc = self._wrap, self._wrap_columns
+
+        def give(name, v):
+            if isinstance(v, ColumnShardedState):
+                return wc(name, v) if wc is not None else v.full()
+            return w(name, v) if w is not None else v
+
+        out: Dict[str, Any] = {"state": {k: {kk: give(kk.rsplit(".", 1)[0], vv) for kk, vv in v.items()}
                                          for k, v in self.state.items()}}
         if self._save_param_groups:
             out["param_groups"] = [{"params": sorted(self._params.keys()), "lr": self.param_groups[0]["lr"]}]
@@ -413,7 +542,10 @@ class EmbeddingFusedOptimizer:
                 if set(st.keys()) != set(mine[k].keys()):
                     raise ValueError(f"fused optimizer state of {k}: {sorted(mine[k].keys())} vs {sorted(st.keys())}")
                 for name, t in st.items():
-                    mine[k][name].copy_(unwrap_local(t))
+                    if isinstance(mine[k][name], ColumnShardedState):
+                        mine[k][name].load(t, f"fused optimizer state {name}")
+                    else:
+                        mine[k][name].copy_(unwrap_local(t))
         if "param_groups" in state_dict and state_dict["param_groups"]:
             self.param_groups[0]["lr"] = state_dict["param_groups"][0].get("lr", self.param_groups[0]["lr"])
             self._emb_module.set_learning_rate(self.param_groups[0]["lr"])
@@ -465,8 +597,9 @@ class ShardedEmbeddingBagCollection(nn.Module):
         self._lengths_per_embedding = g_dim
         self._D_total = sum(g_dim)
         # ---- who holds what --------------------------------------------------------------------
-        kind: List[int] = []  # per table: -1 row-wise, else owning rank
-        for c in cfgs:
+        kind: List[int] = []  # per table: -3 column-wise, -2 replicated, -1 row-wise, else owning rank
+        cw_shards: Dict[int, List[Tuple[int, int, int]]] = {}  # column-wise table -> [(first column, width, rank)]
+        for t, c in enumerate(cfgs):
             ps = table_name_to_parameter_sharding[c.name]
             if ps.sharding_type == ShardingType.DATA_PARALLEL.value:
                 kind.append(-2)
@@ -474,26 +607,61 @@ class ShardedEmbeddingBagCollection(nn.Module):
                 kind.append(-1)
             elif ps.sharding_type == ShardingType.TABLE_WISE.value:
                 kind.append(int(ps.ranks[0]))
+            elif ps.sharding_type in (ShardingType.COLUMN_WISE.value, ShardingType.TABLE_COLUMN_WISE.value):
+                # (one node, no host hierarchy: the two types are the same thing here)
+                kind.append(-3)
+                cw_shards[t] = _column_shards(c.name, c, ps, W)
+                if (ps.compute_kernel == "batched_fused_uvm_caching" and len({w for _, w, _ in cw_shards[t]}) > 1):
+                    raise NotImplementedError(
+                        f"table {c.name}: column shards of different widths {[w for _, w, _ in cw_shards[t]]} behind the HBM row "
+                        "cache (batched_fused_uvm_caching): the cache holds rows of ONE width; choose a min_partition that "
+                        "divides the embedding dim, or another compute kernel")
             else:
                 raise NotImplementedError(f"sharding type {ps.sharding_type} is outside the MI355X hot path "
-                                          "(table_wise / row_wise)")
+                                          "(table_wise / row_wise / column_wise / data_parallel)")
         self._table_kind = kind
-        # local feature list of every rank: row-wise features first (same columns on every rank)
-        rw_feats = [g for g in range(Fg) if kind[g_table[g]] == -1]
+        self._has_cw = bool(cw_shards)
+        if self._has_cw and rw_input_dist == "bucketize":
+            raise NotImplementedError(
+                "rw_input_dist='bucketize' with column-wise tables "
+                f"({[cfgs[t].name for t in cw_shards]}): the bucketized input dist is not built for column shards; use "
+                "'windows' (or 'auto', which does) for such collections")
+        # ---- pieces: the unit of everything below.  A piece is (feature, column shard); tables that are not column-wise
+        #      have ONE piece per feature, so piece number == feature number for them and every list is what it was -------
+        p_feat: List[int] = []   # feature of the piece
+        p_col: List[int] = []    # first column of the piece inside its feature
+        p_dim: List[int] = []    # width
+        p_kind: List[int] = []   # -2 replicated, -1 row-wise, else owning rank
+        p_shard: List[int] = []  # column shard number (0 for whole-width pieces)
+        for g in range(Fg):
+            t = g_table[g]
+            for i, (c0, w, r) in enumerate(cw_shards[t] if kind[t] == -3 else [(0, g_dim[g], kind[t])]):
+                p_feat.append(g)
+                p_col.append(c0)
+                p_dim.append(w)
+                p_kind.append(r)
+                p_shard.append(i)
+        P = len(p_feat)
+        self._piece_feat, self._piece_dim = p_feat, p_dim
+        # local piece list of every rank: row-wise features first (same columns on every rank).  The ids of a feature
+        # travel to every rank that holds one of its pieces — twice to a rank that holds two (the reference duplicates the
+        # feature per shard too: sharding/cw_sharding.py _id_list_features_per_rank)
+        rw_feats = [p for p in range(P) if p_kind[p] == -1]
         self._dp_feats = [g for g in range(Fg) if kind[g_table[g]] == -2]
         self._sharded_feats = [g for g in range(Fg) if kind[g_table[g]] != -2]
-        local_feats = [rw_feats + [g for g in range(Fg) if kind[g_table[g]] == r] for r in range(W)]
+        local_feats = [rw_feats + [p for p in range(P) if p_kind[p] == r] for r in range(W)]
         self._local_feats = local_feats
-        self._D_local_per_rank = [sum(g_dim[g] for g in lf) for lf in local_feats]
+        self._D_local_per_rank = [sum(p_dim[p] for p in lf) for lf in local_feats]
         self._D_local = self._D_local_per_rank[me]
         self._F_local = len(local_feats[me])
-        self._send_feature_order = [g for lf in local_feats for g in lf]
+        self._send_feature_order = [p_feat[p] for lf in local_feats for p in lf]
         self._send_feats_per_rank = [len(lf) for lf in local_feats]
         # bucketized row-wise input dist: row-wise features (bucketized, one block per destination) and the table-wise
         # features in destination order travel as separate pieces of one exchange
+        rw_feats = [p_feat[p] for p in rw_feats]
         self._rw_feats = rw_feats
-        self._tw_send_order = [g for r in range(W) for g in local_feats[r] if kind[g_table[g]] != -1]
-        self._tw_per_rank = [sum(1 for g in local_feats[r] if kind[g_table[g]] != -1) for r in range(W)]
+        self._tw_send_order = [p_feat[p] for r in range(W) for p in local_feats[r] if p_kind[p] != -1]
+        self._tw_per_rank = [sum(1 for p in local_feats[r] if p_kind[p] != -1) for r in range(W)]
         self._rw_block_sizes = torch.tensor([rw_block_size(cfgs[g_table[g]].num_embeddings, W) for g in rw_feats],
                                             dtype=torch.int64, device=self._device if self._device.type != "meta" else "cpu")
         self._rw_mean = any(pooling_type_to_pooling_mode(cfgs[g_table[g]].pooling) == 1 for g in rw_feats)
@@ -501,28 +669,32 @@ class ShardedEmbeddingBagCollection(nn.Module):
             raise NotImplementedError(
                 "rw_input_dist='bucketize' with MEAN-pooled row-wise tables: a rank would divide its partial sum by the number "
                 "of ids in ITS row block, not by the bag length; use 'windows' (or 'auto', which does) for such collections")
-        # exchange descriptors (batch-independent part)
-        feat_src, feat_slab_col = [0] * Fg, [0] * Fg
+        # exchange descriptors (batch-independent part), one entry per piece: the kernels (csrc/pooled_exchange.hip) copy
+        # column ranges and do not care whether a range is a whole feature
+        feat_src, feat_slab_col = [0] * P, [0] * P
         for r in range(W):
             col = 0
-            for g in local_feats[r]:
-                if kind[g_table[g]] == -1:
-                    feat_src[g], feat_slab_col[g] = -1, col
-                elif kind[g_table[g]] == r:
-                    feat_src[g], feat_slab_col[g] = r, col
-                col += g_dim[g]
-        for g in self._dp_feats:
-            feat_src[g] = -2
+            for p in local_feats[r]:
+                if p_kind[p] == -1:
+                    feat_src[p], feat_slab_col[p] = -1, col
+                elif p_kind[p] == r:
+                    feat_src[p], feat_slab_col[p] = r, col
+                col += p_dim[p]
+        for p in range(P):
+            if p_kind[p] == -2:
+                feat_src[p] = -2
         out_col = [0]
         for d in g_dim:
             out_col.append(out_col[-1] + d)
         self._out_col = out_col
+        # the pieces of a feature are consecutive in the output matrix: out_col(piece) = out_col(feature) + first column
+        piece_out_col = [out_col[p_feat[p]] + p_col[p] for p in range(P)]
         dev = self._device
-        self._feat_out_col = torch.tensor(out_col, dtype=torch.int32, device=dev)
+        self._feat_out_col = torch.tensor(piece_out_col + [self._D_total], dtype=torch.int32, device=dev)
         self._feat_src = torch.tensor(feat_src, dtype=torch.int32, device=dev)
         self._feat_slab_col = torch.tensor(feat_slab_col, dtype=torch.int32, device=dev)
         self._slab_stride = torch.tensor(self._D_local_per_rank, dtype=torch.int32, device=dev)
-        self._vec_ok = all(d % 4 == 0 for d in g_dim)
+        self._vec_ok = all(d % 4 == 0 for d in p_dim)
         self._layout_cache: Dict[int, Dict[str, Any]] = {}
         # state_dict() / fused-optimizer state as torch ShardedTensors whenever a process group exists (the reference's
         # behaviour); False hands out the plain local shards
@@ -535,21 +707,24 @@ class ShardedEmbeddingBagCollection(nn.Module):
         self._weights_epoch = 0  # bumped by everything that rewrites tables outside a train step (see ExplicitLookupStep.epoch)
         # ---- local tables + TBE ----------------------------------------------------------------
         self._local_tables: List[_LocalTable] = []
-        local_table_index: Dict[int, int] = {}
-        for g in local_feats[me]:
-            t = g_table[g]
-            if t in local_table_index:
+        local_table_index: Dict[Tuple[int, int], int] = {}  # (table, column shard) -> local TBE table
+        for p in local_feats[me]:
+            t = g_table[p_feat[p]]
+            if (t, p_shard[p]) in local_table_index:
                 continue
             c = cfgs[t]
+            ck = table_name_to_parameter_sharding[c.name].compute_kernel
             if kind[t] == -1:
                 rows = rw_shard_rows(c.num_embeddings, W)[me]
-                self._local_tables.append(_LocalTable(c, rows, me * rw_block_size(c.num_embeddings, W), True,
-                                                      table_name_to_parameter_sharding[c.name].compute_kernel))
+                self._local_tables.append(_LocalTable(c, rows, me * rw_block_size(c.num_embeddings, W), True, ck))
+            elif kind[t] == -3:  # each local column shard is its own TBE table [rows, width]
+                self._local_tables.append(_LocalTable(c, c.num_embeddings, 0, False, ck, p_col[p], p_dim[p],
+                                                      (p_shard[p], len(cw_shards[t]))))
             else:
-                self._local_tables.append(_LocalTable(c, c.num_embeddings, 0, False,
-                                                      table_name_to_parameter_sharding[c.name].compute_kernel))
-            local_table_index[t] = len(self._local_tables) - 1
-        ftm_local = [local_table_index[g_table[g]] for g in local_feats[me]]
+                self._local_tables.append(_LocalTable(c, c.num_embeddings, 0, False, ck))
+            local_table_index[(t, p_shard[p])] = len(self._local_tables) - 1
+        self._cw_shards = {cfgs[t].name: sh for t, sh in cw_shards.items()}
+        ftm_local = [local_table_index[(g_table[p_feat[p]], p_shard[p])] for p in local_feats[me]]
         # row-wise shards see un-bucketized GLOBAL ids: (first global row, global rows) per local feature
         win_first = [self._local_tables[i].row_offset for i in ftm_local]
         win_global = [self._local_tables[i].cfg.num_embeddings for i in ftm_local]
@@ -567,7 +742,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
         self._rw_mode_active = "windows"
         if self._local_tables:
             self._emb_module = factory(
-                [(max(lt.local_rows, 0), lt.cfg.embedding_dim, lt.compute_kernel) for lt in self._local_tables],
+                [(max(lt.local_rows, 0), lt.cols, lt.compute_kernel) for lt in self._local_tables],
                 ftm_local * W, pooling_type_to_pooling_mode(self._local_tables[ftm_local[0]].cfg.pooling), dev, fused_params)
             if self._exchange:
                 self._emb_module.set_a2a_output_layout(W)
@@ -580,11 +755,14 @@ class ShardedEmbeddingBagCollection(nn.Module):
                 self._emb_module.set_feature_pooling(local_pooling * W)
             self._init_parameters()
             self._optim = EmbeddingFusedOptimizer(self._emb_module, [lt.cfg.name for lt in self._local_tables],
-                                                  key_prefix="embedding_bags.", wrap=self._wrap)
+                                                  key_prefix="embedding_bags.", wrap=self._wrap,
+                                                  column_shards=[lt.column_shard and lt.column_shard + (lt.col_offset, lt.cfg.embedding_dim)
+                                                                 for lt in self._local_tables],
+                                                  wrap_columns=self._wrap_columns)
         else:
             self._optim = None
         # global-column addressing of the sharded features for the world_size == 1 "write into one buffer" path
-        self._sharded_out_off = torch.tensor([out_col[g] for g in local_feats[me]], dtype=torch.int64, device=dev)
+        self._sharded_out_off = torch.tensor([piece_out_col[p] for p in local_feats[me]], dtype=torch.int64, device=dev)
         # ---- data-parallel (replicated) tables -------------------------------------------------------
         self._dp_module = None
         self._dp_table_ids: List[int] = []
@@ -682,12 +860,12 @@ class ShardedEmbeddingBagCollection(nn.Module):
         self._weights_epoch += 1
         gen = torch.Generator(device=self._device)
         index = {c.name: t for t, c in enumerate(self._embedding_bag_configs)}
-        targets = [(n, w, r0) for n, (w, r0) in self.local_shards().items()] + [(n, w, 0) for n, w in self.dp_tables().items()]
+        targets = self.local_shard_pieces() + [(n, w, 0, 0) for n, w in self.dp_tables().items()]
         with torch.no_grad():
-            for name, w, row0 in targets:
+            for name, w, row0, col0 in targets:
                 cfg = self._embedding_bag_configs[index[name]]
                 lo, hi = cfg.get_weight_init_min(), cfg.get_weight_init_max()
-                n, D = w.shape
+                n, D = w.shape[0], cfg.embedding_dim  # blocks are drawn at the table's full width; a piece copies its columns
                 c = row0 // chunk_rows
                 while c * chunk_rows < row0 + n:
                     g0 = c * chunk_rows
@@ -695,7 +873,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
                     gen.manual_seed((int(seed) * 1000003 + index[name]) * 1000003 + c)
                     block = torch.rand((rows, D), generator=gen, device=self._device, dtype=torch.float32)
                     a, b = max(g0, row0), min(g0 + rows, row0 + n)
-                    w[a - row0:b - row0].copy_(block[a - g0:b - g0].mul_(hi - lo).add_(lo))
+                    w[a - row0:b - row0].copy_(block[a - g0:b - g0, col0:col0 + w.shape[1]].mul_(hi - lo).add_(lo))
                     c += 1
 
     @property
@@ -707,11 +885,47 @@ class ShardedEmbeddingBagCollection(nn.Module):
         return self._embedding_bag_configs
 
     def local_shards(self) -> Dict[str, Tuple[torch.Tensor, int]]:
-        """table name -> (local weight shard [rows_local, D], first global row of the shard)."""
+        """table name -> (local weight shard [rows_local, D], first global row of the shard), for the full-width local
+        shards (table-wise / row-wise tables); column-wise tables are in local_shard_pieces()."""
         if self._emb_module is None:
             return {}
         return {lt.cfg.name: (w, lt.row_offset)
-                for lt, w in zip(self._local_tables, self._emb_module.split_embedding_weights())}
+                for lt, w in zip(self._local_tables, self._emb_module.split_embedding_weights()) if lt.column_shard is None}
+
+    def local_shard_pieces(self) -> List[Tuple[str, torch.Tensor, int, int]]:
+        """[(table name, weight view [rows_local, cols_local], first global row, first column)] of EVERY local sharded
+        table, in the fused lookup's table order: one entry per table-wise table / row-wise block / column shard held."""
+        if self._emb_module is None:
+            return []
+        return [(lt.cfg.name, w, lt.row_offset, lt.col_offset)
+                for lt, w in zip(self._local_tables, self._emb_module.split_embedding_weights())]
+
+    def _column_pieces(self) -> Dict[str, List[Tuple[int, int, torch.Tensor]]]:
+        """column-wise table -> [(shard number, first column, weight view)] held by this rank, in column order."""
+        out: Dict[str, List[Tuple[int, int, torch.Tensor]]] = {}
+        if self._emb_module is not None:
+            for lt, w in zip(self._local_tables, self._emb_module.split_embedding_weights()):
+                if lt.column_shard is not None:
+                    out.setdefault(lt.cfg.name, []).append((lt.column_shard[0], lt.col_offset, w))
+        for v in out.values():
+            v.sort(key=lambda x: x[0])
+        return out
+
+    def _wrap_columns(self, name: str, pieces):
+        """state_dict value of a column-wise table's weight (`pieces` = [(shard number, first column, view)]) or fused
+        optimizer state (a ColumnShardedState): ONE ShardedTensor of the global size over this rank's pieces when a process
+        group exists, else a tensor of the global size assembled from them — a COPY (the pieces are separate tables of the
+        lookup; columns other ranks hold are zero)."""
+        t = next(i for i, c in enumerate(self._embedding_bag_configs) if c.name == name)
+        cfg, shards = self._embedding_bag_configs[t], self._cw_shards[name]
+        if not isinstance(pieces, ColumnShardedState):
+            pieces = ColumnShardedState(pieces, len(shards), cfg.num_embeddings, cfg.embedding_dim)
+        if not self.sharded_tensor_state or self._pg is None:
+            return pieces.full()
+        rows = cfg.num_embeddings
+        meta = [(([i * rows], [rows], r) if pieces.per_row else ([0, c], [rows, w], r)) for i, (c, w, r) in enumerate(shards)]
+        return wrap_sharded_pieces([(i, v) for i, _, v in pieces.pieces], pieces.global_size(), meta, self._pg, self._rank,
+                                   self._device)
 
     def _table_shards(self, name: str, cols: Optional[int] = None) -> Tuple[List[int], List[Tuple[List[int], List[int], int]]]:
         """(global size, [(offsets, sizes, rank)]) of a sharded table's weight (cols = D) or row-wise state (cols None)."""
@@ -737,11 +951,17 @@ class ShardedEmbeddingBagCollection(nn.Module):
     def state_dict(self, destination=None, prefix: str = "", keep_vars: bool = False):
         """`embedding_bags.<table>.weight` for EVERY table this rank holds (embeddingbag.py:405-416): the local
         shard [rows_local, D] of a sharded table, the whole [rows, D] of a replicated one.  The tensors alias
-        the modules' storage (host views, cache written back, for MANAGED_CACHING tables)."""
+        the modules' storage (host views, cache written back, for MANAGED_CACHING tables) — except a column-wise table's
+        without a process group, which is a copy assembled from the column shards."""
         destination = {} if destination is None else destination
         for name, (w, _) in self.local_shards().items():
             # with a process group the value is a ShardedTensor over the shard, as the reference's (sharded_tensor_state)
             destination[f"{prefix}embedding_bags.{name}.weight"] = self._wrap(name, w if keep_vars else w.detach())
+        for name, pieces in self._column_pieces().items():
+            # a column-wise table: ONE ShardedTensor [rows, D] over this rank's column shards; without a process group a
+            # [rows, D] tensor assembled from them, which is a COPY — the only entry that does not alias storage
+            destination[f"{prefix}embedding_bags.{name}.weight"] = self._wrap_columns(
+                name, [(i, c, w if keep_vars else w.detach()) for i, c, w in pieces])
         for name, w in self.dp_tables().items():
             destination[f"{prefix}embedding_bags.{name}.weight"] = w if keep_vars else w.detach()
         return destination
@@ -770,6 +990,20 @@ class ShardedEmbeddingBagCollection(nn.Module):
                 continue
             with torch.no_grad():
                 w.copy_(src)
+        for name, pieces in self._column_pieces().items():
+            # a column-wise table: a ShardedTensor over exactly this rank's column shards, or the WHOLE [rows, D] table,
+            # which is cut at every piece's first column (as rows are cut above)
+            key = f"{prefix}embedding_bags.{name}.weight"
+            if key not in state_dict:
+                if strict:
+                    missing_keys.append(key)
+                continue
+            try:
+                with torch.no_grad():
+                    load_pieces([(w, [0, c]) for _, c, w in pieces], state_dict[key],
+                                [cfg[name].num_embeddings, cfg[name].embedding_dim], key)
+            except ValueError as e:
+                error_msgs.append(str(e))
         # the replicated tables' dense module is a registered child: nn.Module.load_state_dict will visit it after this
         # method; hand it its own (just restored) storage under the key it expects, so that strict loading of a
         # reference-shaped checkpoint (embedding_bags.<table>.weight only) does not report it missing
@@ -862,8 +1096,8 @@ class ShardedEmbeddingBagCollection(nn.Module):
     AUTO_WINDOWS_MAX_POOLING = 2  # "auto": host-known pooling factor <= this -> windows; longer / data-dependent -> bucketize
 
     def _pick_rw_mode(self, features: KeyedJaggedTensor) -> str:
-        if not self._rw_feats or self._rw_input_dist == "windows" or self._rw_mean:
-            return "windows"
+        if not self._rw_feats or self._rw_input_dist == "windows" or self._rw_mean or self._has_cw:
+            return "windows"  # (column-wise tables: the bucketized form is refused in the constructor, auto stays here)
         if self._rw_input_dist == "bucketize":
             return "bucketize"
         fixed = features.fixed_lengths()
@@ -1107,6 +1341,10 @@ class ShardedEmbeddingBagCollection(nn.Module):
         """Whether compute_explicit() can serve a batch of this (per-rank) size: a fused module and an output buffer of
         exactly that batch — the configuration of the HIP-graph train step (with or without the exchange)."""
         buf = self._output_buffer
+        if self._has_cw:
+            # column-wise tables: refused (and with it the half-batch exchange, the static graph exchange and the prefetched
+            # lookup, which all hang off the explicit step); callers fall back to compute_and_output_dist + autograd
+            return False
         return (self._emb_module is not None and buf is not None
                 and buf.numel() == batch_size * self._D_total and hasattr(self._emb_module, "lookup_no_autograd")
                 and (self._dp_module is None or hasattr(self._dp_module, "lookup_no_autograd")))
@@ -1127,6 +1365,8 @@ class ShardedEmbeddingBagCollection(nn.Module):
         One rank without exchange, replicated tables or row cache; SUM-pooled fp32 DEVICE tables of one dim; no per-sample
         weights; exactly one id per bag.  Everything is known on the host without a sync."""
         m = self._emb_module
+        if self._has_cw:  # a feature's row is spread over several tables of the lookup: the consumer cannot gather it
+            return False
         if (self._exchange or self._world_size != 1 or self._dp_module is not None or m is None
                 or not hasattr(m, "lookup_deferred") or self._is_weighted
                 or self._local_feats[self._rank] != list(range(len(self._feature_names)))):

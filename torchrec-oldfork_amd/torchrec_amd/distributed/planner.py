@@ -1,7 +1,7 @@
 """Sharding planner with an MI355X hardware model.
 
 Plays the role of EmbeddingShardingPlanner (torchrec/distributed/planner/planners.py:126-309)
-for the sharding types on this build's hot path (table-wise, row-wise).  The reference's
+for the sharding types on this build's hot path (table-wise, row-wise, data-parallel; column-wise on request).  The reference's
 perf constants are A100-era (planner/constants.py:14-73: HBM 32 GiB / 897 GB/s, intra-node
 600 GB/s); these are MI355X's (288 GB HBM3E, ~6.3 TB/s achievable, 7 xGMI links x ~153 GB/s,
 all-to-all uses every link at once).
@@ -22,7 +22,11 @@ MAXIMUM number of (feature, dim) units any rank owns.  Three levers, in this ord
   * host offload where even the row-wise shards do not fit (BASELINE config 4: > 2 TB of rows on a
     node with 8 x 288 GB): the largest tables go to pinned host memory behind the HBM row cache
     (compute kernel `batched_fused_uvm_caching`, embedding_types.py:57-76; HBM cost = caching_ratio x
-    shard) until the rest fits.
+    shard) until the rest fits;
+  * column-wise only on request (a table constrained to ["column_wise"] or ["table_column_wise"]): the table is cut into
+    column shards with the reference's geometry (planner/enumerators.py:314-330, block = min(min_partition or
+    MIN_CW_DIM, D), the last shard takes the residual) and every shard is placed like a table-wise table of its width.
+    The planner never chooses it on its own.
 """
 import os
 from dataclasses import dataclass
@@ -41,6 +45,7 @@ class ParameterConstraints:
     sharding_types: Optional[List[str]] = None
     compute_kernels: Optional[List[str]] = None
     caching_ratio: Optional[float] = None  # HBM cache size / table size for batched_fused_uvm_caching
+    min_partition: Optional[int] = None    # column-wise shard width (planner/types.py:254); None = MIN_CW_DIM
 
 
 @dataclass
@@ -69,6 +74,17 @@ def rw_shard_rows(rows: int, world_size: int) -> List[int]:
     return [max(0, min(blk, rows - r * blk)) for r in range(world_size)]
 
 
+MIN_CW_DIM = 32  # planner/constants.py:17
+
+
+def cw_shard_widths(dim: int, min_partition: Optional[int] = None) -> List[int]:
+    """Column-shard widths of a `dim`-wide table (planner/enumerators.py:314-330): blocks of min(min_partition or
+    MIN_CW_DIM, dim) columns, the last one widened by the residual, e.g. 100 -> [32, 32, 36]; 96 at 40 -> [40, 56]."""
+    block = min(min_partition if min_partition else MIN_CW_DIM, dim)
+    n, residual = divmod(dim, block)
+    return [block] * (n - 1) + [block + residual]
+
+
 class EmbeddingShardingPlanner:
     def __init__(self, topology: Topology, constraints: Optional[Dict[str, List[str]]] = None,
                  num_row_wise: Optional[int] = None, dp_max_rows: int = 2500) -> None:
@@ -90,22 +106,26 @@ class EmbeddingShardingPlanner:
         forced_rw = {n for n, c in st_of.items() if c == [ShardingType.ROW_WISE.value]}
         forced_tw = {n for n, c in st_of.items() if c == [ShardingType.TABLE_WISE.value]}
         forced_dp = {n for n, c in st_of.items() if c == [ShardingType.DATA_PARALLEL.value]}
+        forced_cw = {n: c[0] for n, c in st_of.items()
+                     if c in ([ShardingType.COLUMN_WISE.value], [ShardingType.TABLE_COLUMN_WISE.value])}
+        part_of = {n: c.min_partition for n, c in self.constraints.items() if isinstance(c, ParameterConstraints)}
         dp = set(forced_dp)
         # TORCHREC_AMD_FORCE_DP=1: rehearsal switch — replicate the tiny tables even on one rank, so that a
         # one-rank run executes the replicated-table path of an N > 1 plan
         if W > 1 or os.environ.get("TORCHREC_AMD_FORCE_DP", "0") == "1":
             for t in tables:
-                if t.num_embeddings <= self.dp_max_rows and t.name not in forced_rw and t.name not in forced_tw:
+                if (t.num_embeddings <= self.dp_max_rows and t.name not in forced_rw and t.name not in forced_tw
+                        and t.name not in forced_cw):
                     dp.add(t.name)
         n_rw = self.num_row_wise if self.num_row_wise is not None else 0
         rw = set(forced_rw)
         for t in by_size:
-            if W > 1 and size[t.name] > cap and t.name not in dp:
+            if W > 1 and size[t.name] > cap and t.name not in dp and t.name not in forced_cw:
                 rw.add(t.name)  # does not fit one GPU
         for t in by_size:
             if len(rw) >= max(n_rw, len(forced_rw)) or W == 1:
                 break
-            if t.name not in forced_tw and t.name not in dp:
+            if t.name not in forced_tw and t.name not in dp and t.name not in forced_cw:
                 rw.add(t.name)
         # compute kernel per table: forced by a constraint, else fused-in-HBM; when the row-wise shards alone
         # exceed a rank's HBM budget the largest row-wise tables move to host memory behind the row cache
@@ -150,6 +170,21 @@ class EmbeddingShardingPlanner:
                     spec.append(ShardMetadata([off, 0], [rows[r], t.embedding_dim], f"rank:{r}/cuda:{r}"))
                     off += rows[r]
                 out[t.name] = ParameterSharding(ShardingType.ROW_WISE.value, kernel_of[t.name], list(range(W)), spec)
+                continue
+            if t.name in forced_cw:
+                # every column shard is placed like a table-wise table of its width, in shard order
+                ranks, spec, col = [], [], 0
+                for w in cw_shard_widths(t.embedding_dim, part_of.get(t.name)):
+                    need = hbm_bytes(t, t.num_embeddings * w * data_type_to_bits(t.data_type) // 8)
+                    r = next((r for r in sorted(range(W), key=lambda r: (units[r], mem[r], r)) if mem[r] + need <= cap), None)
+                    if r is None:
+                        raise RuntimeError(f"planner: a {w}-wide column shard of table {t.name} does not fit any rank")
+                    units[r] += float(t.num_features() * w)
+                    mem[r] += need
+                    ranks.append(r)
+                    spec.append(ShardMetadata([0, col], [t.num_embeddings, w], f"rank:{r}/cuda:{r}"))
+                    col += w
+                out[t.name] = ParameterSharding(forced_cw[t.name], kernel_of[t.name], ranks, spec)
                 continue
             cost = float(t.num_features() * t.embedding_dim)
             order = sorted(range(W), key=lambda r: (units[r], mem[r], r))
