@@ -55,6 +55,11 @@ extern "C" {
 #define TBE_OPT_EXACT_ROWWISE_ADAGRAD 1
 #define TBE_OPT_ADAM 2
 #define TBE_OPT_EXACT_ADAGRAD 3
+/* the row-norm family: accepted by the tbe_backward_*_ex_* entries only (formulas there) */
+#define TBE_OPT_LAMB 4
+#define TBE_OPT_PARTIAL_ROWWISE_ADAM 5
+#define TBE_OPT_PARTIAL_ROWWISE_LAMB 6
+#define TBE_OPT_LARS_SGD 7
 #define TBE_OPT_DENSE_GRAD 100
 
 /* An id with this value is skipped silently by every lookup (no row, no bounds error): how the row cache hands
@@ -74,6 +79,16 @@ typedef struct tbe_optimizer_args {
   float beta2;
   int64_t iteration;     /* 1-based step count, used by ADAM bias correction */
 } tbe_optimizer_args;
+
+/* What tbe_optimizer_args (frozen: passed by value by every tbe_backward_* entry) has no room for; handed to the
+ * tbe_backward_*_ex_* entries as a pointer to HOST memory that is read during the call.  NULL = no clipping,
+ * momentum = eta = 0. */
+typedef struct tbe_optimizer_ext {
+  float momentum;            /* LARS_SGD: momentum of the velocity m1 */
+  float eta;                 /* LARS_SGD: trust coefficient */
+  float max_gradient;        /* gradient clipping bound, finite and >= 0 when gradient_clipping != 0 */
+  int32_t gradient_clipping; /* != 0: every element of grad_out is clamped to [-max_gradient, max_gradient] as loaded */
+} tbe_optimizer_ext;
 
 const char* tbe_last_error(void);
 int32_t tbe_abi_version(void); /* 3 */
@@ -169,8 +184,8 @@ int tbe_forward_nobag_f32(const uint64_t* feat_weights, const int64_t* feat_rows
  *                    largest global row number.
  * feat_state0/1 [F]  base addresses of optimizer state of the feature's table
  *                    (rowwise Adagrad: float[rows] momentum1; ADAM: float[rows*D] m, v;
- *                    DENSE_GRAD: state0 = float[rows*D] dense gradient table). May be NULL
- *                    for SGD.
+ *                    DENSE_GRAD: state0 = float[rows*D] dense gradient table; the row-norm family:
+ *                    see tbe_backward_*_ex_*). May be NULL for SGD.
  * grad_out: same addressing as the forward output (feat_out_offset, grad_row_stride) when pooled,
  *           or [N, D] rows (grad_row_stride = D) for pooling_mode NONE.
  * flags: TBE_FLAG_UNIFORM_ALIGNED = the host asserts that every feature has dim == max_D
@@ -331,6 +346,85 @@ int tbe_backward_apply_f16w(const uint64_t* feat_weights, const int32_t* feat_D,
                             int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
                             int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags,
                             void* workspace, size_t workspace_bytes, int32_t rounding, uint64_t seed, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The fused backward with the optimizers that need row norms, and with gradient clipping: the rest of
+ * fbgemm_gpu.split_embedding_configs.EmbOptimType that the reference hands through fused_params unchanged
+ * (torchrec/distributed/batched_embedding_kernel.py:604-665) and whose states it exposes as <table>.momentum1/2
+ * (:133-249; the 1-D state of the PARTIAL_ROWWISE pair on its own at :215-227).  Each entry takes its twin's arguments
+ * plus `ext` (host memory, may be NULL) before `stream`; with ext == NULL and an optimizer code of the twin it launches
+ * the twin's kernels and the results are bit-identical.  The twins themselves keep answering TBE_ERR_UNSUPPORTED
+ * ("unknown optimizer") for the codes 4-7.
+ *
+ * g = the coalesced ("exact") row gradient, w = the current row (float(w16) for FP16 tables), D = the row's dim,
+ * t = opt.iteration >= 1, |.| = the Euclidean norm over the row's D columns.  FP32 arithmetic; the row is stored as by
+ * the twins (nearest-even / stochastic rounding for FP16 tables).  Every optimizer reads and writes a touched row and
+ * its state exactly once.
+ *   TBE_OPT_LAMB (state0 = m1 float[rows*D], state1 = m2 float[rows*D]):
+ *     m1 = beta1 m1 + (1-beta1) g;  m2 = beta2 m2 + (1-beta2) g^2;  u = m1 / (sqrt(m2) + eps) + weight_decay w
+ *     r = |w| / |u| if both norms are > 0, else 1;  w -= learning_rate r u                  (no bias correction)
+ *   TBE_OPT_PARTIAL_ROWWISE_ADAM (state0 = m1 float[rows*D], state1 = v float[rows]):
+ *     m1 as above;  v = beta2 v + (1-beta2) mean_d(g^2)
+ *     w -= learning_rate ((m1 / (1-beta1^t)) / (sqrt(v / (1-beta2^t)) + eps) + weight_decay w)
+ *   TBE_OPT_PARTIAL_ROWWISE_LAMB (states as PARTIAL_ROWWISE_ADAM):
+ *     m1, v as there;  u = m1 / (sqrt(v) + eps) + weight_decay w;  r as LAMB;  w -= learning_rate r u
+ *   TBE_OPT_LARS_SGD (state0 = m1 float[rows*D]):
+ *     alr = learning_rate eta |w| / (|g| + weight_decay |w|) if |w| > 0 and |g| > 0, else learning_rate
+ *     m1 = momentum m1 + alr (g + weight_decay w);  w -= m1
+ *   gradient clipping (any optimizer, TBE_OPT_DENSE_GRAD included): every element of grad_out is clamped to
+ *     [-max_gradient, max_gradient] where it is loaded, i.e. before the per-sample weight and the MEAN division.
+ * The forms follow fbgemm's code generator, which is absent from the reference tree (third_party/fbgemm is an empty
+ * submodule): parity with fbgemm is UNPINNED, as for row-wise Adagrad and Adam.  Deliberate difference: the two
+ * "> 0" guards (fbgemm's unguarded quotients give inf * 0 = NaN on a touched row whose gradient is zero).
+ * Norms are summed per lane in column order, then across the lanes of the row's group in a fixed butterfly: no atomics,
+ * two runs are bit-identical.
+ * Errors, before anything is launched: TBE_ERR_INVALID_ARGUMENT for a missing state (LAMB and the PARTIAL_ROWWISE pair
+ * need feat_state0 and feat_state1, LARS_SGD feat_state0), PARTIAL_ROWWISE_ADAM with opt.iteration < 1, clipping with a
+ * max_gradient that is negative or not finite; TBE_ERR_UNSUPPORTED for an unknown optimizer code.
+ * ---------------------------------------------------------------------------------- */
+/* batched_embedding_kernel.py:604-665 (BatchedFusedEmbeddingBag with fused_params optimizer / gradient_clipping) */
+int tbe_backward_fused_ex_f32(const uint64_t* feat_weights, const int32_t* feat_D,
+                              const int64_t* feat_out_offset, const int64_t* feat_rows,
+                              const int64_t* feat_row_base, const uint64_t* feat_state0,
+                              const uint64_t* feat_state1, int32_t F, int32_t B,
+                              int32_t max_D, int32_t key_bits, const int64_t* indices, int64_t N,
+                              const int64_t* offsets, const float* per_sample_weights,
+                              int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+                              int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags,
+                              void* workspace, size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window,
+                              const tbe_optimizer_ext* ext, void* stream);
+/* the same call site, apply phase after tbe_backward_prepare (side-stream sort) */
+int tbe_backward_apply_ex_f32(const uint64_t* feat_weights, const int32_t* feat_D,
+                              const int64_t* feat_out_offset, const int64_t* feat_rows,
+                              const int64_t* feat_row_base, const uint64_t* feat_state0,
+                              const uint64_t* feat_state1, int32_t F, int32_t B,
+                              int32_t max_D, int32_t key_bits, const int64_t* indices, int64_t N,
+                              const int64_t* offsets, const float* per_sample_weights,
+                              int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+                              int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags,
+                              void* workspace, size_t workspace_bytes, const tbe_optimizer_ext* ext, void* stream);
+/* batched_embedding_kernel.py:604-665 with weights_precision FP16 (:625-636) */
+int tbe_backward_fused_ex_f16w(const uint64_t* feat_weights, const int32_t* feat_D,
+                               const int64_t* feat_out_offset, const int64_t* feat_rows,
+                               const int64_t* feat_row_base, const uint64_t* feat_state0,
+                               const uint64_t* feat_state1, int32_t F, int32_t B,
+                               int32_t max_D, int32_t key_bits, const int64_t* indices, int64_t N,
+                               const int64_t* offsets, const float* per_sample_weights,
+                               int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+                               int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags,
+                               void* workspace, size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window,
+                               int32_t rounding, uint64_t seed, const tbe_optimizer_ext* ext, void* stream);
+/* the same call site with FP16 tables, apply phase after tbe_backward_prepare */
+int tbe_backward_apply_ex_f16w(const uint64_t* feat_weights, const int32_t* feat_D,
+                               const int64_t* feat_out_offset, const int64_t* feat_rows,
+                               const int64_t* feat_row_base, const uint64_t* feat_state0,
+                               const uint64_t* feat_state1, int32_t F, int32_t B,
+                               int32_t max_D, int32_t key_bits, const int64_t* indices, int64_t N,
+                               const int64_t* offsets, const float* per_sample_weights,
+                               int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+                               int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags,
+                               void* workspace, size_t workspace_bytes, int32_t rounding, uint64_t seed,
+                               const tbe_optimizer_ext* ext, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * HBM row cache for EmbeddingLocation.MANAGED_CACHING tables (the `batched_fused_uvm_caching`

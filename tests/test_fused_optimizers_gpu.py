@@ -1,0 +1,407 @@
+"""GPU: the row-norm optimizer family (LAMB, PARTIAL_ROWWISE_ADAM, PARTIAL_ROWWISE_LAMB, LARS_SGD) and gradient clipping
+of the fused TBE backward, through the fbgemm_gpu module, the C ABI and the sharded collection, against the float64
+restatement of tests/_fused_optim_ref.py.  Every run is two train steps, so that the optimizer state is read as well as
+written; weights and every state tensor are compared at rtol = atol = 2e-5 (tests/test_fused_optimizers.py shows that
+FP32 arithmetic meets that on the same inputs)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+import _paths  # noqa: F401
+import _fused_optim_ref as fo
+from _results import ResultStore
+from _util import to_dev
+
+pytestmark = pytest.mark.gpu
+
+
+def _opt(code):
+    from fbgemm_gpu.split_embedding_configs import EmbOptimType
+    return getattr(EmbOptimType, fo.OPT_NAMES[code])
+
+
+def build(c, code, weight_decay=0.0, fp16=False, **kw):
+    """The module for input set `c`, holding the set's initial weights."""
+    from fbgemm_gpu.split_embedding_configs import SparseType
+    from fbgemm_gpu.split_table_batched_embeddings_ops import (
+        ComputeDevice, EmbeddingLocation, PoolingMode, SplitTableBatchedEmbeddingBagsCodegen)
+
+    args = dict(fo.hyper(code, weight_decay))
+    args.update(kw)
+    if fp16:
+        args["weights_precision"] = SparseType.FP16
+    mod = SplitTableBatchedEmbeddingBagsCodegen(
+        [(r, d, EmbeddingLocation.DEVICE, ComputeDevice.CUDA) for r, d in zip(c.rows, c.dims)], feature_table_map=c.ftm,
+        pooling_mode=PoolingMode(c.pooling), device=torch.device("cuda", 0), optimizer=_opt(code), **args)
+    for w, init in zip(mod.split_embedding_weights(), c.weights):
+        w.copy_(torch.from_numpy(np.array(init)).to(w.dtype))
+    return mod
+
+
+def train(mod, c):
+    for indices, offsets, psw, grad in c.batches:
+        out = mod(to_dev(indices), to_dev(offsets), to_dev(psw))
+        out.backward(to_dev(grad))
+    torch.cuda.synchronize()
+    assert mod.bounds_check_errors() == 0
+    return mod
+
+
+def snapshot(mod):
+    return ([w.cpu().numpy().copy() for w in mod.split_embedding_weights()],
+            [[s.cpu().numpy().copy() for s in st] for st in mod.split_optimizer_states()])
+
+
+def assert_matches(mod, ref, w_tol=None):
+    weights, states = snapshot(mod)
+    kinds = [k for k in fo.STATE_KINDS[ref.code] if k is not None]
+    for t in range(len(ref.rows)):
+        if w_tol is None:
+            np.testing.assert_allclose(weights[t], ref.w[t], rtol=fo.RTOL, atol=fo.ATOL, err_msg=f"weights of table {t}")
+        else:
+            np.testing.assert_allclose(weights[t].astype(np.float64), ref.w[t], rtol=w_tol[0], atol=w_tol[1],
+                                       err_msg=f"weights of table {t}")
+        assert len(states[t]) == len(kinds)
+        for k, s in enumerate(states[t]):
+            assert s.dtype == np.float32
+            np.testing.assert_allclose(s, ref.state[k][t], rtol=fo.RTOL, atol=fo.ATOL, err_msg=f"momentum{k + 1} of table {t}")
+
+
+# ---- 3. what fails without the feature ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("code", fo.NORM_FAMILY, ids=[fo.OPT_NAMES[c] for c in fo.NORM_FAMILY])
+def test_the_new_optimizers_and_clipping_construct_and_train(code):
+    c = fo.case("a")
+    mod = build(c, code, gradient_clipping=True, max_gradient=0.5)
+    assert mod.optimizer_args.gradient_clipping is True and mod.optimizer_args.max_gradient == 0.5
+    indices, offsets, psw, grad = c.batches[0]
+    mod(to_dev(indices), to_dev(offsets)).backward(to_dev(grad))
+    torch.cuda.synchronize()
+    touched = np.zeros(c.rows[0], dtype=bool)
+    touched[indices[:offsets[c.B]]] = True
+    assert touched.any() and not touched.all()
+    w = mod.split_embedding_weights()[0].cpu().numpy()
+    changed = (w != c.weights[0]).any(axis=1)
+    np.testing.assert_array_equal(changed, touched)
+    assert np.isfinite(w).all()
+
+
+# ---- 4. each optimizer x each shape --------------------------------------------------------------------------------
+SHAPE_CONFIGS = [cfg for cfg in fo.GPU_CONFIGS if cfg[3] is None and cfg[0] != "guards"]
+
+
+@pytest.mark.parametrize("cfg", SHAPE_CONFIGS, ids=[f"{n}-{fo.OPT_NAMES[c]}-wd{wd}" for n, c, wd, _ in SHAPE_CONFIGS])
+def test_two_steps_match_the_restatement(cfg):
+    name, code, wd, _ = cfg
+    c = fo.case(name)
+    assert_matches(train(build(c, code, wd), c), fo.reference(name, code, wd))
+
+
+CALL_SITE_CONFIGS = [("a", fo.LAMB, 0.0, None), ("c", fo.PARTIAL_ROWWISE_ADAM, 0.01, 0.5), ("d", fo.LARS_SGD, 0.0, None)]
+assert all(cfg in fo.GPU_CONFIGS for cfg in CALL_SITE_CONFIGS)
+
+
+@pytest.mark.parametrize("name,code,wd,clip", CALL_SITE_CONFIGS, ids=[f"{n}-{fo.OPT_NAMES[c]}" for n, c, _, _ in CALL_SITE_CONFIGS])
+def test_every_backward_call_site_passes_the_extension(name, code, wd, clip):
+    """The autograd backward after a side-stream sort (prepare + apply, what `train` takes at these sizes), the fused call
+    (no overlap) and the explicit lookup_no_autograd / backward_no_autograd pair run the same kernels: bit-identical."""
+    c = fo.case(name)
+    kw = dict(gradient_clipping=True, max_gradient=clip) if clip is not None else {}
+    first = train(build(c, code, wd, **kw), c)
+    assert_matches(first, fo.reference(name, code, wd, clip))
+    two_phase = snapshot(first)
+    fused = build(c, code, wd, **kw)
+    fused.overlap_backward_sort = "0"
+    fused = snapshot(train(fused, c))
+    explicit = build(c, code, wd, **kw)
+    for indices, offsets, psw, grad in c.batches:
+        _, rec = explicit.lookup_no_autograd(to_dev(indices), to_dev(offsets), to_dev(psw))
+        explicit.backward_no_autograd(rec, to_dev(grad))
+    torch.cuda.synchronize()
+    explicit = snapshot(explicit)
+    flat = lambda s: s[0] + [x for st in s[1] for x in st]  # noqa: E731
+    for a, b, e in zip(flat(two_phase), flat(fused), flat(explicit)):
+        np.testing.assert_array_equal(a, b)
+        np.testing.assert_array_equal(a, e)
+
+
+# ---- 5. the trust-ratio guards ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("code", (fo.LAMB, fo.PARTIAL_ROWWISE_LAMB, fo.LARS_SGD), ids=lambda c: fo.OPT_NAMES[c])
+def test_zero_weight_rows_and_zero_gradient_rows_stay_finite(code):
+    c = fo.guard_case()
+    mod = train(build(c, code), c)
+    weights, states = snapshot(mod)
+    assert np.isfinite(weights[0]).all() and all(np.isfinite(s).all() for s in states[0])
+    np.testing.assert_array_equal(weights[0][1], c.weights[0][1])  # touched, |g| = 0 (|u| = 0): r = 1 / alr = lr, no move
+    assert_matches(mod, fo.reference("guards", code))
+
+
+# ---- 6. gradient clipping --------------------------------------------------------------------------------------------
+CLIP_CONFIGS = [cfg for cfg in fo.GPU_CONFIGS if cfg[3] is not None]
+
+
+@pytest.mark.parametrize("cfg", CLIP_CONFIGS, ids=[f"{n}-{fo.OPT_NAMES[c]}" for n, c, _, _ in CLIP_CONFIGS])
+def test_clipping_matches_the_restatement(cfg):
+    name, code, wd, mg = cfg
+    c = fo.case(name)
+    assert sum(float((np.abs(b[3]) > mg).mean()) for b in c.batches) / len(c.batches) > 0.5  # most elements clamp
+    mod = train(build(c, code, wd, gradient_clipping=True, max_gradient=mg), c)
+    assert_matches(mod, fo.reference(name, code, wd, mg))
+    unclipped = fo.reference(name, code, wd)
+    assert not np.allclose(mod.split_embedding_weights()[0].cpu().numpy(), unclipped.w[0], rtol=1e-3, atol=1e-3)
+
+
+@pytest.mark.parametrize("name,code", [("u128", fo.SGD), ("u128", fo.ROWWISE_ADAGRAD), ("a", fo.LAMB), ("c", fo.LARS_SGD)],
+                         ids=lambda v: fo.OPT_NAMES.get(v, v))
+def test_a_bound_nothing_reaches_is_bit_identical_to_no_clipping(name, code):
+    c = fo.case(name)
+    plain = snapshot(train(build(c, code), c))
+    wide = snapshot(train(build(c, code, gradient_clipping=True, max_gradient=1e30), c))
+    for a, b in zip(plain[0] + [s for st in plain[1] for s in st], wide[0] + [s for st in wide[1] for s in st]):
+        np.testing.assert_array_equal(a, b)
+
+
+def test_trained_per_sample_weights_with_clipping_raise_by_name():
+    c = fo.case("c")
+    mod = build(c, fo.LAMB, gradient_clipping=True, max_gradient=0.5)
+    indices, offsets, psw, _ = c.batches[0]
+    w = to_dev(psw).requires_grad_(True)
+    with pytest.raises(NotImplementedError, match="gradient_clipping.*per_sample_weights"):
+        mod(to_dev(indices), to_dev(offsets), w)
+    mod(to_dev(indices), to_dev(offsets), to_dev(psw))  # weights that are not trained are fine
+    build(c, fo.LAMB)(to_dev(indices), to_dev(offsets), w)  # and so are trained ones without clipping
+
+
+def test_constructor_refusals_of_the_new_ground():
+    from fbgemm_gpu.split_table_batched_embeddings_ops import WeightDecayMode
+
+    c = fo.case("a")
+    for code in fo.NORM_FAMILY:
+        with pytest.raises(NotImplementedError, match="weight_decay"):
+            build(c, code, 0.01, weight_decay_mode=WeightDecayMode.L2)
+        build(c, code, 0.0, weight_decay_mode=WeightDecayMode.L2)  # no decay: the mode says nothing
+    for bad in (-1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="max_gradient"):
+            build(c, fo.SGD, gradient_clipping=True, max_gradient=bad)
+
+
+# ---- 7. the _ex entry with ext = NULL is its twin --------------------------------------------------------------------
+def test_ex_entry_without_ext_is_bit_identical_to_its_twin():
+    from _bwd_abi import BackwardCase, Inputs, opt_args
+    from fbgemm_gpu import _lib
+
+    c = fo.case("a")
+    indices, offsets, psw, grad = c.batches[0]
+    inp = Inputs(indices=indices, offsets=offsets, psw=psw, grad=grad, N=int(indices.size), B=c.B, F=len(c.rows))
+    bc = BackwardCase(c.rows, c.dims, init={"weights": [w.copy() for w in c.weights], "state0": None, "state1": None})
+    opt = opt_args(fo.SGD, 0.05)
+    twin = bc.run(inp, opt)
+    lib, d, dev = _lib.load(), bc._device(), torch.device("cuda", 0)
+    d["buf"].copy_(d["host"])
+    nbytes = lib.tbe_backward_workspace_bytes(inp.N, bc.F, inp.B, bc.max_D, bc.key_bits)
+    ws = torch.full((nbytes + 256,), 0xFF, dtype=torch.uint8, device="cuda")
+    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+    bounds = torch.zeros(1, dtype=torch.int32, device="cuda")
+    p = _lib.ptr
+    i_dev, o_dev, _, g_dev = inp._dev
+    _lib.check(lib.tbe_backward_fused_ex_f32(
+        p(d["weights"]), p(d["feat_D"]), p(d["out_pooled"]), p(d["feat_rows"]), p(d["feat_row_base"]), None, None, bc.F,
+        inp.B, bc.max_D, bc.key_bits, p(i_dev), inp.N, p(o_dev), None, 0, None, p(g_dev), int(grad.shape[1]), opt, 0, ws_ptr,
+        nbytes, p(bounds), None, None, _lib.stream_ptr(dev)), "tbe_backward_fused_ex_f32")
+    torch.cuda.synchronize()
+    after = d["buf"].cpu().numpy()
+    assert twin.guards_ok and int(bounds.item()) == 0
+    for t in range(bc.T):
+        o, a = bc._slots[("weights", t)]
+        got = after[o:o + a.nbytes].view(a.dtype).reshape(a.shape)
+        np.testing.assert_array_equal(got, twin.weights[t])
+        assert (got != c.weights[t]).any()
+    assert (after[bc._gap] == 0xC3).all()
+
+
+# ---- 8. FP16 tables ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("code", (fo.LAMB, fo.PARTIAL_ROWWISE_ADAM), ids=lambda c: fo.OPT_NAMES[c])
+def test_fp16_tables_nearest_even(code):
+    """Stored halves against the restatement run on the up-cast table.  The restatement keeps FP64 rows between the two
+    steps where the module rounds to half after each, so the first step's rounding (2^-11 relative) is carried into the
+    second; the comparison is made after ONE step, where the bound of the stored half is one rounding (2^-11) plus a
+    possible move to the neighbouring half from an FP32 difference: rtol = 2^-10, atol = 2^-24.  States: FP32 tolerance."""
+    c = fo.case("a")
+    mod = build(c, code, fp16=True, stochastic_rounding=False)
+    ref = fo.Ref(c.rows, c.dims, c.ftm, [w.astype(np.float16).astype(np.float32) for w in c.weights], code, **fo.hyper(code))
+    for step, (indices, offsets, psw, grad) in enumerate(c.batches):
+        out = mod(to_dev(indices), to_dev(offsets), to_dev(psw))
+        out.backward(to_dev(grad))
+        torch.cuda.synchronize()
+        ref.step(indices, offsets, grad, psw, c.pooling)
+        assert mod.split_embedding_weights()[0].dtype == torch.float16
+        assert_matches(mod, ref, w_tol=(2.0 ** -10, 2.0 ** -24))
+        for t, w in enumerate(mod.split_embedding_weights()):  # the next step starts from what the table holds
+            ref.w[t][...] = w.cpu().numpy().astype(np.float64)
+
+
+@pytest.mark.parametrize("code", (fo.LAMB, fo.PARTIAL_ROWWISE_ADAM), ids=lambda c: fo.OPT_NAMES[c])
+def test_fp16_tables_stochastic_rounding_is_a_function_of_the_seed(code):
+    c = fo.case("a")
+    runs = []
+    for _ in range(2):
+        torch.manual_seed(1234)
+        runs.append(snapshot(train(build(c, code, fp16=True, stochastic_rounding=True), c)))
+    for a, b in zip(runs[0][0] + [s for st in runs[0][1] for s in st], runs[1][0] + [s for st in runs[1][1] for s in st]):
+        np.testing.assert_array_equal(a, b)
+    nearest = snapshot(train(build(c, code, fp16=True, stochastic_rounding=False), c))
+    assert any((a != b).any() for a, b in zip(runs[0][0], nearest[0]))
+
+
+# ---- 9. determinism ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("code", fo.NORM_FAMILY, ids=[fo.OPT_NAMES[c] for c in fo.NORM_FAMILY])
+def test_two_runs_are_bit_identical(code):
+    c = fo.case("b1024")
+    a, b = (snapshot(train(build(c, code, 0.01), c)) for _ in range(2))
+    for x, y in zip(a[0] + [s for st in a[1] for s in st], b[0] + [s for st in b[1] for s in st]):
+        np.testing.assert_array_equal(x, y)
+
+
+# ---- 10. the state surface -------------------------------------------------------------------------------------------
+def test_split_optimizer_states_shapes():
+    c = fo.case("a")
+    for code in fo.NORM_FAMILY:
+        mod = build(c, code)
+        for (r, d), st in zip(zip(c.rows, c.dims), mod.split_optimizer_states()):
+            want = [(r, d) if k == "elem" else (r,) for k in fo.STATE_KINDS[code] if k is not None]
+            assert [tuple(s.shape) for s in st] == want
+            assert all(s.dtype == torch.float32 and s.is_cuda for s in st)
+    assert build(c, fo.LARS_SGD).momentum2_dev.numel() == 0
+
+
+def _world1_collection(optimizer, sharding=None, rows=(40, 7), dims=(36, 8)):
+    from _cw_sharded import tables_and_plan
+    from torchrec_amd.distributed.embeddingbag import ShardedEmbeddingBagCollection
+    from torchrec_amd.distributed.types import ShardingEnv
+    from torchrec_amd.modules.embedding_modules import EmbeddingBagCollection
+
+    tables, plan = tables_and_plan(1, list(rows), list(dims), sharding or {}, "cuda")
+    ebc = EmbeddingBagCollection(tables, device=torch.device("meta"))
+    fused = dict(fo.hyper(fo.PARTIAL_ROWWISE_ADAM), optimizer=optimizer)
+    return ShardedEmbeddingBagCollection(ebc, plan, ShardingEnv.from_local(1, 0), fused, torch.device("cuda", 0))
+
+
+def _kjt_step(sebc, rng, rows, dims, B=6):
+    from torchrec_amd.sparse.jagged_tensor import KeyedJaggedTensor
+
+    lengths = rng.integers(0, 4, size=len(rows) * B).astype(np.int32)
+    vals = np.concatenate([rng.integers(0, rows[f], size=int(lengths[f * B:(f + 1) * B].sum())) for f in range(len(rows))])
+    kjt = KeyedJaggedTensor.from_lengths_sync([f"f{i}" for i in range(len(rows))], to_dev(vals.astype(np.int64)), to_dev(lengths))
+    grad = rng.standard_normal((B, sum(dims))).astype(np.float32)
+    sebc(kjt).wait().values().backward(to_dev(grad))
+    torch.cuda.synchronize()
+
+
+def test_sharded_collection_exposes_saves_and_restores_both_states():
+    rows, dims = (40, 7), (36, 8)
+    a = _world1_collection(_opt(fo.PARTIAL_ROWWISE_ADAM))
+    rng = np.random.default_rng(3)
+    _kjt_step(a, rng, rows, dims)
+    osd = a.fused_optimizer.state_dict()["state"]
+    assert sorted(osd) == ["embedding_bags.t0.weight", "embedding_bags.t1.weight"]
+    for t, (r, d) in enumerate(zip(rows, dims)):
+        st = osd[f"embedding_bags.t{t}.weight"]
+        assert sorted(st) == [f"t{t}.momentum1", f"t{t}.momentum2"]
+        assert tuple(st[f"t{t}.momentum1"].shape) == (r, d) and tuple(st[f"t{t}.momentum2"].shape) == (r,)
+        assert st[f"t{t}.momentum1"].abs().sum() > 0 and st[f"t{t}.momentum2"].abs().sum() > 0
+    b = _world1_collection(_opt(fo.PARTIAL_ROWWISE_ADAM))
+    b.load_state_dict(a.state_dict())
+    b.fused_optimizer.load_state_dict(a.fused_optimizer.state_dict())
+    b._emb_module.iter = a._emb_module.iter  # the step count of the bias correction is the module's, not a state tensor
+    seed = np.random.default_rng(4).bit_generator.state
+    for m in (a, b):
+        r2 = np.random.default_rng(0)
+        r2.bit_generator.state = seed
+        _kjt_step(m, r2, rows, dims)
+    for (_, wa, _, _), (_, wb, _, _) in zip(a.local_shard_pieces(), b.local_shard_pieces()):
+        assert torch.equal(wa, wb)
+    for sa, sb in zip(a._emb_module.split_optimizer_states(), b._emb_module.split_optimizer_states()):
+        assert len(sa) == 2 and all(torch.equal(x, y) for x, y in zip(sa, sb))
+
+
+def test_column_wise_table_with_a_row_norm_optimizer_raises_naming_the_table():
+    with pytest.raises(NotImplementedError, match=r"t0.*LAMB"):
+        _world1_collection(_opt(fo.LAMB), sharding={0: "column_wise"}, rows=(40, 7), dims=(64, 8))
+    _world1_collection(_opt(fo.SGD), sharding={0: "column_wise"}, rows=(40, 7), dims=(64, 8))  # an element-wise one is fine
+
+
+# ---- 11. two ranks on one GPU over gloo -------------------------------------------------------------------------------
+MR_ROWS, MR_DIMS, MR_B = [41, 30], [36, 8], 6  # t0 row-wise (21 + 20 rows), t1 table-wise
+MR_STEPS = 2
+
+
+def _mr_worker(rank, W, port, code, ret):
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=W)
+    try:
+        from _cw_sharded import data, load_init, tables_and_plan, train_step
+        from torchrec_amd.distributed._rehearsal import stage_all_to_all_through_host
+        from torchrec_amd.distributed.embeddingbag import ShardedEmbeddingBagCollection
+        from torchrec_amd.distributed.types import ShardingEnv
+        from torchrec_amd.modules.embedding_modules import EmbeddingBagCollection
+
+        stage_all_to_all_through_host()  # gloo has no device all-to-all
+        dev = torch.device("cuda", 0)
+        tables, plan = tables_and_plan(W, MR_ROWS, MR_DIMS, {0: "row_wise", 1: "table_wise"}, "cuda")
+        ebc = EmbeddingBagCollection(tables, device=torch.device("meta"))
+        fused = dict(fo.hyper(code, 0.01), optimizer=_opt(code))
+        sebc = ShardedEmbeddingBagCollection(ebc, plan, ShardingEnv.from_process_group(dist.group.WORLD), fused, dev)
+        for step in range(MR_STEPS):
+            per_rank, init = data(W, MR_B, MR_ROWS, MR_DIMS, 0, False, seed=31 + step)
+            if step == 0:
+                load_init(sebc, init)
+            train_step(sebc, per_rank, rank, W, 0, False, dev, None)
+        ret[rank] = [(lt.cfg.name, lt.row_offset, w.detach().cpu().numpy().copy(), [s.detach().cpu().numpy().copy() for s in st])
+                     for lt, w, st in zip(sebc._local_tables, sebc._emb_module.split_embedding_weights(),
+                                          sebc._emb_module.split_optimizer_states())]
+        ret[f"kinds{rank}"] = {n: p.sharding_type for n, p in plan.items()}
+        osd = sebc.fused_optimizer.state_dict()["state"]
+        ret[f"m2_{rank}"] = {k: list(v[k.split(".")[1] + ".momentum2"].size()) for k, v in osd.items()}
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("code", (fo.PARTIAL_ROWWISE_ADAM, fo.LAMB), ids=lambda c: fo.OPT_NAMES[c])
+def test_two_ranks_match_the_unsharded_module(code):
+    """Table-wise and row-wise shards hold whole rows: every local shard and its two states equal the matching rows of ONE
+    unsharded TBE trained on the global batch (gradient / world size, as the pooled exchange scales it)."""
+    from _cw_sharded import data, global_batch
+    from test_sharded_gloo import _free_port
+
+    W = 2
+    ret = ResultStore()
+    mp.spawn(_mr_worker, args=(W, _free_port(), code, ret), nprocs=W, join=True)
+    assert ret["kinds0"] == {"t0": "row_wise", "t1": "table_wise"}
+    _, init = data(W, MR_B, MR_ROWS, MR_DIMS, 0, False, seed=31)
+    c = fo.Case(rows=MR_ROWS, dims=MR_DIMS, ftm=None, pooling=fo.POOL_SUM, weights=init)
+    mod = build(c, code, 0.01)
+    for step in range(MR_STEPS):
+        per_rank, _ = data(W, MR_B, MR_ROWS, MR_DIMS, 0, False, seed=31 + step)
+        vals, offs, _, grad = global_batch(per_rank, W, MR_B, len(MR_ROWS), False)
+        mod(to_dev(vals), to_dev(offs)).backward(to_dev(grad))
+    torch.cuda.synchronize()
+    weights, states = snapshot(mod)
+    seen = [np.zeros(r, dtype=np.int32) for r in MR_ROWS]
+    for rank in range(W):
+        for name, row0, w, st in ret[rank]:
+            t, n = int(name[1:]), w.shape[0]
+            seen[t][row0:row0 + n] += 1
+            np.testing.assert_allclose(w, weights[t][row0:row0 + n], rtol=fo.RTOL, atol=fo.ATOL)
+            assert len(st) == 2 and st[0].shape == (n, MR_DIMS[t])
+            assert st[1].shape == ((n,) if code == fo.PARTIAL_ROWWISE_ADAM else (n, MR_DIMS[t]))
+            for k in range(2):
+                np.testing.assert_allclose(st[k], states[t][k][row0:row0 + n], rtol=fo.RTOL, atol=fo.ATOL)
+                assert np.abs(st[k]).sum() > 0
+        # the 1-D state of a row-wise table is a ShardedTensor over the table's rows (to_rowwise_sharded_metadata)
+        want_t0 = [MR_ROWS[0]] if code == fo.PARTIAL_ROWWISE_ADAM else [MR_ROWS[0], MR_DIMS[0]]
+        assert ret[f"m2_{rank}"]["embedding_bags.t0.weight"] == want_t0
+    assert all((s == 1).all() for s in seen)

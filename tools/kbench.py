@@ -1,6 +1,7 @@
 """Kernel-level timing of the TBE hot path at the Criteo-1TB shape (development tool;
 bench.py is the judged harness).
 Usage: python tools/kbench.py [--batch 65536[,4096]] [--cap ROWS] [--precision fp32|fp16] [--rounding stochastic|nearest] [--repeats N] [--json FILE]
+       python tools/kbench.py --opt LAMB|PARTIAL_ROWWISE_ADAM|PARTIAL_ROWWISE_LAMB|LARS_SGD|ADAM|... [--clip MAX_GRADIENT] ...
        python tools/kbench.py --indice-weights-grad [--pooling L] ...   the per-sample-weight gradient next to the weighted forward"""
 import argparse
 import json
@@ -27,7 +28,9 @@ def main():
     ap.add_argument("--cap", type=int, default=0, help="cap rows per table (0 = full 85 GiB in fp32)")
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--opt", default="EXACT_SGD")
+    ap.add_argument("--opt", default="EXACT_SGD", help="an EmbOptimType name, e.g. ADAM, LAMB, PARTIAL_ROWWISE_ADAM, LARS_SGD")
+    ap.add_argument("--clip", type=float, default=None, metavar="MAX_GRADIENT",
+                    help="gradient clipping with this bound (such a launch takes the generic update kernel)")
     ap.add_argument("--nbatches", type=int, default=8)
     ap.add_argument("--pooling", type=int, default=1, help="ids per bag (fixed pooling factor)")
     ap.add_argument("--precision", choices=["fp32", "fp16"], default="fp32", help="storage type of the tables")
@@ -47,7 +50,8 @@ def main():
     mod = SplitTableBatchedEmbeddingBagsCodegen(
         [(r, D, EmbeddingLocation.DEVICE, ComputeDevice.CUDA) for r in rows], device=dev,
         weights_precision=SparseType.FP16 if args.precision == "fp16" else SparseType.FP32,
-        stochastic_rounding=args.rounding == "stochastic", optimizer=getattr(EmbOptimType, args.opt), learning_rate=0.01)
+        stochastic_rounding=args.rounding == "stochastic", optimizer=getattr(EmbOptimType, args.opt), learning_rate=0.01,
+        gradient_clipping=args.clip is not None, max_gradient=args.clip if args.clip is not None else 1.0)
     for w, r in zip(mod.split_embedding_weights(), rows):
         w.uniform_(-(1.0 / r) ** 0.5, (1.0 / r) ** 0.5)
     torch.cuda.synchronize()
@@ -56,7 +60,7 @@ def main():
     for B in [int(b) for b in str(args.batch).split(",")]:
         for rep in range(args.repeats):
             rec = (measure_indice_weights_grad if args.indice_weights_grad else measure)(mod, rows, B, D, esz, args)
-            rec.update(batch=B, dim=D, pooling=args.pooling, opt=args.opt, precision=args.precision,
+            rec.update(batch=B, dim=D, pooling=args.pooling, opt=args.opt, clip=args.clip, cap=args.cap, precision=args.precision,
                        rounding=args.rounding if args.precision == "fp16" else None, repeat=rep)
             if args.json:
                 with open(args.json, "a") as f:
@@ -134,7 +138,11 @@ def measure(mod, rows, B, D, esz, args):
     N = F * B * L
     U = nrows.value / max(1, args.iters)
     fwd_kernel_bytes = N * (D * esz + 8) + F * B * (D * 4 + 8)
-    upd_kernel_bytes = N * (D * 4 + 8) + U * 2 * D * esz
+    # + the optimizer state of each distinct row, read and written once: float[D] per element-wise state, 4 B per row-wise
+    elem_states = {"ADAM": 2, "LAMB": 2, "EXACT_ADAGRAD": 1, "LARS_SGD": 1, "PARTIAL_ROWWISE_ADAM": 1, "PARTIAL_ROWWISE_LAMB": 1}
+    row_states = {"EXACT_ROWWISE_ADAGRAD": 1, "ROWWISE_ADAGRAD": 1, "PARTIAL_ROWWISE_ADAM": 1, "PARTIAL_ROWWISE_LAMB": 1}
+    state_bytes = U * 2 * 4 * (elem_states.get(args.opt, 0) * D + row_states.get(args.opt, 0))
+    upd_kernel_bytes = N * (D * 4 + 8) + U * 2 * D * esz + state_bytes
     rec = {"fwd_kernel_us": med[0], "bwd_update_kernel_us": med[1], "bwd_apply_us": med[2], "bwd_prepare_us": med[3],
            "distinct_rows_per_step": U, "fwd_kernel_bytes": fwd_kernel_bytes, "bwd_update_kernel_bytes": upd_kernel_bytes}
     if med[0]:

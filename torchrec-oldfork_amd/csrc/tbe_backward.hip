@@ -158,15 +158,17 @@ static int backward_entry(
     int32_t key_bits, const int64_t* indices, int64_t N, const int64_t* offsets,
     const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
     int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
-    size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window, void* stream, int phase) {
-  static const char* const kWho[4] = {"", "tbe_backward_prepare", "tbe_backward_apply_f32", "tbe_backward_fused_f32"};
+    size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window, void* stream, int phase,
+    bool ex = false, const tbe_optimizer_ext* ext = nullptr) {
+  static const char* const kWho[8] = {"", "tbe_backward_prepare", "tbe_backward_apply_f32", "tbe_backward_fused_f32",
+                                      "", "", "tbe_backward_apply_ex_f32", "tbe_backward_fused_ex_f32"};
   BwdArgs a;
   BwdWorkspace w;
   bool wide = false, done = false;
-  const int rc = bwd_setup(kWho[phase & 3], feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0,
+  const int rc = bwd_setup(kWho[(phase & 3) + (ex ? 4 : 0)], feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0,
                            feat_state1, F, B, max_D, key_bits, indices, N, offsets, per_sample_weights, pooling_mode,
                            feat_pooling, grad_out, grad_row_stride, opt, flags, workspace, workspace_bytes, bounds_errors,
-                           feat_window, phase, &a, &w, &wide, &done);
+                           feat_window, phase, &a, &w, &wide, &done, ex, ext);
   if (rc != TBE_OK || done) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (key_bits > 32)
@@ -210,6 +212,37 @@ extern "C" int tbe_backward_apply_f32(
   return backward_entry(feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F,
                         B, max_D, key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out,
                         grad_row_stride, opt, flags, workspace, workspace_bytes, nullptr, nullptr, stream, kPhaseApply);
+}
+
+// The twins that also take the row-norm optimizer family and gradient clipping (include/tbe_hip.h); with ext == NULL and
+// an optimizer of the twin they are the twin.
+extern "C" int tbe_backward_fused_ex_f32(
+    const uint64_t* feat_weights, const int32_t* feat_D, const int64_t* feat_out_offset,
+    const int64_t* feat_rows, const int64_t* feat_row_base, const uint64_t* feat_state0,
+    const uint64_t* feat_state1, int32_t F, int32_t B, int32_t max_D,
+    int32_t key_bits, const int64_t* indices, int64_t N, const int64_t* offsets,
+    const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+    int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
+    size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window, const tbe_optimizer_ext* ext,
+    void* stream) {
+  return backward_entry(feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F,
+                        B, max_D, key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out,
+                        grad_row_stride, opt, flags, workspace, workspace_bytes, bounds_errors, feat_window, stream,
+                        kPhasePrepare | kPhaseApply, true, ext);
+}
+
+extern "C" int tbe_backward_apply_ex_f32(
+    const uint64_t* feat_weights, const int32_t* feat_D, const int64_t* feat_out_offset,
+    const int64_t* feat_rows, const int64_t* feat_row_base, const uint64_t* feat_state0,
+    const uint64_t* feat_state1, int32_t F, int32_t B, int32_t max_D,
+    int32_t key_bits, const int64_t* indices, int64_t N, const int64_t* offsets,
+    const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+    int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
+    size_t workspace_bytes, const tbe_optimizer_ext* ext, void* stream) {
+  return backward_entry(feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F,
+                        B, max_D, key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out,
+                        grad_row_stride, opt, flags, workspace, workspace_bytes, nullptr, nullptr, stream, kPhaseApply,
+                        true, ext);
 }
 
 // ---- the pair sort as a public entry (tests, micro-benchmarks) ---------------------------------------

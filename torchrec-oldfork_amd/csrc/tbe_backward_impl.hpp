@@ -36,8 +36,11 @@ struct BwdArgs {
   int32_t key_bits;
   int32_t C;  // contributions per chunk
   tbe_optimizer_args opt;
-  float bias1;  // ADAM: 1 - beta1^t
-  float bias2;  // ADAM: 1 - beta2^t
+  float bias1;  // ADAM, PARTIAL_ROWWISE_ADAM: 1 - beta1^t
+  float bias2;  // ADAM, PARTIAL_ROWWISE_ADAM: 1 - beta2^t
+  float momentum;      // LARS_SGD (tbe_optimizer_ext)
+  float eta;           // LARS_SGD
+  float max_gradient;  // gradient clipping bound; < 0 = no clipping
   // workspace
   void* keys_sorted;
   const void* payload_sorted;  // uint32 bag numbers, or uint64 (bag << 32) | position
@@ -201,6 +204,136 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
+// OPTC of the row-norm family (LAMB, PARTIAL_ROWWISE_ADAM, PARTIAL_ROWWISE_LAMB, LARS_SGD; chosen at run time inside
+// it): its own instantiations, so that the generic ones (OPTC = -1) keep their register footprint.
+constexpr int kOptNormFamily = -2;
+__host__ __device__ __forceinline__ bool is_norm_family(int optimizer) {
+  return optimizer >= TBE_OPT_LAMB && optimizer <= TBE_OPT_LARS_SGD;
+}
+
+// x . x added to s in column order; columns beyond D must be zero in x.
+__device__ __forceinline__ float sumsq4(float4 x, float s) {
+  s = fmaf(x.x, x.x, s);
+  s = fmaf(x.y, x.y, s);
+  s = fmaf(x.z, x.z, s);
+  return fmaf(x.w, x.w, s);
+}
+// Zeroes the columns of x (columns [d, d+4)) that lie beyond D: values computed from zero-filled loads need not be zero.
+__device__ __forceinline__ float4 mask_tail(float4 x, int d, int D) {
+  if (d + 1 >= D) x.y = 0.f;
+  if (d + 2 >= D) x.z = 0.f;
+  if (d + 3 >= D) x.w = 0.f;
+  return x;
+}
+
+// The row-norm family (formulas: include/tbe_hip.h, tbe_backward_*_ex_*).  Two passes over register-resident data: the
+// first updates the element-wise state (loaded and stored once, never held), leaves the update direction u in g's
+// registers and sums the norms; the second writes the row.  Live across the norm: w and g only, as for ADAM.
+template <typename WT, int G, int NV>
+__device__ __forceinline__ void apply_row_norm(const BwdArgs& a, int f, int64_t local_row, int D, bool vec, int gl,
+                                               WT* wrow, float4 (&w)[NV], float4 (&g)[NV], const RowRounding& rr) {
+  const int optimizer = a.opt.optimizer;
+  const float lr = a.opt.learning_rate, wd = a.opt.weight_decay;
+  float* m1row = reinterpret_cast<float*>(a.feat_state0[f]) + local_row * D;
+  const bool m1vec = vec && ((reinterpret_cast<uintptr_t>(m1row) & 15) == 0);
+  // columns beyond D are zero in w and g (never loaded)
+  float ww = 0.f;
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+    if ((v * G + gl) * 4 < D) ww = sumsq4(w[v], ww);
+  if (optimizer == TBE_OPT_LARS_SGD) {
+    float gg = 0.f;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+      if ((v * G + gl) * 4 < D) gg = sumsq4(g[v], gg);
+    const float wn = sqrtf(group_sum<G>(ww)), gn = sqrtf(group_sum<G>(gg));
+    const float alr = (wn > 0.f && gn > 0.f) ? lr * a.eta * wn / (gn + wd * wn) : lr;
+    const float mom = a.momentum;
+#define TBE_LARS1(c)                                        \
+  m.c = fmaf(mom, m.c, alr * fmaf(wd, w[v].c, g[v].c));     \
+  r.c = w[v].c - m.c;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int d = (v * G + gl) * 4;
+      if (d < D) {
+        float4 m = ldc(m1row, d, D, m1vec);
+        float4 r;
+        TBE_LARS1(x) TBE_LARS1(y) TBE_LARS1(z) TBE_LARS1(w)
+        stc(m1row, d, D, m1vec, m);
+        stw(wrow, d, D, vec, r, rr);
+      }
+    }
+#undef TBE_LARS1
+    return;
+  }
+  const float b1 = a.opt.beta1, b2 = a.opt.beta2, eps = a.opt.eps;
+  const bool lamb = optimizer == TBE_OPT_LAMB;
+  const bool adam = optimizer == TBE_OPT_PARTIAL_ROWWISE_ADAM;
+  float den_row = 1.f;  // PARTIAL_ROWWISE_*: the row's denominator
+  float* m2row = nullptr;
+  bool m2vec = false;
+  if (lamb) {
+    m2row = reinterpret_cast<float*>(a.feat_state1[f]) + local_row * D;
+    m2vec = vec && ((reinterpret_cast<uintptr_t>(m2row) & 15) == 0);
+  } else {
+    float ss = 0.f;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+      if ((v * G + gl) * 4 < D) ss = sumsq4(g[v], ss);
+    ss = group_sum<G>(ss);
+    float* vp = reinterpret_cast<float*>(a.feat_state1[f]) + local_row;
+    const float v_new = fmaf(b2, *vp, (1.f - b2) * (ss / static_cast<float>(D)));
+    if (gl == 0) *vp = v_new;
+    den_row = adam ? sqrtf(v_new / a.bias2) + eps : sqrtf(v_new) + eps;
+  }
+  const float m1div = adam ? a.bias1 : 1.f;
+  float uu = 0.f;
+#define TBE_NORM_M1(c) m1.c = fmaf(b1, m1.c, (1.f - b1) * g[v].c);
+#define TBE_NORM_M2(c)                                   \
+  m2.c = fmaf(b2, m2.c, (1.f - b2) * g[v].c * g[v].c);   \
+  den.c = sqrtf(m2.c) + eps;
+#define TBE_NORM_U(c) u.c = (m1.c / m1div) / den.c + wd * w[v].c;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int d = (v * G + gl) * 4;
+    if (d < D) {
+      float4 m1 = ldc(m1row, d, D, m1vec);
+      TBE_NORM_M1(x) TBE_NORM_M1(y) TBE_NORM_M1(z) TBE_NORM_M1(w)
+      stc(m1row, d, D, m1vec, m1);
+      float4 den = make_float4(den_row, den_row, den_row, den_row);
+      if (lamb) {
+        float4 m2 = ldc(m2row, d, D, m2vec);
+        TBE_NORM_M2(x) TBE_NORM_M2(y) TBE_NORM_M2(z) TBE_NORM_M2(w)
+        stc(m2row, d, D, m2vec, m2);
+      }
+      float4 u;
+      TBE_NORM_U(x) TBE_NORM_U(y) TBE_NORM_U(z) TBE_NORM_U(w)
+      g[v] = mask_tail(u, d, D);
+      uu = sumsq4(g[v], uu);
+    }
+  }
+#undef TBE_NORM_M1
+#undef TBE_NORM_M2
+#undef TBE_NORM_U
+  float step = lr;
+  if (!adam) {  // the trust ratio |w| / |u|, 1 when either norm is zero
+    const float wn = sqrtf(group_sum<G>(ww)), un = sqrtf(group_sum<G>(uu));
+    if (wn > 0.f && un > 0.f) step = lr * (wn / un);
+  }
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int d = (v * G + gl) * 4;
+    if (d < D) {
+      float4 r;
+      r.x = fmaf(-step, g[v].x, w[v].x);
+      r.y = fmaf(-step, g[v].y, w[v].y);
+      r.z = fmaf(-step, g[v].z, w[v].z);
+      r.w = fmaf(-step, g[v].w, w[v].w);
+      stw(wrow, d, D, vec, r, rr);
+    }
+  }
+}
+
 // Applies the optimizer to one table row.  `g` = coalesced gradient columns held by this lane,
 // `w` = current weight columns (pre-loaded).  Group-uniform control flow.
 // OPTC >= 0 fixes the optimizer at compile time (smaller live state => more waves per SIMD).
@@ -209,6 +342,10 @@ __device__ __forceinline__ void apply_row(const BwdArgs& a, int f, int64_t local
                                           bool vec, int gl, WT* wrow, float4 (&w)[NV],
                                           float4 (&g)[NV], uint32_t rowh) {
   const RowRounding rr{sizeof(WT) == 2 ? a.rounding : TBE_ROUND_NEAREST_EVEN, rowh};
+  if constexpr (OPTC == kOptNormFamily) {
+    apply_row_norm<WT, G, NV>(a, f, local_row, D, vec, gl, wrow, w, g, rr);
+    return;
+  }
   const int optimizer = OPTC >= 0 ? OPTC : a.opt.optimizer;
   const float lr = a.opt.learning_rate;
   if (optimizer == TBE_OPT_EXACT_SGD) {
@@ -439,6 +576,16 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (val[u]) {
+          if (!FAST && a.max_gradient >= 0.f) {  // gradient clipping: the loaded element, before weight and MEAN division
+            const float mg = a.max_gradient;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+              x[u][v].x = fminf(fmaxf(x[u][v].x, -mg), mg);
+              x[u][v].y = fminf(fmaxf(x[u][v].y, -mg), mg);
+              x[u][v].z = fminf(fmaxf(x[u][v].z, -mg), mg);
+              x[u][v].w = fminf(fmaxf(x[u][v].w, -mg), mg);
+            }
+          }
 #pragma unroll
           for (int v = 0; v < NV; ++v) {
             acc[v].x = fmaf(wt[u], x[u][v].x, acc[v].x);
@@ -535,7 +682,7 @@ __device__ __forceinline__ void sum_partials(const float* __restrict__ base, int
   }
 }
 
-template <typename WT, typename KeyT, typename PayT, int G, int NV>
+template <typename WT, typename KeyT, typename PayT, int G, int NV, int OPTC>
 __global__ __launch_bounds__(256) void bwd_fixup_kernel(BwdArgs a) {
   constexpr int NG = kWave / G;
   constexpr int NGB = 4 * NG;
@@ -618,7 +765,7 @@ __global__ __launch_bounds__(256) void bwd_fixup_kernel(BwdArgs a) {
               tot[v].w += o.w;
             }
           }
-          apply_row<WT, G, NV>(a, f, lrow, D, vec, gl, wrow, w, tot,
+          apply_row<WT, G, NV, OPTC>(a, f, lrow, D, vec, gl, wrow, w, tot,
                             row_hash_if_needed<WT>(a, static_cast<uint64_t>(key_run)));
         }
       }
@@ -660,7 +807,7 @@ __global__ __launch_bounds__(256) void bwd_fixup_kernel(BwdArgs a) {
             tot[v].w += o.w;
           }
         }
-        apply_row<WT, G, NV>(a, f, lrow, D, vec, gl, wrow, w, tot,
+        apply_row<WT, G, NV, OPTC>(a, f, lrow, D, vec, gl, wrow, w, tot,
                             row_hash_if_needed<WT>(a, static_cast<uint64_t>(key_run)));
       }
     }
@@ -719,12 +866,14 @@ static int launch_update(const BwdArgs& a, hipStream_t st) {
   const unsigned grid = static_cast<unsigned>((nchunks + groups_per_block - 1) / groups_per_block);
   {
     ProfileSpan span(TBE_PROFILE_BWD_UPDATE_KERNEL, st);
-    const bool fast = a.fast_D > 0 && a.pooling_mode == TBE_POOL_SUM && a.psw == nullptr;
+    // (a launch with gradient clipping takes the generic kernel: the fast ones have no clamp)
+    const bool fast = a.fast_D > 0 && a.pooling_mode == TBE_POOL_SUM && a.psw == nullptr && a.max_gradient < 0.f;
     const int oc = a.opt.optimizer;
 #define TBE_UPD(OPTC, FAST_, UU, MW) \
   hipLaunchKernelGGL((bwd_update_kernel<WT, KeyT, PayT, G, NV, OPTC, FAST_, UU, MW>), dim3(grid), dim3(256), 0, st, a)
-    // the fast kernels exist for the one (G, NV) pair that can reach them
-    if constexpr (G == 32 && NV == 1) {
+    if (is_norm_family(oc)) {
+      TBE_UPD(kOptNormFamily, false, BwdUnroll<NV>::U, 1);
+    } else if constexpr (G == 32 && NV == 1) {  // the fast kernels exist for the one (G, NV) pair that can reach them
       if (fast && oc == TBE_OPT_EXACT_SGD) {
         TBE_UPD(TBE_OPT_EXACT_SGD, true, 4, 4);
       } else if (fast && oc == TBE_OPT_EXACT_ROWWISE_ADAGRAD) {
@@ -742,7 +891,10 @@ static int launch_update(const BwdArgs& a, hipStream_t st) {
   }
   TBE_CHECK_LAUNCH("tbe_backward update");
   const unsigned fgrid = static_cast<unsigned>(std::min<int64_t>((nchunks + 3) / 4, 1024));
-  hipLaunchKernelGGL((bwd_fixup_kernel<WT, KeyT, PayT, G, NV>), dim3(fgrid), dim3(256), 0, st, a);
+  if (is_norm_family(a.opt.optimizer))
+    hipLaunchKernelGGL((bwd_fixup_kernel<WT, KeyT, PayT, G, NV, kOptNormFamily>), dim3(fgrid), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((bwd_fixup_kernel<WT, KeyT, PayT, G, NV, -1>), dim3(fgrid), dim3(256), 0, st, a);
   TBE_CHECK_LAUNCH("tbe_backward fixup");
   return TBE_OK;
 }
@@ -771,7 +923,9 @@ static int bwd_setup(
     const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
     int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
     size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window, int phase,
-    BwdArgs* args, BwdWorkspace* ws, bool* wide_payload, bool* done) {
+    BwdArgs* args, BwdWorkspace* ws, bool* wide_payload, bool* done, bool ex = false,
+    const tbe_optimizer_ext* ext = nullptr) {
+  // ex: called by a tbe_backward_*_ex_* entry, which alone accepts the row-norm family and `ext`
   *done = false;
   TBE_REQUIRE(F > 0 && B >= 0 && N >= 0, "%s: bad sizes", who);
   if (phase == kPhasePrepare) {  // gradient / optimizer arguments are not used by this phase
@@ -803,10 +957,27 @@ static int bwd_setup(
       TBE_REQUIRE(feat_state0 != nullptr && feat_state1 != nullptr, "%s: ADAM needs two states", who);
       TBE_REQUIRE(opt.iteration >= 1, "%s: ADAM iteration must be >= 1", who);
       break;
+    case TBE_OPT_LAMB:
+    case TBE_OPT_PARTIAL_ROWWISE_ADAM:
+    case TBE_OPT_PARTIAL_ROWWISE_LAMB:
+    case TBE_OPT_LARS_SGD:
+      if (ex) {
+        TBE_REQUIRE(feat_state0 != nullptr, "%s: optimizer %d needs feat_state0", who, opt.optimizer);
+        TBE_REQUIRE(opt.optimizer == TBE_OPT_LARS_SGD || feat_state1 != nullptr, "%s: optimizer %d needs feat_state1", who,
+                    opt.optimizer);
+        TBE_REQUIRE(opt.optimizer != TBE_OPT_PARTIAL_ROWWISE_ADAM || opt.iteration >= 1,
+                    "%s: PARTIAL_ROWWISE_ADAM iteration must be >= 1", who);
+        break;
+      }
+      [[fallthrough]];
     default:
       set_error("%s: unknown optimizer %d", who, opt.optimizer);
       return TBE_ERR_UNSUPPORTED;
   }
+  const bool clip = ext != nullptr && ext->gradient_clipping != 0;
+  if (clip)
+    TBE_REQUIRE(ext->max_gradient >= 0.f && ext->max_gradient <= 3.402823466e38f,
+                "%s: gradient clipping needs a finite max_gradient >= 0", who);
   if (N == 0 || B == 0) {
     *done = true;
     return TBE_OK;
@@ -846,10 +1017,13 @@ static int bwd_setup(
   a.opt = opt;
   a.bias1 = 1.f;
   a.bias2 = 1.f;
-  if (opt.optimizer == TBE_OPT_ADAM) {
+  if (opt.optimizer == TBE_OPT_ADAM || opt.optimizer == TBE_OPT_PARTIAL_ROWWISE_ADAM) {
     a.bias1 = 1.f - powf(opt.beta1, static_cast<float>(opt.iteration));
     a.bias2 = 1.f - powf(opt.beta2, static_cast<float>(opt.iteration));
   }
+  a.momentum = ext != nullptr ? ext->momentum : 0.f;
+  a.eta = ext != nullptr ? ext->eta : 0.f;
+  a.max_gradient = clip ? ext->max_gradient : -1.f;
   a.partial_first = w.partial_first;
   a.partial_last = w.partial_last;
   a.origin_list = w.origin_list;

@@ -36,6 +36,17 @@ class OptimizerArgs(ctypes.Structure):
     ]
 
 
+class OptimizerExt(ctypes.Structure):
+    """Mirror of ``tbe_optimizer_ext`` (include/tbe_hip.h): handed to the ``tbe_backward_*_ex_*`` entries by pointer."""
+
+    _fields_ = [
+        ("momentum", c_float),
+        ("eta", c_float),
+        ("max_gradient", c_float),
+        ("gradient_clipping", c_i32),
+    ]
+
+
 class CacheDesc(ctypes.Structure):
     """Mirror of ``tbe_cache_desc`` (include/tbe_hip.h)."""
 
@@ -112,6 +123,30 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
          c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
          c_i32, c_void_p, c_size, c_i32, c_u64, c_void_p],
+    ),
+    "tbe_backward_fused_ex_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
+         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
+         c_i32, c_void_p, c_size, c_void_p, c_void_p, ctypes.POINTER(OptimizerExt), c_void_p],
+    ),
+    "tbe_backward_apply_ex_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
+         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
+         c_i32, c_void_p, c_size, ctypes.POINTER(OptimizerExt), c_void_p],
+    ),
+    "tbe_backward_fused_ex_f16w": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
+         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
+         c_i32, c_void_p, c_size, c_void_p, c_void_p, c_i32, c_u64, ctypes.POINTER(OptimizerExt), c_void_p],
+    ),
+    "tbe_backward_apply_ex_f16w": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
+         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
+         c_i32, c_void_p, c_size, c_i32, c_u64, ctypes.POINTER(OptimizerExt), c_void_p],
     ),
     "tbe_backward_indice_weights_f32": (
         ctypes.c_int,

@@ -5,7 +5,7 @@ Mirrors the module surface the reference constructs and calls
 :124-148 / :250-257 optimizer surface, :468-477 / :677-704 dense variant) on top of the
 C ABI in ``include/tbe_hip.h``.  Names, argument meaning and error behaviour follow the
 public fbgemm_gpu API of the reference's era; what the reference's own tests do not pin
-(row-wise Adagrad / Adam arithmetic, defaults) is marked "parity unpinned" in DESIGN.md.
+(row-wise Adagrad / Adam / LAMB / LARS / partial row-wise arithmetic, defaults) is marked "parity unpinned" in DESIGN.md.
 
 There is no CPU implementation here: ``ComputeDevice.CPU`` / ``use_cpu=True`` raise.
 """
@@ -20,7 +20,7 @@ import torch
 from torch import nn
 
 from . import _lib, _streams
-from ._lib import CacheDesc, OptimizerArgs, check, ptr, raise_on_faults, require_gpu, stream_ptr, workspace
+from ._lib import CacheDesc, OptimizerArgs, OptimizerExt, check, ptr, raise_on_faults, require_gpu, stream_ptr, workspace
 from .split_embedding_configs import EmbOptimType as OptimType
 from .split_embedding_configs import SparseType
 
@@ -71,8 +71,17 @@ _OPT_CODE = {
     OptimType.ROWWISE_ADAGRAD: 1,
     OptimType.ADAM: 2,
     OptimType.EXACT_ADAGRAD: 3,
+    # the row-norm family (include/tbe_hip.h, tbe_backward_*_ex_*)
+    OptimType.LAMB: 4,
+    OptimType.PARTIAL_ROWWISE_ADAM: 5,
+    OptimType.PARTIAL_ROWWISE_LAMB: 6,
+    OptimType.LARS_SGD: 7,
 }
 _OPT_DENSE_GRAD = 100
+_NORM_FAMILY = (4, 5, 6, 7)
+# layout of (momentum1, momentum2) per optimizer code: "row" = float[rows], "elem" = float[rows * D], None = absent
+_STATE_KINDS = {0: (None, None), 1: ("row", None), 2: ("elem", "elem"), 3: ("elem", None),
+                4: ("elem", "elem"), 5: ("elem", "row"), 6: ("elem", "row"), 7: ("elem", None)}
 
 
 @dataclass
@@ -694,7 +703,10 @@ class _TBEBase(nn.Module):
 
     def _backward_impl(self, grad_out, indices, offsets, per_sample_weights, B: int,
                        opt: OptimizerArgs, state0_override: Optional[torch.Tensor] = None,
-                       prepared=None, layout=None, state0_aligned: bool = False) -> None:
+                       prepared=None, layout=None, state0_aligned: bool = False,
+                       ext: Optional[OptimizerExt] = None) -> None:
+        """`ext` (momentum / eta / gradient clipping: include/tbe_hip.h tbe_optimizer_ext) selects the _ex entries, which
+        alone take the row-norm optimizers and clipping; without it the call is the one it always was."""
         lay = self._get_layout()
         dev = self.current_device
         lib = _lib.load()
@@ -721,21 +733,24 @@ class _TBEBase(nn.Module):
                       and (state0_override is None or state0_aligned)) else 0
         # FP16 tables: how the float result of a row update is rounded (include/tbe_hip.h TBE_ROUND_*)
         rounding = (int(getattr(self, "_rounding", 0)), int(getattr(self, "_sr_seed", 0))) if f16 else ()
+        extra = (ctypes_byref(ext),) if ext is not None else ()
+        ex = "_ex" if ext is not None else ""
         if per_sample_weights is not None:
             flags |= _FLAG_WEIGHTED  # the sort payload then carries positions too (set in prepare as well)
         with torch.cuda.device(dev):
             if prepared is not None:
                 ws, ev = prepared
                 torch.cuda.current_stream(dev).wait_event(ev)
-                apply = lib.tbe_backward_apply_f16w if f16 else lib.tbe_backward_apply_f32
+                apply_name = f"tbe_backward_apply{ex}_f16w" if f16 else f"tbe_backward_apply{ex}_f32"
+                apply = getattr(lib, apply_name)
                 check(
                     apply(ptr(lay.feat_weights), ptr(lay.feat_D), ptr(out_off),
                           ptr(lay.feat_rows), ptr(lay.feat_row_base), ptr(feat_state0),
                           ptr(lay.feat_state1), self.F, B, self.max_D, self.key_bits,
                           ptr(indices), N, ptr(offsets), ptr(per_sample_weights),
                           int(self.pooling_mode), ptr(lay.feat_pooling), ptr(grad_out), stride, opt, flags,
-                          ptr(ws), ws.numel(), *rounding, stream_ptr(dev)),
-                    "tbe_backward_apply_f16w" if f16 else "tbe_backward_apply_f32",
+                          ptr(ws), ws.numel(), *rounding, *extra, stream_ptr(dev)),
+                    apply_name,
                 )
                 return
             nbytes = lib.tbe_backward_workspace_bytes(N, self.F, B, self.max_D, self.key_bits)
@@ -743,7 +758,8 @@ class _TBEBase(nn.Module):
                 raise RuntimeError(f"TBE backward: {N} ids in one call is beyond the limit of 2^29 - 1 (include/tbe_hip.h): "
                                    "split the batch")
             ws = workspace(nbytes, dev)
-            fused = lib.tbe_backward_fused_f16w if f16 else lib.tbe_backward_fused_f32
+            fused_name = f"tbe_backward_fused{ex}_f16w" if f16 else f"tbe_backward_fused{ex}_f32"
+            fused = getattr(lib, fused_name)
             check(
                 fused(ptr(lay.feat_weights), ptr(lay.feat_D),
                       ptr(out_off), ptr(lay.feat_rows),
@@ -752,8 +768,8 @@ class _TBEBase(nn.Module):
                       self.max_D, self.key_bits, ptr(indices), N, ptr(offsets),
                       ptr(per_sample_weights), int(self.pooling_mode), ptr(lay.feat_pooling),
                       ptr(grad_out), stride, opt, flags, ptr(ws), ws.numel(),
-                      self._errors_ptr(), ptr(lay.feat_window), *rounding, stream_ptr(dev)),
-                "tbe_backward_fused_f16w" if f16 else "tbe_backward_fused_f32",
+                      self._errors_ptr(), ptr(lay.feat_window), *rounding, *extra, stream_ptr(dev)),
+                fused_name,
             )
 
     def _indice_weights_grad(self, grad_out, indices, offsets, B: int, layout=None,
@@ -804,6 +820,9 @@ class _TBEBase(nn.Module):
         place the rows this reads."""
         if rec.per_sample_weights is None:
             raise RuntimeError("indice_weights_grad: the lookup had no per_sample_weights")
+        if getattr(getattr(self, "optimizer_args", None), "gradient_clipping", False):
+            raise NotImplementedError("gradient_clipping=True with trained per_sample_weights (grad_indice_weights): the "
+                                      "indice-weights kernel does not clamp the output gradient")
         return self._indice_weights_grad(grad_out, rec.indices, rec.offsets, rec.B, rec.layout, feature_requires_grad)
 
 
@@ -841,7 +860,7 @@ class _FusedLookupInto(torch.autograd.Function):
                if ctx.needs_input_grad[5] else None)
         module.iter += 1
         module._backward_impl(grad_out, indices, offsets, psw, ctx.B, module._optimizer_struct(),
-                              prepared=ctx.prepared, layout=ctx.layout)
+                              prepared=ctx.prepared, layout=ctx.layout, ext=module._optimizer_ext())
         ctx.prepared = None
         if module._cache is not None:
             module._cache.after_backward()
@@ -895,7 +914,7 @@ class _FusedLookup(torch.autograd.Function):
                if ctx.needs_input_grad[4] else None)
         module.iter += 1
         module._backward_impl(grad_out, indices, offsets, psw, ctx.B, module._optimizer_struct(),
-                              prepared=ctx.prepared)
+                              prepared=ctx.prepared, ext=module._optimizer_ext())
         ctx.prepared = None
         if module._cache is not None:
             module._cache.after_backward()
@@ -956,8 +975,8 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
                                       "HBM row cache stores float rows (use MANAGED or DEVICE)")
         if optimizer not in _OPT_CODE:
             raise NotImplementedError(f"optimizer {optimizer} is not implemented")
-        if gradient_clipping:
-            raise NotImplementedError("gradient_clipping is not implemented")
+        if gradient_clipping and not (float(max_gradient) >= 0.0 and float(max_gradient) != float("inf")):
+            raise ValueError(f"gradient_clipping needs a finite max_gradient >= 0, not {max_gradient}")
         # weight decay: one form per optimizer is implemented (parity unpinned: fbgemm's is absent);
         # any other request raises instead of silently computing something else
         wdm = WeightDecayMode(int(weight_decay_mode))
@@ -971,6 +990,10 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
                                           "WeightDecayMode.L2 is not implemented")
             if optimizer in (OptimType.EXACT_SGD, OptimType.EXACT_ADAGRAD):
                 raise NotImplementedError(f"weight_decay is not implemented for {optimizer}")
+            if _OPT_CODE[optimizer] in _NORM_FAMILY and wdm != WeightDecayMode.NONE:
+                raise NotImplementedError(f"{optimizer} implements weight_decay in one form (weight_decay * w added to the "
+                                          "update direction; include/tbe_hip.h), selected by the default "
+                                          f"weight_decay_mode: {wdm.name} is not implemented")
         wdtype = torch.float16 if fp16 else torch.float32
         self._init_tables(list(rows), list(dims), list(locations), feature_table_map,
                           pooling_mode, device, weights_dtype=wdtype)
@@ -1000,15 +1023,12 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         self.register_buffer("weights_uvm", self._alloc("uvm", self._flat_sizes["uvm"], wdtype), persistent=False)
         code = _OPT_CODE[optimizer]
         rowwise = code == 1
-        elementwise = code in (2, 3)
-        for name, needed in (("momentum1", rowwise or elementwise), ("momentum2", code == 2)):
+        for name, kind in zip(("momentum1", "momentum2"), _STATE_KINDS[code]):
             for p in ("dev", "uvm"):
-                n = 0
-                if needed:
-                    n = self._row_sizes[p] if rowwise else self._flat_sizes[p]
+                n = 0 if kind is None else (self._row_sizes[p] if kind == "row" else self._flat_sizes[p])
                 self.register_buffer(f"{name}_{p}", self._alloc(p, n), persistent=False)
         # HBM row cache for the MANAGED_CACHING tables (SGD / row-wise Adagrad; tables whose optimizer
-        # keeps per-element state are served straight from host memory, like MANAGED)
+        # keeps per-element state — Adam, Adagrad, the row-norm family — are served straight from host memory, like MANAGED)
         cached = [t for t, loc in enumerate(self.locations) if loc == EmbeddingLocation.MANAGED_CACHING]
         if cached and code in (0, 1) and self.current_device.type == "cuda":
             self._cache = _RowCache(self, cached, cache_load_factor, cache_sets, rowwise_state=rowwise)
@@ -1028,10 +1048,8 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         return getattr(self, f"{name}_{placement}")
 
     def _state_key(self):
-        code = _OPT_CODE[self.optimizer]
-        if code == 0:
-            return ()
-        names = ("momentum1", "momentum2") if code == 2 else ("momentum1",)
+        kinds = _STATE_KINDS[_OPT_CODE[self.optimizer]]
+        names = [n for n, k in zip(("momentum1", "momentum2"), kinds) if k is not None]
         return tuple(self._state_flat(n, p).data_ptr() for n in names for p in ("dev", "uvm"))
 
     def _state_ptrs(self):
@@ -1039,14 +1057,14 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         if code == 0:
             return None, None
         out = []
-        for name in ("momentum1", "momentum2"):
-            if name == "momentum2" and code != 2:
+        for name, kind in zip(("momentum1", "momentum2"), _STATE_KINDS[code]):
+            if kind is None:
                 out.append(None)
                 continue
             ptrs = []
             for t in range(self.T):
                 flat = self._state_flat(name, self.placement[t])
-                off = self.state_row_offsets[t] if code == 1 else self.weights_offsets[t]
+                off = self.state_row_offsets[t] if kind == "row" else self.weights_offsets[t]
                 ptrs.append(flat.data_ptr() + 4 * off)
             out.append(ptrs)
         return out[0], out[1]
@@ -1054,26 +1072,24 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
     def split_optimizer_states(self) -> List[Tuple[torch.Tensor, ...]]:
         """Per-table optimizer state views (batched_embedding_kernel.py:133-148):
         ``()`` for SGD, ``(momentum1[rows],)`` for row-wise Adagrad,
-        ``(m[rows, D], v[rows, D])`` for Adam, ``(momentum1[rows, D],)`` for Adagrad."""
+        ``(m[rows, D], v[rows, D])`` for Adam and LAMB, ``(momentum1[rows, D],)`` for Adagrad and LARS_SGD,
+        ``(m[rows, D], v[rows])`` for PARTIAL_ROWWISE_ADAM / PARTIAL_ROWWISE_LAMB (the 1-D state the reference handles
+        on its own at :215-227)."""
         if self._cache is not None:
             self._cache.flush(invalidate=True)
-        code = _OPT_CODE[self.optimizer]
+        kinds = _STATE_KINDS[_OPT_CODE[self.optimizer]]
         states: List[Tuple[torch.Tensor, ...]] = []
         for t in range(self.T):
             r, d, p = self.rows_per_table[t], self.dims_per_table[t], self.placement[t]
-            if code == 0:
-                states.append(())
-            elif code == 1:
-                o = self.state_row_offsets[t]
-                states.append((self.momentum1_dev[o:o + r] if p == "dev" else self.momentum1_uvm[o:o + r],))
-            else:
-                o = self.weights_offsets[t]
-                m1 = self._state_flat("momentum1", p)[o:o + r * d].view(r, d)
-                if code == 2:
-                    m2 = self._state_flat("momentum2", p)[o:o + r * d].view(r, d)
-                    states.append((m1, m2))
-                else:
-                    states.append((m1,))
+            views = []
+            for name, kind in zip(("momentum1", "momentum2"), kinds):
+                if kind == "row":
+                    o = self.state_row_offsets[t]
+                    views.append(self._state_flat(name, p)[o:o + r])
+                elif kind == "elem":
+                    o = self.weights_offsets[t]
+                    views.append(self._state_flat(name, p)[o:o + r * d].view(r, d))
+            states.append(tuple(views))
         return states
 
     # optimizer surface ---------------------------------------------------------------------
@@ -1101,9 +1117,25 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         return OptimizerArgs(_OPT_CODE[self.optimizer], a.learning_rate, a.eps, a.weight_decay,
                              a.beta1, a.beta2, max(self.iter, 1))
 
+    def _optimizer_ext(self) -> Optional[OptimizerExt]:
+        """The extension struct of the _ex backward entries, for a module that needs them (a row-norm optimizer or
+        gradient clipping); None keeps a module on the entries it always called."""
+        a = self.optimizer_args
+        if _OPT_CODE[self.optimizer] not in _NORM_FAMILY and not a.gradient_clipping:
+            return None
+        return OptimizerExt(a.momentum, a.eta, a.max_gradient, 1 if a.gradient_clipping else 0)
+
+    def _refuse_clipped_indice_weights_grad(self, per_sample_weights) -> None:
+        if (self.optimizer_args.gradient_clipping and per_sample_weights is not None and per_sample_weights.requires_grad
+                and torch.is_grad_enabled()):
+            raise NotImplementedError(
+                "gradient_clipping=True with trained per_sample_weights (grad_indice_weights): the indice-weights kernel "
+                "does not clamp the output gradient, so the two gradients of one lookup would disagree")
+
     def forward(self, indices: torch.Tensor, offsets: torch.Tensor,
                 per_sample_weights: Optional[torch.Tensor] = None,
                 feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._refuse_clipped_indice_weights_grad(per_sample_weights)
         indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
         if self._cache is not None:
             indices = self._cache.prefetch(self._real_layout(), indices, offsets, B, torch.is_grad_enabled())
@@ -1120,6 +1152,7 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
                      feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Pooled lookup whose feature blocks land at `out[b * row_stride + out_offsets[f] + d]` of the
         given buffer (returned, marked dirty for autograd)."""
+        self._refuse_clipped_indice_weights_grad(per_sample_weights)
         indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
         if self._cache is not None:
             indices = self._cache.prefetch(self._real_layout(), indices, offsets, B, torch.is_grad_enabled())
@@ -1179,7 +1212,7 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         """Coalesced gradient + fused optimizer update for the lookup `rec` describes (what _FusedLookup.backward does)."""
         self.iter += 1
         self._backward_impl(grad_out, rec.indices, rec.offsets, rec.per_sample_weights, rec.B, self._optimizer_struct(),
-                            prepared=rec.prepared, layout=rec.layout)
+                            prepared=rec.prepared, layout=rec.layout, ext=self._optimizer_ext())
         rec.prepared = None
         if self._cache is not None:
             self._cache.after_backward()

@@ -621,6 +621,15 @@ class ShardedEmbeddingBagCollection(nn.Module):
                                           "(table_wise / row_wise / column_wise / data_parallel)")
         self._table_kind = kind
         self._has_cw = bool(cw_shards)
+        # LAMB, PARTIAL_ROWWISE_LAMB and LARS_SGD scale a row's step by norms over the WHOLE row, PARTIAL_ROWWISE_ADAM keeps
+        # one second moment per row: a column shard sees only its columns, so the result would depend on the sharding
+        # (table-wise and row-wise shards hold whole rows and are invariant).  Gradient clipping is element-wise: allowed.
+        opt = (fused_params or {}).get("optimizer")
+        if cw_shards and getattr(opt, "name", None) in ("LAMB", "PARTIAL_ROWWISE_ADAM", "PARTIAL_ROWWISE_LAMB", "LARS_SGD"):
+            raise NotImplementedError(
+                f"column-wise table(s) {[cfgs[t].name for t in cw_shards]} with optimizer {opt.name}: its row norms / row-wise "
+                "state are taken over a whole row, which a column shard does not hold; shard these tables table-wise or "
+                "row-wise, or use an element-wise optimizer")
         if self._has_cw and rw_input_dist == "bucketize":
             raise NotImplementedError(
                 "rw_input_dist='bucketize' with column-wise tables "
