@@ -11,8 +11,10 @@ Two halves:
   premise (tests/test_backward_run_inputs.py) imports this half.
 * `BackwardCase` lays tables and optimizer state in one flat device buffer between guard bytes, builds the feat_*
   arrays (a `row_base_shift` of 2^33 gives 64-bit sort keys, which the Python module only reaches with 2^32 rows), and
-  runs `tbe_backward_fused_*` or `tbe_backward_prepare` + `tbe_backward_apply_*` with an explicit `flags` word.
+  runs `tbe_backward_fused_*` or `tbe_backward_prepare` + `tbe_backward_apply_*` with an explicit `flags` word.  The
+  row-norm family (codes 4-7), an `ext=` (tbe_optimizer_ext) or `force_ex=True` take the `_ex` twins of those entries.
 """
+import ctypes
 import functools
 
 import numpy as np
@@ -102,6 +104,15 @@ def make_inputs(layout, dims, ftm=None, weighted=False, nobag=False, seed=0):
     return _make_inputs(layout, tuple(dims), ftm, bool(weighted), bool(nobag), seed)
 
 
+def with_grad(inp, grad):
+    """`inp` with another output gradient of the same shape (read-only, like the rest); nothing is shared on the device."""
+    grad = np.ascontiguousarray(grad, dtype=np.float32)
+    assert grad.shape == inp.grad.shape
+    grad.setflags(write=False)
+    kw = {k: v for k, v in inp.__dict__.items() if k != "_dev"}
+    return Inputs(**dict(kw, grad=grad))
+
+
 def feature_of_position(inp):
     return np.repeat(np.arange(inp.F), np.diff(inp.offsets[::inp.B]))
 
@@ -160,10 +171,21 @@ GUARD_ELEMS = 64
 GUARD_BYTE = 0xC3
 
 
+OPT_LAMB, OPT_PARTIAL_ROWWISE_ADAM, OPT_PARTIAL_ROWWISE_LAMB, OPT_LARS_SGD = 4, 5, 6, 7  # TBE_OPT_*: the _ex entries only
+NORM_FAMILY = (OPT_LAMB, OPT_PARTIAL_ROWWISE_ADAM, OPT_PARTIAL_ROWWISE_LAMB, OPT_LARS_SGD)
+
+
 def opt_args(code, lr, eps=1e-8, weight_decay=0.0, beta1=0.9, beta2=0.999, iteration=1):
     from fbgemm_gpu._lib import OptimizerArgs
 
     return OptimizerArgs(int(code), lr, eps, weight_decay, beta1, beta2, iteration)
+
+
+def opt_ext(momentum=0.0, eta=0.0, max_gradient=None):
+    """tbe_optimizer_ext; max_gradient None = no clipping."""
+    from fbgemm_gpu._lib import OptimizerExt
+
+    return OptimizerExt(momentum, eta, 0.0 if max_gradient is None else max_gradient, int(max_gradient is not None))
 
 
 class Result:
@@ -178,8 +200,12 @@ def _state_shapes(code, rows, dims):
         return [(r,) for r in rows], None
     if code in (oracle.OPT_EXACT_ADAGRAD, oracle.OPT_DENSE_GRAD):
         return per_elem, None
-    if code == oracle.OPT_ADAM:
+    if code in (oracle.OPT_ADAM, OPT_LAMB):
         return per_elem, per_elem
+    if code in (OPT_PARTIAL_ROWWISE_ADAM, OPT_PARTIAL_ROWWISE_LAMB):
+        return per_elem, [(r,) for r in rows]
+    if code == OPT_LARS_SGD:
+        return per_elem, None
     return None, None
 
 
@@ -275,9 +301,11 @@ class BackwardCase:
         return self._dev
 
     def run(self, inp, opt, pooling=oracle.POOL_SUM, feat_pooling=None, mode="fused", flags=None,
-            rounding=ROUND_NEAREST_EVEN, seed=0):
+            rounding=ROUND_NEAREST_EVEN, seed=0, ext=None, force_ex=False):
         """mode "fused": tbe_backward_fused_*; "split": tbe_backward_prepare + tbe_backward_apply_*.  flags None = what a
-        host may assert (UNIFORM_ALIGNED where it holds); TBE_FLAG_WEIGHTED is added whenever the batch has weights."""
+        host may assert (UNIFORM_ALIGNED where it holds); TBE_FLAG_WEIGHTED is added whenever the batch has weights.
+        ext (fbgemm_gpu._lib.OptimizerExt), an optimizer code of the row-norm family or force_ex=True (ext = NULL) call
+        the tbe_backward_*_ex_* twin of the same entry."""
         import torch
         from fbgemm_gpu import _lib
 
@@ -303,20 +331,23 @@ class BackwardCase:
         st = _lib.stream_ptr(dev)
         p = _lib.ptr
         f16 = self.dtype == np.float16
+        ex = ext is not None or force_ex or int(opt.optimizer) in NORM_FAMILY
+        name = ("{}_ex_{}" if ex else "{}_{}").format("{}", "f16w" if f16 else "f32")
+        ext_arg = ((ctypes.byref(ext) if ext is not None else None),) if ex else ()
         table_args = (p(d["weights"]), p(d["feat_D"]), p(out_off), p(d["feat_rows"]), p(d["feat_row_base"]), p(d["state0"]),
                       p(d["state1"]), self.F, inp.B, self.max_D, self.key_bits, p(indices), inp.N, p(offsets), p(psw),
                       int(pooling), p(fpool), p(grad), stride, opt, flags, ws, nbytes)
         rnd = (int(rounding), int(seed)) if f16 else ()
         if mode == "fused":
-            fn = lib.tbe_backward_fused_f16w if f16 else lib.tbe_backward_fused_f32
-            _lib.check(fn(*table_args, p(bounds), None, *rnd, st), "tbe_backward_fused")
+            fn = getattr(lib, name.format("tbe_backward_fused"))
+            _lib.check(fn(*table_args, p(bounds), None, *rnd, *ext_arg, st), name.format("tbe_backward_fused"))
         else:
             assert mode == "split"
             _lib.check(lib.tbe_backward_prepare(p(d["feat_rows"]), p(d["feat_row_base"]), self.F, inp.B, self.max_D,
                                                 self.key_bits, p(indices), inp.N, p(offsets), int(pooling),
                                                 flags & FLAG_WEIGHTED, ws, nbytes, p(bounds), None, st), "tbe_backward_prepare")
-            fn = lib.tbe_backward_apply_f16w if f16 else lib.tbe_backward_apply_f32
-            _lib.check(fn(*table_args, *rnd, st), "tbe_backward_apply")
+            fn = getattr(lib, name.format("tbe_backward_apply"))
+            _lib.check(fn(*table_args, *rnd, *ext_arg, st), name.format("tbe_backward_apply"))
         torch.cuda.synchronize()
         assert _lib.fault_count() == faults, "the pair sort gave up on a spin-wait"
         after = d["buf"].cpu().numpy()

@@ -4,8 +4,9 @@ GPU kernel may be compared with it bitwise.  Widening a value range breaks THIS 
 import numpy as np
 import pytest
 
+import _fused_optim_ref
 import _paths  # noqa: F401
-from _bwd_abi import LAYOUTS, BackwardCase, coalesced_grad_f64, make_inputs, valid_keys
+from _bwd_abi import LAYOUTS, BackwardCase, coalesced_grad_f64, make_inputs, valid_keys, with_grad
 from oracle import oracle
 
 CONFIGS = {
@@ -39,6 +40,31 @@ def test_oracle_dense_gradient_equals_the_float64_sum_exactly(layout, cfg):
         # the sums are multiples of 1/8 far below 2^24 / 8: every partial sum of every order is representable
         assert np.array_equal(ref[t] * 8, np.round(ref[t] * 8)) and np.abs(ref[t]).max() * 8 < 2 ** 24
         assert np.abs(ref[t]).max() > 0
+
+
+CLIP = 1.5  # _fused_optim_ref.RUN_CLIP: the bound the clipping tests of the run harness use
+
+
+@pytest.mark.parametrize("layout,cfg", list(_cases()))
+def test_clamped_gradient_is_exact_too(layout, cfg):
+    """Gradient clipping at 1.5 clamps the integer gradients to {-1.5, -1, 0, 1, 1.5}: times {0.5, 1, 2} and over {1, 2, 4}
+    every term is a multiple of 1/16, so the FP32 sum of clamped terms equals the float64 one bit for bit in any order."""
+    assert _fused_optim_ref.RUN_CLIP == CLIP
+    base = make_inputs(layout, cfg["dims"], weighted=cfg["weighted"])
+    inp = with_grad(base, np.clip(base.grad, -CLIP, CLIP))
+    assert set(np.unique(inp.grad).tolist()) == {-1.5, -1.0, 0.0, 1.0, 1.5} and (np.abs(base.grad) > CLIP).mean() > 0.5
+    case = BackwardCase(inp.rows, cfg["dims"], row_base_shift=cfg["shift"], code=oracle.OPT_DENSE_GRAD)
+    tabs, dense, _ = case.oracle_tables()
+    bad = oracle.tbe_backward(tabs, inp.indices, inp.offsets, inp.grad, oracle.OPT_DENSE_GRAD, 0.0, inp.psw, cfg["pooling"],
+                              state0=dense)
+    assert bad == inp.n_bad * inp.F
+    ref = coalesced_grad_f64(inp, tabs, cfg["pooling"])
+    unclamped = coalesced_grad_f64(base, tabs, cfg["pooling"])
+    for t in range(len(inp.rows)):
+        assert dense[t].dtype == np.float32
+        assert np.array_equal(dense[t].astype(np.float64), ref[t]), f"table {t}"
+        assert np.array_equal(ref[t] * 16, np.round(ref[t] * 16)) and np.abs(ref[t]).max() * 16 < 2 ** 24
+        assert not np.array_equal(ref[t], unclamped[t])
 
 
 @pytest.mark.parametrize("layout", list(LAYOUTS))

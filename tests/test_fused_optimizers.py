@@ -1,6 +1,7 @@
 """CPU half of the row-norm optimizer family (LAMB, PARTIAL_ROWWISE_ADAM, PARTIAL_ROWWISE_LAMB, LARS_SGD) and gradient
 clipping: the C ABI's argument validation, which returns before anything is launched, and the margin of the numpy
-restatement the GPU tests (tests/test_fused_optimizers_gpu.py) compare with."""
+restatement the GPU tests (tests/test_fused_optimizers_gpu.py) compare with; for the run harness
+(tests/test_fused_optimizers_runs_gpu.py) also where its tolerance comes from and that a wrong norm leaves it."""
 import ctypes
 import math
 
@@ -108,3 +109,81 @@ def test_guard_inputs_reach_both_guards_and_stay_finite(code):
     assert all(np.isfinite(a).all() for a in done.w + [s[0] for s in done.state if s is not None])
     np.testing.assert_array_equal(done.w[0][1], c.weights[0][1].astype(np.float64))
     assert np.abs(done.w[0][0]).min() > 0
+
+
+# ---- the run harness: tolerance and sensitivity --------------------------------------------------------------------------
+def _run_case(cfg):
+    from _bwd_abi import BackwardCase, finishing_paths
+
+    layout, dims, payload, code, wd, clip = cfg
+    inp = fo.run_inputs(layout, dims, payload)
+    case = BackwardCase(inp.rows, list(dims), code=code)  # the initial arrays the GPU test starts from
+    return inp, case, finishing_paths(inp, case.oracle_tables()[0])
+
+
+def _arrays(ref, t):
+    return [("weights", ref.w[t])] + [(f"state{k}", s[t]) for k, s in enumerate(ref.state) if s is not None]
+
+
+@pytest.mark.parametrize("cfg", fo.RUN_CONFIGS, ids=fo.run_config_id)
+def test_run_harness_float32_restatement_is_within_an_eighth_of_the_tolerance(cfg):
+    """NORM_TOL = 8 x NORM_F32_ERROR, and NORM_F32_ERROR bounds max |r32 - r64| / (1 + |r64|) of the restatement run in
+    float32 on exactly the GPU configurations (worst measured: 4.257e-7, the weights of PARTIAL_ROWWISE_ADAM at [2048]).  A configuration
+    added to RUN_CONFIGS that needs more fails here, not on the GPU."""
+    inp, case, _ = _run_case(cfg)
+    r64, r32 = fo.run_reference(cfg, case.init), fo.run_reference(cfg, case.init, np.float32)
+    assert fo.NORM_TOL == 8 * fo.NORM_F32_ERROR and fo.NORM_TOL <= fo.RTOL
+    for t in range(len(inp.rows)):
+        for (what, a32), (_, a64) in zip(_arrays(r32, t), _arrays(r64, t)):
+            assert a32.dtype == np.float32 and a64.dtype == np.float64
+            err = fo.norm_error(a32, a64).max() * 8  # in units of NORM_F32_ERROR
+            assert err <= 1.0, f"{what} of table {t}: float32 is {err:.3f} x NORM_F32_ERROR away from float64"
+            R = inp.touched[t]
+            assert (a64[R] != np.asarray(case.init[what][t], dtype=np.float64)[R]).reshape(R.size, -1).any(axis=1).all()
+
+
+@pytest.mark.parametrize("code", fo.RUN_GUARD_CODES, ids=lambda c: fo.OPT_NAMES[c])
+def test_run_harness_guard_rows_are_finished_by_the_block_fixup_and_reach_both_guards(code):
+    from _bwd_abi import BLOCK_FIXUP, BackwardCase, coalesced_grad_f64, finishing_paths
+
+    cfg, inp, init, zero_g, zero_w = fo.run_guard_case(code)
+    tabs = BackwardCase(inp.rows, [128]).oracle_tables()[0]
+    paths = finishing_paths(inp, tabs)[0]
+    assert zero_g != zero_w and paths[zero_g] == paths[zero_w] == BLOCK_FIXUP
+    G = coalesced_grad_f64(inp, tabs, fo.POOL_SUM)[0]
+    assert not G[zero_g].any() and G[zero_w].any() and not init["weights"][0][zero_w].any()
+    assert np.array_equal(G * 8, np.round(G * 8))  # zeroed bags keep the sums exact
+    r64, r32 = fo.run_guard_reference(code), fo.run_guard_reference(code, np.float32)
+    for (what, a32), (_, a64) in zip(_arrays(r32, 0), _arrays(r64, 0)):
+        assert np.isfinite(a64).all()
+        assert fo.norm_error(a32, a64).max() * 8 <= 1.0
+        np.testing.assert_array_equal(a64[zero_g], np.asarray(init[what][0][zero_g], dtype=np.float64))  # |g| = |u| = 0: no move
+    assert r64.w[0][zero_w].any()  # |w| = 0: the ratio is 1 and the row moves
+
+
+SENSITIVITY_CONFIGS = [cfg for cfg in fo.RUN_CONFIGS if cfg[0] == "MIXED" and cfg[5] is None]
+
+
+@pytest.mark.parametrize("cfg", SENSITIVITY_CONFIGS, ids=fo.run_config_id)
+def test_a_column_missing_from_any_one_norm_leaves_the_run_harness_tolerance(cfg):
+    """The condition NORM_TOL has to meet: a kernel that drops the last valid column from ONE of the optimizer's sums of
+    squares (|w|, |g|, |u|, the mean(g^2) of v) gives, in every table and on EVERY finishing path, at least one row that a
+    comparison at NORM_TOL rejects — for every optimizer and every dispatch class, D = 2048 included.  The smallest
+    margin is |g| of LARS_SGD at [2048] on the wave fix-up's rows: 3.09 x NORM_TOL.  At rtol = atol = 2e-5 that change is
+    0.53 x the tolerance (0.91 x on the in-chunk rows) and this test fails."""
+    from _bwd_abi import PATH_NAMES
+
+    inp, case, paths = _run_case(cfg)
+    code = cfg[3]
+    good = fo.run_reference(cfg, case.init)
+    for which in fo.NORMS[code]:
+        bad = fo.run_reference(cfg, case.init, drop=which)
+        for t in range(len(inp.rows)):
+            err = np.max([fo.norm_error(b, g).reshape(inp.rows[t], -1).max(axis=1)
+                          for (_, b), (_, g) in zip(_arrays(bad, t), _arrays(good, t))], axis=0)
+            assert not err[paths[t] < 0].any()  # rows no id names do not move at all
+            for p, name in PATH_NAMES.items():
+                assert (paths[t] == p).any()
+                worst = err[paths[t] == p].max()
+                assert worst > 1.0, (f"dropping a column from {which!r}: table {t}, rows finished {name}: the largest "
+                                     f"change is {worst:.3f} x NORM_TOL — the comparison would not see it")

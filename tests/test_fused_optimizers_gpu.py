@@ -191,7 +191,6 @@ def test_constructor_refusals_of_the_new_ground():
 # ---- 7. the _ex entry with ext = NULL is its twin --------------------------------------------------------------------
 def test_ex_entry_without_ext_is_bit_identical_to_its_twin():
     from _bwd_abi import BackwardCase, Inputs, opt_args
-    from fbgemm_gpu import _lib
 
     c = fo.case("a")
     indices, offsets, psw, grad = c.batches[0]
@@ -199,27 +198,12 @@ def test_ex_entry_without_ext_is_bit_identical_to_its_twin():
     bc = BackwardCase(c.rows, c.dims, init={"weights": [w.copy() for w in c.weights], "state0": None, "state1": None})
     opt = opt_args(fo.SGD, 0.05)
     twin = bc.run(inp, opt)
-    lib, d, dev = _lib.load(), bc._device(), torch.device("cuda", 0)
-    d["buf"].copy_(d["host"])
-    nbytes = lib.tbe_backward_workspace_bytes(inp.N, bc.F, inp.B, bc.max_D, bc.key_bits)
-    ws = torch.full((nbytes + 256,), 0xFF, dtype=torch.uint8, device="cuda")
-    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-    bounds = torch.zeros(1, dtype=torch.int32, device="cuda")
-    p = _lib.ptr
-    i_dev, o_dev, _, g_dev = inp._dev
-    _lib.check(lib.tbe_backward_fused_ex_f32(
-        p(d["weights"]), p(d["feat_D"]), p(d["out_pooled"]), p(d["feat_rows"]), p(d["feat_row_base"]), None, None, bc.F,
-        inp.B, bc.max_D, bc.key_bits, p(i_dev), inp.N, p(o_dev), None, 0, None, p(g_dev), int(grad.shape[1]), opt, 0, ws_ptr,
-        nbytes, p(bounds), None, None, _lib.stream_ptr(dev)), "tbe_backward_fused_ex_f32")
-    torch.cuda.synchronize()
-    after = d["buf"].cpu().numpy()
-    assert twin.guards_ok and int(bounds.item()) == 0
+    ex = bc.run(inp, opt, flags=0, force_ex=True)  # tbe_backward_fused_ex_f32 with ext = NULL
+    assert twin.guards_ok and ex.bounds == 0
     for t in range(bc.T):
-        o, a = bc._slots[("weights", t)]
-        got = after[o:o + a.nbytes].view(a.dtype).reshape(a.shape)
-        np.testing.assert_array_equal(got, twin.weights[t])
-        assert (got != c.weights[t]).any()
-    assert (after[bc._gap] == 0xC3).all()
+        np.testing.assert_array_equal(ex.weights[t], twin.weights[t])
+        assert (ex.weights[t] != c.weights[t]).any()
+    assert ex.guards_ok
 
 
 # ---- 8. FP16 tables ---------------------------------------------------------------------------------------------------

@@ -168,13 +168,16 @@ STATEFUL_CONFIGS = {"d128": ([128], "narrow_sum"), "d13_260": ([13, 260], "wide_
 TOL = 2e-5  # rtol = atol of test_tbe_gpu.py::test_backward_fused_vs_oracle; the gradient itself is exact here
 
 
-def _worst_row_per_path(got, want, paths):
-    """{path name: (|got - want| / (atol + rtol |want|) of its worst row, that row)} over the rows ids name."""
-    err = np.abs(got.astype(np.float64) - want) / (TOL + TOL * np.abs(want.astype(np.float64)))
+def _worst_row_per_path(got, want, paths, tol=TOL):
+    """{path name: (|got - want| / (atol + rtol |want|) of its worst row, that row)} over the rows ids name, for every
+    finishing path the layout has."""
+    err = np.abs(got.astype(np.float64) - want) / (tol + tol * np.abs(want.astype(np.float64)))
     err = err.reshape(got.shape[0], -1).max(axis=1)
     out = {}
     for p, name in PATH_NAMES.items():
         rows = np.nonzero(paths == p)[0]
+        if rows.size == 0:
+            continue
         worst = rows[np.argmax(err[rows])]
         out[name] = (float(err[worst]), int(worst))
     return out
