@@ -507,6 +507,41 @@ int tbe_permute_2d_data(const int32_t* permute, int32_t T_out, int32_t B,
                         void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * torch.ops.fbgemm.permute_1D_sparse_data (torchrec/distributed/dist_data.py:249-255: the
+ * recat of a variable-batch KJTAllToAll).  The B = 1 case of permute_2D, in the same two
+ * steps: lengths [L] (elem 4|8), permute [P] int32 with entries in [0, L), P need not
+ * equal L (entries may repeat or be left out).
+ *  1. tbe_permute_1d_lengths: out_lengths[i] = lengths[permute[i]]; in_offsets [L+1] /
+ *     out_offsets [P+1] = complete cumsums (int64) written to caller buffers.
+ *  2. tbe_permute_1d_data: segment i of out_values (and out_weights) = segment permute[i].
+ * The 2-D kernels count segments in `int`: L or P outside [0, 2^31) is
+ * TBE_ERR_INVALID_ARGUMENT (workspace query: 0), never a wrapped count.
+ * ---------------------------------------------------------------------------------- */
+size_t tbe_permute_1d_workspace_bytes(int64_t L, int64_t P);
+int tbe_permute_1d_lengths(const int32_t* permute, int64_t L, int64_t P, const void* lengths,
+                           int32_t len_elem_size, void* out_lengths, int64_t* in_offsets,
+                           int64_t* out_offsets, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int tbe_permute_1d_data(const int32_t* permute, int64_t P, const int64_t* in_offsets,
+                        const int64_t* out_offsets, const void* values, void* out_values,
+                        int32_t val_elem_size, const void* weights, void* out_weights,
+                        int32_t w_elem_size, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * torch.ops.fbgemm.expand_into_jagged_permute (torchrec/distributed/dist_data.py:110-115:
+ * the element-level recat of a variable-batch KJTAllToAll).
+ *   out[output_offset[i] + k] = input_offset[permute[i]] + k
+ *   for i in [0, P), k in [0, output_offset[i+1] - output_offset[i]).
+ * permute [P], input_offset [P+1], output_offset [P+1] and out [output_size] share one
+ * element size, 4 (int32) or 8 (int64).  The segment length is read from output_offset; that
+ * it equals the input segment's is the caller's contract.  Nothing is stored outside
+ * [0, output_size).  P == 0 or output_size == 0 launches nothing.
+ * ---------------------------------------------------------------------------------- */
+int tbe_expand_into_jagged_permute(const void* permute, const void* input_offset,
+                                   const void* output_offset, int64_t P, int64_t output_size,
+                                   int32_t elem_size, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * torch.ops.fbgemm.block_bucketize_sparse_features
  * (torchrec/distributed/embedding_sharding.py:121-184; python reference of the result:
  * torchrec/distributed/tests/test_utils.py:83-236).

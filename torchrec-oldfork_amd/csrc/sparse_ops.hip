@@ -196,6 +196,57 @@ __global__ __launch_bounds__(256) void permute_lengths_kernel(const int32_t* __r
 }
 
 // ---------------------------------------------------------------------------------------
+// expand_into_jagged_permute: out[output_offset[i] + k] = input_offset[permute[i]] + k for k inside output segment i.
+// The scheme of permute_2d_data_kernel with the copy replaced by the index itself: a wave serves 64 consecutive output
+// segments, its lanes stride over their contiguous output range (coalesced stores) and find their segment by the
+// cross-lane search.  The recat of KJTAllToAll has FEW, LONG segments (F_local x W of them, a batch each), so the 64
+// segments' range is dealt to `splits` waves in interleaved 64-element chunks (wave j takes chunks j, j + splits, ...):
+// one wave alone took 1.37 ms for 32 segments of ~8192 on the MI355X.  Stores are confined to [0, output_size) and a
+// permute entry outside [0, P) reads nothing, so offsets that break the caller's contract cannot make the kernel touch
+// memory it was not given.
+// ---------------------------------------------------------------------------------------
+constexpr int kExpandChunksPerWave = 16;  // chunks of 64 outputs a wave should find in an average range
+constexpr int kExpandMaxSplits = 4096;
+
+template <typename T>
+__global__ __launch_bounds__(256) void expand_into_jagged_permute_kernel(const T* __restrict__ perm, int64_t P,
+                                                                        const T* __restrict__ in_offsets,
+                                                                        const T* __restrict__ out_offsets,
+                                                                        int64_t output_size, int splits,
+                                                                        T* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  const int64_t group = wave / splits;
+  const int64_t j = wave - group * splits;
+  const int64_t s0 = group * kWave;
+  if (s0 >= P) return;
+  const int64_t s = s0 + lane;
+  const int64_t s_end = min(s0 + static_cast<int64_t>(kWave), P);
+  const int64_t range_begin = static_cast<int64_t>(out_offsets[s0]);
+  const int64_t range_end = min(static_cast<int64_t>(out_offsets[s_end]), output_size);
+  int64_t ostart_l = range_end, istart_l = 0;  // lanes past P: a sentinel the search below never selects
+  if (s < P) {
+    ostart_l = static_cast<int64_t>(out_offsets[s]);
+    const int64_t p = static_cast<int64_t>(perm[s]);
+    if (static_cast<uint64_t>(p) < static_cast<uint64_t>(P)) istart_l = static_cast<int64_t>(in_offsets[p]);
+  }
+  for (int64_t eb = range_begin + j * kWave; eb < range_end; eb += static_cast<int64_t>(splits) * kWave) {
+    const int64_t e = eb + lane;
+    // largest segment k in [0, 64) with ostart[k] <= e
+    int k = 0;
+#pragma unroll
+    for (int step = 32; step >= 1; step >>= 1) {
+      const int cand = k + step;
+      const int64_t v = shfl64(ostart_l, cand & 63);
+      if (cand < kWave && v <= e) k = cand;
+    }
+    const int64_t os = shfl64(ostart_l, k);
+    const int64_t is = shfl64(istart_l, k);
+    if (e >= 0 && e < range_end) out[e] = static_cast<T>(is + (e - os));
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // block_bucketize_sparse_features.  Thread per bag for count and scatter (a bag's entries in
 // new_lengths / cursor are touched by that thread only => no atomics, stable order).
 // ---------------------------------------------------------------------------------------
@@ -512,6 +563,61 @@ extern "C" int tbe_permute_2d_data(const int32_t* permute, int32_t T_out, int32_
     case 4: return launch_permute_data<uint32_t>(permute, T_out, B, in_offsets, out_offsets, values, out_values, weights, out_weights, we, st);
     default: return launch_permute_data<uint64_t>(permute, T_out, B, in_offsets, out_offsets, values, out_values, weights, out_weights, we, st);
   }
+}
+
+// permute_1D_sparse_data is the B = 1 case of permute_2D: the same scan and data kernels serve it.  The
+// 2-D entries count segments in `int`; a 1-D call that does not fit is refused, not wrapped.
+static bool fits_segment_count(int64_t n) { return n >= 0 && n <= INT32_MAX; }
+
+extern "C" size_t tbe_permute_1d_workspace_bytes(int64_t L, int64_t P) {
+  if (!fits_segment_count(L) || !fits_segment_count(P)) return 0;
+  return tbe_permute_2d_workspace_bytes(static_cast<int32_t>(L), static_cast<int32_t>(P), 1);
+}
+
+extern "C" int tbe_permute_1d_lengths(const int32_t* permute, int64_t L, int64_t P, const void* lengths,
+                                      int32_t len_elem_size, void* out_lengths, int64_t* in_offsets,
+                                      int64_t* out_offsets, void* workspace, size_t workspace_bytes, void* stream) {
+  TBE_REQUIRE(fits_segment_count(L) && fits_segment_count(P),
+              "tbe_permute_1d_lengths: L=%lld / P=%lld outside [0, 2^31)", (long long)L, (long long)P);
+  TBE_REQUIRE(P == 0 || (permute != nullptr && out_lengths != nullptr), "tbe_permute_1d_lengths: null pointer");
+  TBE_REQUIRE(L == 0 || lengths != nullptr, "tbe_permute_1d_lengths: null lengths");
+  return tbe_permute_2d_lengths(permute, static_cast<int32_t>(L), static_cast<int32_t>(P), 1, lengths, len_elem_size,
+                                out_lengths, in_offsets, out_offsets, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tbe_permute_1d_data(const int32_t* permute, int64_t P, const int64_t* in_offsets,
+                                   const int64_t* out_offsets, const void* values, void* out_values,
+                                   int32_t val_elem_size, const void* weights, void* out_weights, int32_t w_elem_size,
+                                   void* stream) {
+  TBE_REQUIRE(fits_segment_count(P), "tbe_permute_1d_data: P=%lld outside [0, 2^31)", (long long)P);
+  return tbe_permute_2d_data(permute, static_cast<int32_t>(P), 1, in_offsets, out_offsets, values, out_values,
+                             val_elem_size, weights, out_weights, w_elem_size, stream);
+}
+
+extern "C" int tbe_expand_into_jagged_permute(const void* permute, const void* input_offset, const void* output_offset,
+                                              int64_t P, int64_t output_size, int32_t elem_size, void* out, void* stream) {
+  TBE_REQUIRE(P >= 0 && output_size >= 0, "tbe_expand_into_jagged_permute: bad sizes");
+  TBE_REQUIRE(elem_size == 4 || elem_size == 8, "tbe_expand_into_jagged_permute: elem_size %d", elem_size);
+  if (P == 0 || output_size == 0) return TBE_OK;
+  TBE_REQUIRE(permute && input_offset && output_offset && out, "tbe_expand_into_jagged_permute: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // waves per 64-segment group: enough that an average range gives each kExpandChunksPerWave chunks of 64 outputs
+  const int64_t groups = (P + kWave - 1) / kWave;
+  const int64_t per_wave = static_cast<int64_t>(kWave) * kExpandChunksPerWave;
+  const int splits = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(kExpandMaxSplits, (output_size / groups + per_wave - 1) / per_wave)));
+  const int64_t blocks = (groups * splits + 3) / 4;
+  TBE_REQUIRE(blocks <= INT32_MAX, "tbe_expand_into_jagged_permute: P=%lld too large", (long long)P);
+  const unsigned grid = static_cast<unsigned>(blocks);
+  if (elem_size == 4)
+    hipLaunchKernelGGL((expand_into_jagged_permute_kernel<int32_t>), dim3(grid), dim3(256), 0, st,
+                       static_cast<const int32_t*>(permute), P, static_cast<const int32_t*>(input_offset),
+                       static_cast<const int32_t*>(output_offset), output_size, splits, static_cast<int32_t*>(out));
+  else
+    hipLaunchKernelGGL((expand_into_jagged_permute_kernel<int64_t>), dim3(grid), dim3(256), 0, st,
+                       static_cast<const int64_t*>(permute), P, static_cast<const int64_t*>(input_offset),
+                       static_cast<const int64_t*>(output_offset), output_size, splits, static_cast<int64_t*>(out));
+  TBE_CHECK_LAUNCH("tbe_expand_into_jagged_permute");
+  return TBE_OK;
 }
 
 namespace {

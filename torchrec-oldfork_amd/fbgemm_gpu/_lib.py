@@ -179,6 +179,17 @@ SIGNATURES = {
         [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
          c_i32, c_void_p],
     ),
+    "tbe_permute_1d_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "tbe_permute_1d_lengths": (
+        ctypes.c_int,
+        [c_void_p, c_i64, c_i64, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p],
+    ),
+    "tbe_permute_1d_data": (
+        ctypes.c_int,
+        [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p],
+    ),
+    "tbe_expand_into_jagged_permute": (
+        ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i32, c_void_p, c_void_p]),
     "tbe_bucketize_workspace_bytes": (c_size, [c_i64, c_i32]),
     "tbe_block_bucketize": (
         ctypes.c_int,

@@ -5,6 +5,8 @@ Schemas are the ones the reference calls:
   * permute_2D_sparse_data              torchrec/sparse/jagged_tensor.py:946-952,
                                         torchrec/distributed/dist_data.py:257-263,
                                         torchrec/distributed/comm_ops.py:633-639, 691-697
+  * permute_1D_sparse_data              torchrec/distributed/dist_data.py:249-255 (variable batch size per rank)
+  * expand_into_jagged_permute          torchrec/distributed/dist_data.py:110-115 (variable batch size per rank)
   * block_bucketize_sparse_features     torchrec/distributed/embedding_sharding.py:160-168
   * offsets_range                       torchrec/modules/feature_processor.py:65
   * jagged_2d_to_dense                  examples/bert4rec/models/bert4rec.py:394-400
@@ -126,6 +128,86 @@ def permute_2D_sparse_data(
             "tbe_permute_2d_data",
         )
     return out_lengths, out_values, out_weights
+
+
+def permute_1D_sparse_data(
+    permute: torch.Tensor,
+    lengths: torch.Tensor,
+    values: torch.Tensor,
+    weights: Optional[torch.Tensor] = None,
+    permuted_lengths_sum: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """out_lengths[i] = lengths[permute[i]]; segment i of the output values (and weights) is segment permute[i] of the
+    input.  permute [P] need not have as many entries as lengths [L]: entries may repeat or be left out."""
+    dev = require_gpu(permute, lengths, values, weights)
+    if lengths.dim() != 1:
+        raise RuntimeError("permute_1D_sparse_data: lengths must be 1-D [L]")
+    if lengths.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"permute_1D_sparse_data: lengths dtype {lengths.dtype}")
+    L, P = lengths.numel(), permute.numel()
+    if L == 0 and P > 0:
+        raise RuntimeError(f"permute_1D_sparse_data: {P} permute entries into empty lengths")
+    perm = permute.to(torch.int32).contiguous().view(-1)
+    lengths_c = lengths.contiguous()
+    values_c = values.contiguous().view(-1)
+    weights_c = weights.contiguous().view(-1) if weights is not None else None
+    lib = _lib.load()
+    ws_bytes = lib.tbe_permute_1d_workspace_bytes(L, P)
+    if ws_bytes == 0:
+        raise RuntimeError(f"permute_1D_sparse_data: L={L} / P={P} segments do not fit the kernels' 32-bit segment count")
+    out_lengths = torch.empty(P, dtype=lengths.dtype, device=dev)
+    in_offsets = torch.empty(L + 1, dtype=torch.int64, device=dev)
+    out_offsets = torch.empty(P + 1, dtype=torch.int64, device=dev)
+    ws = workspace(ws_bytes, dev)
+    st = stream_ptr(dev)
+    with torch.cuda.device(dev):
+        check(
+            lib.tbe_permute_1d_lengths(ptr(perm), L, P, ptr(lengths_c), lengths_c.element_size(),
+                                       ptr(out_lengths), ptr(in_offsets), ptr(out_offsets), ptr(ws),
+                                       ws.numel(), st),
+            "tbe_permute_1d_lengths",
+        )
+        if permuted_lengths_sum is None:
+            # data-dependent output size: one D2H read, as permute_2D_sparse_data does
+            permuted_lengths_sum = int(out_offsets[-1].item())
+        out_values = torch.empty(permuted_lengths_sum, dtype=values.dtype, device=dev)
+        out_weights = (
+            torch.empty(permuted_lengths_sum, dtype=weights_c.dtype, device=dev)
+            if weights_c is not None else None
+        )
+        check(
+            lib.tbe_permute_1d_data(ptr(perm), P, ptr(in_offsets), ptr(out_offsets), ptr(values_c),
+                                    ptr(out_values), values_c.element_size(), ptr(weights_c),
+                                    ptr(out_weights),
+                                    weights_c.element_size() if weights_c is not None else 4, st),
+            "tbe_permute_1d_data",
+        )
+    return out_lengths, out_values, out_weights
+
+
+def expand_into_jagged_permute(permute: torch.Tensor, input_offset: torch.Tensor, output_offset: torch.Tensor,
+                               output_size: int) -> torch.Tensor:
+    """out[output_offset[i] + k] = input_offset[permute[i]] + k for k < output_offset[i + 1] - output_offset[i]."""
+    dev = require_gpu(permute, input_offset, output_offset)
+    P = permute.numel()
+    if permute.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"expand_into_jagged_permute: dtype {permute.dtype} not supported (int32/int64)")
+    for name, t, n in (("permute", permute, P), ("input_offset", input_offset, P + 1), ("output_offset", output_offset, P + 1)):
+        if t.dim() != 1 or t.numel() != n:
+            raise RuntimeError(f"expand_into_jagged_permute: {name} must be a vector of {n} entries, got {tuple(t.shape)}")
+        if t.dtype != permute.dtype:
+            raise RuntimeError(f"expand_into_jagged_permute: {name} is {t.dtype}, permute is {permute.dtype}")
+    if output_size < 0:
+        raise RuntimeError(f"expand_into_jagged_permute: output_size {output_size} < 0")
+    out = torch.empty(output_size, dtype=permute.dtype, device=dev)
+    if output_size == 0 or P == 0:
+        return out
+    perm, in_off, out_off = permute.contiguous(), input_offset.contiguous(), output_offset.contiguous()
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_expand_into_jagged_permute(ptr(perm), ptr(in_off), ptr(out_off), P, output_size,
+                                                         perm.element_size(), ptr(out), stream_ptr(dev)),
+              "tbe_expand_into_jagged_permute")
+    return out
 
 
 def block_bucketize_sparse_features(
@@ -295,5 +377,6 @@ _impl_lib.impl("jagged_2d_to_dense", jagged_2d_to_dense_forward)
 # permute_pooled_embs is the plain op (no gradient: autograd raises on it); _auto_grad is the differentiable one
 _impl_lib.impl("permute_pooled_embs", permute_pooled_embs)
 _impl_lib.impl("permute_pooled_embs_auto_grad", permute_pooled_embs)
-# permute_1D_sparse_data / expand_into_jagged_permute: schema only (variable-batch path,
-# SURVEY.md §2a "OUT OF SCOPE"); calling them raises from the dispatcher.
+# the variable-batch recat of KJTAllToAll (torchrec_amd/distributed/dist_data.py)
+_impl_lib.impl("permute_1D_sparse_data", permute_1D_sparse_data)
+_impl_lib.impl("expand_into_jagged_permute", expand_into_jagged_permute)

@@ -45,6 +45,7 @@ class _A2APooledReq(torch.autograd.Function):
         me = dist.get_rank(st["pg"])
         D_local = x.shape[1]
         st["D_local"] = D_local
+        st["shape"] = x.shape
         B_me = st["B_per_rank"][me]
         st["send_splits"] = [b * D_local for b in st["B_per_rank"]]
         st["recv_splits"] = [B_me * d for d in st["dims"]]
@@ -58,7 +59,7 @@ class _A2APooledReq(torch.autograd.Function):
     def backward(ctx, _):
         st = ctx.st
         st["bwork"].wait()
-        g = st["grecv"].view(-1, st["D_local"])
+        g = st["grecv"].view(st["shape"])  # (not view(-1, D_local): a rank may hold no columns at all)
         st["grecv"] = None
         return g, None
 
@@ -90,9 +91,13 @@ def alltoall_pooled(a2a_pooled_embs_tensor: Tensor, batch_size_per_rank: List[in
                     dim_sum_per_rank_tensor: Optional[Tensor] = None,
                     cumsum_dim_sum_per_rank_tensor: Optional[Tensor] = None,
                     group: Optional[dist.ProcessGroup] = None) -> Awaitable[Tensor]:
-    """[B_global, D_local_sum] -> Awaitable of [B_local, D_global_sum]."""
+    """[B_global, D_local_sum] -> Awaitable of [B_local, D_global_sum].  batch_size_per_rank[r] is rank r's local batch:
+    rows [sum(B[:r]), sum(B[:r + 1])) of the input go to rank r, entries may differ and may be 0."""
     if group is None:
         group = dist.distributed_c10d._get_default_group()
+    if a2a_pooled_embs_tensor.shape[0] != sum(batch_size_per_rank):
+        raise ValueError(f"alltoall_pooled: the pooled embeddings have {a2a_pooled_embs_tensor.shape[0]} rows, "
+                         f"batch_size_per_rank {list(batch_size_per_rank)} sums to {sum(batch_size_per_rank)}")
     if dist.get_world_size(group) <= 1:
         return NoWait(a2a_pooled_embs_tensor)
     dev = a2a_pooled_embs_tensor.device

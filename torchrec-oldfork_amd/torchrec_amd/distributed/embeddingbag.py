@@ -244,9 +244,13 @@ class SparseFeaturesDist:
     """What input_dist hands to compute (embedding_types.py `SparseFeatures`, after the a2a):
     ids in [src rank][local feature][sample] order + offsets for the local TBE."""
 
-    def __init__(self, values, offsets, weights, batch_size: int, dp=None) -> None:
+    def __init__(self, values, offsets, weights, batch_size: int, dp=None,
+                 batch_size_per_rank: Optional[List[int]] = None) -> None:
         self.values, self.offsets, self.weights, self.batch_size = values, offsets, weights, batch_size
         self.dp = dp  # (values, offsets, weights) of the data-parallel features, local batch
+        # variable-batch mode: every rank's local batch; the ids are then in [local piece][src rank][sample] order and
+        # `batch_size` is this rank's own entry
+        self.batch_size_per_rank = batch_size_per_rank
 
     def record_stream(self, stream) -> None:
         for t in (self.values, self.offsets, self.weights) + (tuple(self.dp) if self.dp is not None else ()):
@@ -441,6 +445,45 @@ class _ExchangeState:
         self._half_send_keepalive.append(send)
 
 
+class _VariableExchangeState(_ExchangeState):
+    """The pooled exchange when every rank brings its own batch size (sharding/vb_tw_sharding.py, vb_cw_sharding.py in the
+    reference).  The lookup ran once at batch sum(B_r) over [local piece][src rank][sample] ids, so the rows for
+    destination r are the contiguous block [sum(B[:r]), sum(B[:r + 1])) of its [sum(B_r), D_local] output: the all-to-all
+    sends B_r * D_local straight from that matrix and receives B_me * D_local_src per source.  The exchange kernels depend
+    on the RECEIVING rank's batch only: unpack / pack run with the layout of B_me, as in the fixed-batch exchange."""
+
+    def __init__(self, owner: "ShardedEmbeddingBagCollection", batch_size_per_rank: List[int]) -> None:
+        super().__init__(owner, batch_size_per_rank[owner._rank])
+        self.bpr = list(batch_size_per_rank)
+        self.send_splits = [b * owner._D_local for b in self.bpr]
+
+    def start_forward(self, emb: torch.Tensor, allow_static: bool = False) -> None:
+        o, lay = self.o, self.lay
+        self.recv_fwd = torch.empty(lay["recv_numel"], dtype=torch.float32, device=emb.device)
+        with label("## alltoall_fwd_single ##"):  # comm_ops.py:489
+            self.work = dist.all_to_all_single(self.recv_fwd, emb.reshape(-1), output_split_sizes=lay["recv_splits"],
+                                               input_split_sizes=self.send_splits, group=o._pg, async_op=True)
+
+    def start_backward(self, grad_out: torch.Tensor) -> None:
+        o, lay = self.o, self.lay
+        scale = 1.0 / o._world_size if GRADIENT_DIVISION else 1.0
+        send = torch.ops.tbe_hip.pooled_exchange_pack(
+            grad_out, lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"], lay["slab_offset"],
+            lay["slab_stride"], lay["recv_numel"], o._vec_ok, scale)
+        self.grad_recv = torch.empty(sum(self.send_splits), dtype=torch.float32, device=grad_out.device)
+        with label("## alltoall_bwd_single ##"):  # comm_ops.py:591, the forward's two split lists swapped
+            self.bwd_work = dist.all_to_all_single(self.grad_recv, send, output_split_sizes=self.send_splits,
+                                                   input_split_sizes=lay["recv_splits"], group=o._pg, async_op=True)
+        self._send_keepalive = send
+
+    def finish_backward(self) -> torch.Tensor:
+        with label("## alltoall_bwd_wait ##"):
+            self.bwd_work.wait()
+        self.bwd_work = None
+        self._send_keepalive = None
+        return self.grad_recv.view(sum(self.bpr), self.o._D_local)
+
+
 class _OutputAwaitable(LazyAwaitable):
     def __init__(self, fn: Callable[[], KeyedTensor]) -> None:
         super().__init__()
@@ -562,6 +605,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
         tbe_factory: Optional[Callable] = None,
         dp_tbe_factory: Optional[Callable] = None,
         rw_input_dist: Optional[str] = None,
+        variable_batch_size: bool = False,
     ) -> None:
         super().__init__()
         self._env = env
@@ -572,6 +616,9 @@ class ShardedEmbeddingBagCollection(nn.Module):
         W, me = env.world_size, env.rank
         self._world_size, self._rank = W, me
         self._exchange = W > 1 or (FORCE_EXCHANGE and env.process_group is not None)
+        # every rank may bring its own batch size to a step (KJTAllToAll(variable_batch_size=True) and
+        # sharding/vb_tw_sharding.py / vb_cw_sharding.py in the reference); a module that exchanges nothing has nothing to vary
+        self._variable_batch = bool(variable_batch_size) and self._exchange
         self._device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         # the exchanges' group: the environment's, or — for an RCCL group whose collective stream is not high-priority, i.e. a
         # launcher written for CUDA — a second communicator whose stream is, clear of the compute stream's hardware queue
@@ -604,6 +651,10 @@ class ShardedEmbeddingBagCollection(nn.Module):
             if ps.sharding_type == ShardingType.DATA_PARALLEL.value:
                 kind.append(-2)
             elif ps.sharding_type == ShardingType.ROW_WISE.value:
+                if self._variable_batch:
+                    raise NotImplementedError(
+                        f"table {c.name}: row_wise sharding in a variable_batch_size collection (the reference has no "
+                        "variable-batch row-wise sharding either); shard it table-wise or column-wise, or replicate it")
                 kind.append(-1)
             elif ps.sharding_type == ShardingType.TABLE_WISE.value:
                 kind.append(int(ps.ranks[0]))
@@ -750,10 +801,13 @@ class ShardedEmbeddingBagCollection(nn.Module):
         self._row_windows = None
         self._rw_mode_active = "windows"
         if self._local_tables:
+            # variable-batch mode: ONE lookup over the local pieces at batch sum(B_r), ids in [piece][src rank][sample] order,
+            # plain [sum(B_r), D_local] output; otherwise one feature per (src rank, piece) and the all-to-all-ready layout
+            n_src = 1 if self._variable_batch else W
             self._emb_module = factory(
                 [(max(lt.local_rows, 0), lt.cols, lt.compute_kernel) for lt in self._local_tables],
-                ftm_local * W, pooling_type_to_pooling_mode(self._local_tables[ftm_local[0]].cfg.pooling), dev, fused_params)
-            if self._exchange:
+                ftm_local * n_src, pooling_type_to_pooling_mode(self._local_tables[ftm_local[0]].cfg.pooling), dev, fused_params)
+            if self._exchange and not self._variable_batch:
                 self._emb_module.set_a2a_output_layout(W)
             self._row_windows = (win_first * W, win_global * W) if self._has_rw else None
             self._rw_mode_active = "windows"
@@ -761,7 +815,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
                 self._emb_module.set_row_windows(*self._row_windows)
             local_pooling = [pooling_type_to_pooling_mode(self._local_tables[i].cfg.pooling) for i in ftm_local]
             if len(set(local_pooling)) > 1:
-                self._emb_module.set_feature_pooling(local_pooling * W)
+                self._emb_module.set_feature_pooling(local_pooling * n_src)
             self._init_parameters()
             self._optim = EmbeddingFusedOptimizer(self._emb_module, [lt.cfg.name for lt in self._local_tables],
                                                   key_prefix="embedding_bags.", wrap=self._wrap,
@@ -814,6 +868,9 @@ class ShardedEmbeddingBagCollection(nn.Module):
         no eager launch in a stretch of the step where the host is what the GPU waits for.  One step at a time uses the
         buffers, which the explicit step guarantees (also with the next lookup prefetched: its all-to-all is ordered
         behind this step's unpack)."""
+        if batch_size is not None and self._variable_batch:
+            raise NotImplementedError("set_graph_exchange: a variable_batch_size collection has no fixed batch size to "
+                                      "build persistent exchange buffers for")
         if batch_size is None or not self._exchange:
             self._static_exchange = None
             return None
@@ -842,6 +899,9 @@ class ShardedEmbeddingBagCollection(nn.Module):
         """compute_explicit() then exchanges the pooled embeddings (and their gradients) as two half-batches
         (ExplicitLookupStep.finish_half / start_backward_half): the owner of the step interleaves the halves' dense work
         with the other half's exchange."""
+        if on and self._variable_batch:
+            raise NotImplementedError("set_half_batch_exchange(True): a variable_batch_size collection exchanges whole "
+                                      "batches only (the halves of unequal batches do not line up across ranks)")
         self.half_batch_exchange = bool(on)
 
     def _alias_output_buffer(self, B: int) -> torch.Tensor:
@@ -1226,7 +1286,46 @@ class ShardedEmbeddingBagCollection(nn.Module):
 
         return _InputDistAwaitable(finish)
 
+    def _input_dist_variable(self, features: KeyedJaggedTensor) -> Awaitable[SparseFeaturesDist]:
+        """Input dist when the ranks' batch sizes differ (dist_data.py variable_batch_exchange: batch sizes, lengths, one
+        D2H read of the id counts, ids and weights, recat with expand_into_jagged_permute + permute_1D_sparse_data).  The
+        pieces travel in `_send_feature_order`, a column-wise feature once per shard as always; a local batch of 0 sends
+        nothing and still takes part in every collective."""
+        from .dist_data import variable_batch_exchange
+
+        B = features.stride()
+        order, _ = self._send_perm(features.keys())
+        weighted = self._is_weighted and features.weights_or_none() is not None
+        if B > 0 and order:
+            sent = features.permute(order, None)
+            lengths, values, lpk = sent.lengths(), sent.values(), sent.length_per_key()
+            weights = sent.weights() if weighted else None
+        else:
+            lengths, values, lpk = features.lengths()[:0], features.values()[:0], [0] * len(order)
+            weights = features.weights()[:0] if weighted else None
+        val_in, k = [], 0
+        for n in self._send_feats_per_rank:
+            val_in.append(sum(lpk[k:k + n]))
+            k += n
+        dp_in = None
+        if self._dp_module is not None:
+            if B > 0:
+                dp_in = self._dp_inputs(features)
+            else:
+                dp_in = (features.values()[:0], torch.zeros(1, dtype=torch.int64, device=features.values().device),
+                         features.weights()[:0] if weighted else None)
+        bpr, finish_exchange = variable_batch_exchange(self._pg, self._send_feats_per_rank, val_in, lengths, values, weights, B)
+
+        def finish() -> SparseFeaturesDist:
+            l2, v2, w2 = finish_exchange()
+            offsets = torch.ops.fbgemm.asynchronous_complete_cumsum(l2).long()
+            return SparseFeaturesDist(v2, offsets, w2, B, dp_in, batch_size_per_rank=bpr)
+
+        return _InputDistAwaitable(finish)
+
     def input_dist(self, features: KeyedJaggedTensor) -> Awaitable[SparseFeaturesDist]:
+        if self._variable_batch:
+            return self._input_dist_variable(features)
         W, B = self._world_size, features.stride()
         dp_in = self._dp_inputs(features)
         mode = self._pick_rw_mode(features)
@@ -1339,9 +1438,9 @@ class ShardedEmbeddingBagCollection(nn.Module):
             with label("## tbe_lookup ##"):
                 emb = self._emb_module(dist_input.values, dist_input.offsets, dist_input.weights)
         else:
-            emb = torch.zeros((self._world_size * B, 0), dtype=torch.float32, device=self._device,
-                              requires_grad=True)
-        state = _ExchangeState(self, B)
+            rows = sum(dist_input.batch_size_per_rank) if self._variable_batch else self._world_size * B
+            emb = torch.zeros((rows, 0), dtype=torch.float32, device=self._device, requires_grad=True)
+        state = _VariableExchangeState(self, dist_input.batch_size_per_rank) if self._variable_batch else _ExchangeState(self, B)
         recv = _ExchangeReq.apply(emb, state)
         return _OutputAwaitable(
             lambda: KeyedTensor(keys, lpe, self._dp_fill(_ExchangeWait.apply(recv, state), dist_input)))
@@ -1350,6 +1449,8 @@ class ShardedEmbeddingBagCollection(nn.Module):
         """Whether compute_explicit() can serve a batch of this (per-rank) size: a fused module and an output buffer of
         exactly that batch — the configuration of the HIP-graph train step (with or without the exchange)."""
         buf = self._output_buffer
+        if self._variable_batch:  # no fixed batch: the explicit step and everything that hangs off it is refused, as below
+            return False
         if self._has_cw:
             # column-wise tables: refused (and with it the half-batch exchange, the static graph exchange and the prefetched
             # lookup, which all hang off the explicit step); callers fall back to compute_and_output_dist + autograd
@@ -1374,7 +1475,9 @@ class ShardedEmbeddingBagCollection(nn.Module):
         One rank without exchange, replicated tables or row cache; SUM-pooled fp32 DEVICE tables of one dim; no per-sample
         weights; exactly one id per bag.  Everything is known on the host without a sync."""
         m = self._emb_module
-        if self._has_cw:  # a feature's row is spread over several tables of the lookup: the consumer cannot gather it
+        if self._has_cw or self._variable_batch:
+            # a feature's row is spread over several tables of the lookup: the consumer cannot gather it (a variable-batch
+            # collection exchanges, which rules the deferred lookup out anyway)
             return False
         if (self._exchange or self._world_size != 1 or self._dp_module is not None or m is None
                 or not hasattr(m, "lookup_deferred") or self._is_weighted
@@ -1568,8 +1671,10 @@ class EmbeddingBagCollectionSharder:
     (torchrec/distributed/embeddingbag.py:489-515)."""
 
     def __init__(self, fused_params: Optional[Dict[str, Any]] = None, tbe_factory: Optional[Callable] = None,
-                 dp_tbe_factory: Optional[Callable] = None, rw_input_dist: Optional[str] = None) -> None:
+                 dp_tbe_factory: Optional[Callable] = None, rw_input_dist: Optional[str] = None,
+                 variable_batch_size: bool = False) -> None:
         self.fused_params = fused_params
+        self.variable_batch_size = variable_batch_size  # every rank may bring its own batch size (ShardedEmbeddingBagCollection)
         self.tbe_factory = tbe_factory
         self.dp_tbe_factory = dp_tbe_factory
         self.rw_input_dist = rw_input_dist  # "auto" | "windows" | "bucketize" (ShardedEmbeddingBagCollection)
@@ -1577,7 +1682,7 @@ class EmbeddingBagCollectionSharder:
     def shard(self, module: EmbeddingBagCollection, params: Dict[str, ParameterSharding], env: ShardingEnv,
               device: Optional[torch.device] = None) -> ShardedEmbeddingBagCollection:
         return ShardedEmbeddingBagCollection(module, params, env, self.fused_params, device, self.tbe_factory,
-                                             self.dp_tbe_factory, self.rw_input_dist)
+                                             self.dp_tbe_factory, self.rw_input_dist, self.variable_batch_size)
 
     @property
     def module_type(self):

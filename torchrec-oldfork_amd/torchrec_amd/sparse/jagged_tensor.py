@@ -189,7 +189,7 @@ class KeyedJaggedTensor:
                 # the one unavoidable D2H read for data-dependent lengths
                 # (jagged_tensor.py:502-509 does the same)
                 self._length_per_key = (
-                    self.lengths().view(len(self._keys), -1).sum(dim=1).cpu().tolist())
+                    self.lengths().view(len(self._keys), self._stride).sum(dim=1).cpu().tolist())
         return self._length_per_key
 
     def offset_per_key(self) -> List[int]:
@@ -244,7 +244,7 @@ class KeyedJaggedTensor:
         if trained:
             w = torch.arange(w.numel(), dtype=torch.int64, device=w.device)
         lengths, values, weights = torch.ops.fbgemm.permute_2D_sparse_data(
-            indices_tensor, self.lengths().view(len(self._keys), -1), self._values, w, sum(new_lpk))
+            indices_tensor, self.lengths().view(len(self._keys), self._stride), self._values, w, sum(new_lpk))
         if trained:
             weights = self._weights.view(-1).index_select(0, weights)
         return KeyedJaggedTensor(
