@@ -439,12 +439,18 @@ int tbe_backward_apply_ex_f16w(const uint64_t* feat_weights, const int32_t* feat
  * the staging slots for this batch; tbe_cache_writeback_staging copies them home after backward.
  * Results are identical to an uncached table.
  *
- *   tags [slots] int64  cached-row key (tab_key_base[t] + local row), -1 = empty
- *   lru  [slots] int32  iteration of last use, -1 = never; `iteration` must increase per prefetch
+ *   tags [slots] int64  cached-row key (tab_key_base[t] + local row), -1 = empty; must be 16-B aligned (a set's tags
+ *                       are loaded four at a time).  Slots s*64 .. s*64+63 are the ways of set s, and a key lives
+ *                       only in the set  (((key * 0x9E3779B97F4A7C15) mod 2^64) >> 32) % num_sets.
+ *                       Within a set a missed key takes the way with the smallest (lru, way number) among the ways
+ *                       not used by this iteration; with none left the row goes to a staging slot.
+ *   lru  [slots] int32  iteration of last use, -1 = never; `iteration` must increase per prefetch and stay
+ *                       in [0, 2^25): the victim order packs (lru + 1) * 64 + way into 32 bits
  *   rows [(slots + staging_cap) * row_stride] float;  state: same slots, rowwise optimizer state or NULL
  *   staging_keys [staging_cap] int64;  counters [8] int32: 0 staging rows of this batch, 1 hits,
  *   2 misses, 3 evictions (write-backs), 4 unique cached rows of this batch, 5 misses of this batch
- *   tab_* : the cached tables (num_tables entries; tab_key_base has num_tables+1 = prefix sum of rows)
+ *   tab_* : the cached tables (num_tables entries; tab_key_base has num_tables+1 = prefix sum of rows);
+ *           tab_D[t] <= row_stride, and only columns 0 .. tab_D[t] of a slot that holds a row of table t are touched
  * tbe_cache_prefetch: feat_cached_table[f] = index into tab_* or -1 (ids of such features are copied
  *   unchanged); key_bits = bits of the total cached rows; staging_cap must be >= N.
  * tbe_cache_flush: every valid slot -> host table; invalidate != 0 also empties the cache.

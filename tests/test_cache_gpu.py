@@ -201,3 +201,85 @@ def test_cache_stress_random_shapes(seed):
     assert st["evictions"] > 0 and st["hits"] > 0
     for x, y in zip(cached.split_embedding_weights(), plain.split_embedding_weights()):
         torch.testing.assert_close(x.cpu(), y.cpu(), rtol=1e-4, atol=1e-5)
+
+
+@pytest.mark.parametrize("optname", ["sgd", "rowwise_adagrad"])
+def test_cached_tables_with_odd_dim(optname):
+    """D = 13: every row moves through the scalar branch of the cache's row copy (tests/test_cache_abi_gpu.py pins that
+    branch byte for byte; this is what a module user reaches).  One set: eviction and staging every step."""
+    from fbgemm_gpu.split_embedding_configs import EmbOptimType
+    from fbgemm_gpu.split_table_batched_embeddings_ops import EmbeddingLocation as L
+
+    rng = np.random.default_rng(21)
+    rows, dims = [700, 90, 300], [13, 13, 13]
+    ftm = [0, 1, 2, 0]
+    locs = [L.MANAGED_CACHING, L.DEVICE, L.MANAGED_CACHING]
+    opt = EmbOptimType.EXACT_SGD if optname == "sgd" else EmbOptimType.EXACT_ROWWISE_ADAGRAD
+    ocode = oracle.OPT_EXACT_SGD if optname == "sgd" else oracle.OPT_EXACT_ROWWISE_ADAGRAD
+    cached, plain = _modules(rows, dims, locs, opt, ftm=ftm, cache_sets=1)
+    assert cached._cache is not None and cached._cache.D == 13 and plain._cache is None
+    tabs = oracle.Tables(rows, dims, ftm)
+    wc, wp = cached.split_embedding_weights(), plain.split_embedding_weights()
+    for t in range(len(rows)):
+        init = rng.standard_normal((rows[t], dims[t])).astype(np.float32)
+        tabs.weights[t][...] = init
+        wc[t].copy_(torch.from_numpy(init))
+        wp[t].copy_(torch.from_numpy(init))
+    s0 = [np.zeros(r, dtype=np.float32) for r in rows]
+    for step in range(5):
+        indices, offsets, _ = make_inputs(rng, rows, 64, 3, ftm=ftm, zipf=(step % 2 == 0))
+        out_c = cached(to_dev(indices), to_dev(offsets))
+        out_p = plain(to_dev(indices), to_dev(offsets))
+        ref, _ = oracle.tbe_forward(tabs, indices, offsets)
+        torch.testing.assert_close(out_c, out_p, rtol=1e-5, atol=1e-5)
+        np.testing.assert_allclose(out_c.detach().cpu().numpy(), ref, rtol=1e-5, atol=1e-5)
+        grad = rng.standard_normal(tuple(out_c.shape)).astype(np.float32)
+        out_c.backward(to_dev(grad))
+        out_p.backward(to_dev(grad))
+        oracle.tbe_backward(tabs, indices, offsets, grad, ocode, 0.1, eps=1e-3, state0=s0)
+    st = cached.cache_stats()
+    assert st["evictions"] > 0 and st["hits"] > 0 and st["misses"] > 0, st
+    cached.flush()
+    torch.cuda.synchronize()
+    host = [cached._table_view(cached._flat_weights, t).cpu().numpy().copy() for t in range(len(rows))]
+    for t in range(len(rows)):
+        np.testing.assert_allclose(host[t], plain.split_embedding_weights()[t].cpu().numpy(), rtol=1e-5, atol=1e-5)
+        np.testing.assert_allclose(host[t], tabs.weights[t], rtol=3e-5, atol=3e-5)
+    if optname == "rowwise_adagrad":
+        for t, (sc, sp) in enumerate(zip(cached.split_optimizer_states(), plain.split_optimizer_states())):
+            np.testing.assert_allclose(sc[0].cpu().numpy(), sp[0].cpu().numpy(), rtol=1e-5, atol=1e-5)
+            np.testing.assert_allclose(sc[0].cpu().numpy(), s0[t], rtol=3e-5, atol=3e-5)
+
+
+def test_cached_table_behind_an_odd_sized_managed_table():
+    """D = 12 cached rows behind a MANAGED table of 7 x 3 = 21 floats in the same host buffer.  Where the cached table
+    starts is read from the module's own pointer table, not assumed: the module pads every table to the 16-B grid
+    (_init_tables), so the base is ON the grid although 21 floats precede it, and the cache's vector copy applies.  A
+    host base 4 B off the grid is therefore reachable through the C ABI only; tests/test_cache_abi_gpu.py (geometry G3)
+    pins it there."""
+    from fbgemm_gpu.split_embedding_configs import EmbOptimType
+    from fbgemm_gpu.split_table_batched_embeddings_ops import EmbeddingLocation as L
+
+    rng = np.random.default_rng(33)
+    rows, dims = [7, 400], [3, 12]
+    cached, plain = _modules(rows, dims, [L.MANAGED, L.MANAGED_CACHING], EmbOptimType.EXACT_SGD, cache_sets=1)
+    for t in range(2):
+        init = rng.standard_normal((rows[t], dims[t])).astype(np.float32)
+        cached.split_embedding_weights()[t].copy_(torch.from_numpy(init))
+        plain.split_embedding_weights()[t].copy_(torch.from_numpy(init))
+    for step in range(4):
+        indices, offsets, _ = make_inputs(rng, rows, 80, 3)
+        a, b = cached(to_dev(indices), to_dev(offsets)), plain(to_dev(indices), to_dev(offsets))
+        torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-5)
+        g = to_dev(rng.standard_normal(tuple(a.shape)).astype(np.float32))
+        a.backward(g)
+        b.backward(g)
+        if step == 0:
+            cached._cache.desc()
+            base = int(cached._cache._tab_ptrs[0].cpu()[0])
+            flat = cached._flat_weights("uvm").data_ptr()
+            assert (base - flat) // 4 >= 21, "the cached table does not lie behind the 21 floats of the MANAGED table"
+            assert base % 16 == 0 and (flat + 4 * 21) % 16 == 4, (base % 16, flat % 16)
+    assert cached.cache_stats()["evictions"] > 0
+    for x, y in zip(cached.split_embedding_weights(), plain.split_embedding_weights()):
+        torch.testing.assert_close(x.cpu(), y.cpu(), rtol=1e-5, atol=1e-5)

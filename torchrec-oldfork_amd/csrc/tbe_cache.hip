@@ -317,6 +317,9 @@ static int to_dev(const tbe_cache_desc* d, CacheDev* c) {
   TBE_REQUIRE(d->num_sets > 0 && d->row_stride > 0 && d->staging_cap >= 0, "tbe_cache: bad geometry");
   TBE_REQUIRE(static_cast<int64_t>(d->num_sets) * kWays + d->staging_cap < (1ll << 31), "tbe_cache: too many slots");
   TBE_REQUIRE(d->state == nullptr || d->tab_state != nullptr, "tbe_cache: state cache without host state");
+  // cache_lookup_kernel loads four tags of a set as two longlong2; lru words are claimed by 32-bit atomics
+  TBE_REQUIRE((reinterpret_cast<uintptr_t>(d->tags) & 15) == 0, "tbe_cache: tags must be 16-B aligned");
+  TBE_REQUIRE((reinterpret_cast<uintptr_t>(d->lru) & 3) == 0, "tbe_cache: lru must be 4-B aligned");
   c->tags = d->tags;
   c->lru = d->lru;
   c->rows = d->rows;
@@ -357,8 +360,22 @@ extern "C" int tbe_cache_prefetch(const tbe_cache_desc* desc, const int32_t* fea
   TBE_REQUIRE(N < kSortMaxPairs, "tbe_cache_prefetch: N = %lld ids in one call; the limit is 2^29 - 1 (the pair sort's count field)",
               static_cast<long long>(N));
   TBE_REQUIRE(key_bits >= 1 && key_bits <= 62, "tbe_cache_prefetch: key_bits=%d", key_bits);
-  TBE_REQUIRE(iteration >= 0, "tbe_cache_prefetch: iteration < 0");
+  // the victim order packs (last use + 1) << 6 | way into 32 bits
+  TBE_REQUIRE(iteration >= 0 && iteration < (1 << 25), "tbe_cache_prefetch: iteration=%d outside [0, 2^25)", iteration);
   TBE_REQUIRE(c.staging_cap >= N, "tbe_cache_prefetch: staging_cap (%d) must be >= N (%lld)", c.staging_cap, (long long)N);
+  const bool work = N > 0 && B > 0;
+  PrefetchWorkspace w;
+  if (work) {  // every argument is checked before the first byte changes
+    TBE_REQUIRE(feat_cached_table && feat_rows && indices && offsets && remapped_indices && workspace,
+                "tbe_cache_prefetch: null pointer");
+    TBE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "tbe_cache_prefetch: workspace must be 256-B aligned");
+    carve_prefetch(workspace, N, key_bits, &w);
+    if (w.total > workspace_bytes) {
+      set_error("tbe_cache_prefetch: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+      return TBE_ERR_WORKSPACE;
+    }
+    TBE_REQUIRE((static_cast<size_t>(F) + 1) * sizeof(int64_t) <= 60000, "tbe_cache_prefetch: too many features (%d)", F);
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   // staging count + per-batch miss counter restart; hit / miss / eviction totals accumulate
   if (hipMemsetAsync(c.counters + kCntStaging, 0, sizeof(int32_t), st) != hipSuccess ||
@@ -366,19 +383,9 @@ extern "C" int tbe_cache_prefetch(const tbe_cache_desc* desc, const int32_t* fea
     set_error("tbe_cache_prefetch: hipMemsetAsync failed");
     return TBE_ERR_LAUNCH;
   }
-  if (N == 0 || B == 0) return TBE_OK;
-  TBE_REQUIRE(feat_cached_table && feat_rows && indices && offsets && remapped_indices && workspace,
-              "tbe_cache_prefetch: null pointer");
-  TBE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "tbe_cache_prefetch: workspace must be 256-B aligned");
-  PrefetchWorkspace w;
-  carve_prefetch(workspace, N, key_bits, &w);
-  if (w.total > workspace_bytes) {
-    set_error("tbe_cache_prefetch: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-    return TBE_ERR_WORKSPACE;
-  }
+  if (!work) return TBE_OK;
   const uint64_t sentinel = (1ull << key_bits) - 1ull;
   const size_t lds = (static_cast<size_t>(F) + 1) * sizeof(int64_t);
-  TBE_REQUIRE(lds <= 60000, "tbe_cache_prefetch: too many features (%d)", F);
   const unsigned gridN = static_cast<unsigned>((N + 255) / 256);
   hipLaunchKernelGGL(cache_linearize_kernel, dim3(std::min<unsigned>(gridN, 256 * 16)), dim3(256), lds, st, indices, offsets,
                      feat_cached_table, feat_rows, feat_window, c.tab_key_base, F, B, N, sentinel, w.k0, w.p0, remapped_indices);
