@@ -628,28 +628,42 @@ def test_full_size_criteo_26_tables_properties(B):
 
 
 @pytest.mark.parametrize("optname", ["EXACT_SGD", "EXACT_ROWWISE_ADAGRAD"])
-@pytest.mark.parametrize("case", [CASES[0], CASES[3], CASES[5]], ids=["0", "3", "5"])
-def test_lookup_without_autograd_is_the_autograd_path(case, optname):
+@pytest.mark.parametrize("case,defer_sort", [(CASES[0], False), (CASES[3], False), (CASES[5], False),
+                                             (CASES[0], True), (CASES[2], True)],
+                         ids=["0", "3", "5", "0-deferred", "2-deferred"])
+def test_lookup_without_autograd_is_the_autograd_path(case, defer_sort, optname):
     """lookup_no_autograd / backward_no_autograd (what the explicit train step of models/dlrm.py drives) against the
     module's own autograd path: same output, same weights and optimizer state after two steps, bit for bit — for the
-    fused module and for the dense-gradient module, into a caller's buffer too."""
-    def run(explicit, dense):
+    fused module and for the dense-gradient module, into a caller's buffer too.
+    The `deferred` cases (without and with per-sample weights, which widen the sort's payload): a lookup made with
+    defer_sort=True, whose side-stream sort is started afterwards through the record (what the sharded steps do),
+    against the explicit lookup that starts its sort itself."""
+    def run(explicit, dense, defer=False):
         rng = np.random.default_rng(11)
         if dense:
             mod, _ = build_pair(case["rows"], case["dims"], case["ftm"], case["pooling"], None, rng, dense=True)
         else:
             mod, _ = build_pair(case["rows"], case["dims"], case["ftm"], case["pooling"], _opt(optname), rng, learning_rate=0.05)
+        if defer_sort:
+            mod.overlap_backward_sort = True  # whatever the environment says: the sort under test runs on the side stream
         outs, grads_w = [], []
         for _ in range(2):
             indices, offsets, psw = make_inputs(rng, case["rows"], case["B"], case["max_len"], case["ftm"],
                                                 case["fixed_len"], case["weighted"])
             i, o, w = to_dev(indices), to_dev(offsets), to_dev(psw)
-            if explicit:
+            if defer:
+                out, rec = mod.lookup_no_autograd(i, o, w, defer_sort=True)
+                assert rec.prepared is None, "the deferred sort started inside the lookup"
+            elif explicit:
                 out, rec = mod.lookup_no_autograd(i, o, w)
+                assert not defer_sort or rec.prepared is not None
             else:
                 out = mod(i, o, w)
             grad = to_dev(rng.standard_normal(tuple(out.shape)).astype(np.float32))
             outs.append(out.detach().clone())
+            if defer:
+                assert mod.start_backward_sort(rec) and rec.prepared is not None
+                assert not mod.start_backward_sort(rec), "a record's sort starts once"
             if explicit:
                 g = mod.backward_no_autograd(rec, grad)
                 if dense:
@@ -667,7 +681,9 @@ def test_lookup_without_autograd_is_the_autograd_path(case, optname):
     for dense in (False, True):
         if dense and optname != "EXACT_SGD":
             continue
-        a, b = run(False, dense), run(True, dense)
+        # the explicit lookup (deferred in the `deferred` cases) against autograd, or against the undeferred explicit lookup
+        a = run(explicit=defer_sort, dense=dense)
+        b = run(explicit=True, dense=dense, defer=defer_sort)
         for x, y in zip(a[0] + a[1] + a[3], b[0] + b[1] + b[3]):
             assert torch.equal(x, y)
         for sa, sb in zip(a[2], b[2]):

@@ -42,8 +42,8 @@ def wrap(owner, name, label=None, static=False):
 base = tbe.SplitTableBatchedEmbeddingBagsCodegen.__mro__[1]
 for n in ("_real_layout", "_get_layout", "_pooled_layout", "_forward_impl", "_prepare_backward", "_ensure_pinned"):
     wrap(base, n)
-for cls in (tbe._FusedLookupInto, tbe._DenseLookupInto, tbe._FusedLookup, tbe._DenseLookup, eb._ExchangeReq, eb._ExchangeWait,
-            hip_graph._Replay, dlrm._FusedDotInteraction):
+for cls in (tbe._FusedLookup, tbe._DenseLookup, eb._ExchangeReq, eb._ExchangeWait, hip_graph._Replay,
+            dlrm._FusedDotInteraction):
     wrap(cls, "forward", static=True)
     wrap(cls, "backward", static=True)
 for n in ("input_dist", "compute_and_output_dist", "_dp_inputs"):

@@ -99,41 +99,41 @@ __global__ __launch_bounds__(256) void bwd_linearize_nobag_kernel(
 }
 
 template <typename KeyT, typename PayT>
-static int run_backward(BwdArgs a, const BwdWorkspace& w, int32_t max_D, hipStream_t st, int phase) {
-  ProfileSpan total_span(phase == kPhasePrepare ? -1 : TBE_PROFILE_BWD_TOTAL, st);
+static int prepare(const BwdArgs& a, const BwdWorkspace& w, hipStream_t st) {
+  ProfileSpan prep_span(TBE_PROFILE_BWD_PREPARE, st);
   KeyT* kin = static_cast<KeyT*>(w.keys_in);
   KeyT* kout = static_cast<KeyT*>(w.keys_out);
   PayT* pin = static_cast<PayT*>(w.pay_in);
   PayT* pout = static_cast<PayT*>(w.pay_out);
-  if (phase & kPhasePrepare) {
-    ProfileSpan prep_span(TBE_PROFILE_BWD_PREPARE, st);
-    {
-      // 16-B units; both buffers start 256-B aligned and the carver pads each to the next 256-B boundary
-      const int64_t n_keys16 = a.pooling_mode == TBE_POOL_NONE ? 0 : (a.N * static_cast<int64_t>(sizeof(KeyT)) + 15) / 16;
-      const int64_t n_state16 = (static_cast<int64_t>(radix_state_words(a.N, a.key_bits, sizeof(KeyT) + sizeof(PayT))) + 3) / 4;
-      const unsigned grid = static_cast<unsigned>(std::min<int64_t>((std::max(n_keys16, n_state16) + 255) / 256, 2048));
-      hipLaunchKernelGGL(bwd_fill_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<uint4*>(kin), n_keys16,
-                         reinterpret_cast<uint4*>(w.sort.state), n_state16);
+  {
+    // 16-B units; both buffers start 256-B aligned and the carver pads each to the next 256-B boundary
+    const int64_t n_keys16 = a.pooling_mode == TBE_POOL_NONE ? 0 : (a.N * static_cast<int64_t>(sizeof(KeyT)) + 15) / 16;
+    const int64_t n_state16 = (static_cast<int64_t>(radix_state_words(a.N, a.key_bits, sizeof(KeyT) + sizeof(PayT))) + 3) / 4;
+    const unsigned grid = static_cast<unsigned>(std::min<int64_t>((std::max(n_keys16, n_state16) + 255) / 256, 2048));
+    hipLaunchKernelGGL(bwd_fill_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<uint4*>(kin), n_keys16,
+                       reinterpret_cast<uint4*>(w.sort.state), n_state16);
+  }
+  if (a.pooling_mode == TBE_POOL_NONE) {
+    if constexpr (sizeof(PayT) == 8) {
+      const size_t lds = (static_cast<size_t>(a.F) + 1) * sizeof(int64_t);
+      const unsigned grid = static_cast<unsigned>(std::min<int64_t>((a.N + 255) / 256, 256 * 16));
+      hipLaunchKernelGGL((bwd_linearize_nobag_kernel<KeyT>), dim3(grid), dim3(256), lds, st, a.indices, a.offsets,
+                         a.feat_rows, a.feat_row_base, a.F, a.B, a.N, a.key_bits, kin, pin, a.bounds_errors);
     }
-    if (a.pooling_mode == TBE_POOL_NONE) {
-      if constexpr (sizeof(PayT) == 8) {
-        const size_t lds = (static_cast<size_t>(a.F) + 1) * sizeof(int64_t);
-        const unsigned grid = static_cast<unsigned>(std::min<int64_t>((a.N + 255) / 256, 256 * 16));
-        hipLaunchKernelGGL((bwd_linearize_nobag_kernel<KeyT>), dim3(grid), dim3(256), lds, st, a.indices, a.offsets,
-                           a.feat_rows, a.feat_row_base, a.F, a.B, a.N, a.key_bits, kin, pin, a.bounds_errors);
-      }
-    } else {
-      const int64_t nbags = static_cast<int64_t>(a.F) * a.B;
-      const unsigned grid = static_cast<unsigned>((nbags + 255) / 256);
-      hipLaunchKernelGGL((bwd_linearize_pooled_kernel<KeyT, PayT>), dim3(grid), dim3(256), 0, st, a.indices, a.offsets,
-                         a.feat_rows, a.feat_row_base, a.feat_window, a.F, a.B, a.N, a.key_bits, kin, pin, a.bounds_errors);
-    }
-    TBE_CHECK_LAUNCH("tbe_backward linearize");
-    const int where = radix_sort_pairs<KeyT, PayT>(kin, kout, pin, pout, a.N, a.key_bits, w.sort, st, kSortStateZeroed);
-    if (where < 0) return where;
-  }  // prepare
-  if (!(phase & kPhaseApply)) return TBE_OK;
-  return run_apply<float, KeyT, PayT>(a, max_D, st);
+  } else {
+    const int64_t nbags = static_cast<int64_t>(a.F) * a.B;
+    const unsigned grid = static_cast<unsigned>((nbags + 255) / 256);
+    hipLaunchKernelGGL((bwd_linearize_pooled_kernel<KeyT, PayT>), dim3(grid), dim3(256), 0, st, a.indices, a.offsets,
+                       a.feat_rows, a.feat_row_base, a.feat_window, a.F, a.B, a.N, a.key_bits, kin, pin, a.bounds_errors);
+  }
+  TBE_CHECK_LAUNCH("tbe_backward linearize");
+  const int where = radix_sort_pairs<KeyT, PayT>(kin, kout, pin, pout, a.N, a.key_bits, w.sort, st, kSortStateZeroed);
+  return where < 0 ? where : TBE_OK;
+}
+
+int run_prepare(const BwdArgs& a, const BwdWorkspace& w, bool wide_payload, hipStream_t st) {
+  if (a.key_bits > 32) return wide_payload ? prepare<uint64_t, uint64_t>(a, w, st) : prepare<uint64_t, uint32_t>(a, w, st);
+  return wide_payload ? prepare<uint32_t, uint64_t>(a, w, st) : prepare<uint32_t, uint32_t>(a, w, st);
 }
 
 }  // namespace tbe
@@ -151,31 +151,6 @@ extern "C" size_t tbe_backward_workspace_bytes(int64_t N, int32_t F, int32_t B, 
   return w.total;
 }
 
-static int backward_entry(
-    const uint64_t* feat_weights, const int32_t* feat_D, const int64_t* feat_out_offset,
-    const int64_t* feat_rows, const int64_t* feat_row_base, const uint64_t* feat_state0,
-    const uint64_t* feat_state1, int32_t F, int32_t B, int32_t max_D,
-    int32_t key_bits, const int64_t* indices, int64_t N, const int64_t* offsets,
-    const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
-    int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
-    size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window, void* stream, int phase,
-    bool ex = false, const tbe_optimizer_ext* ext = nullptr) {
-  static const char* const kWho[8] = {"", "tbe_backward_prepare", "tbe_backward_apply_f32", "tbe_backward_fused_f32",
-                                      "", "", "tbe_backward_apply_ex_f32", "tbe_backward_fused_ex_f32"};
-  BwdArgs a;
-  BwdWorkspace w;
-  bool wide = false, done = false;
-  const int rc = bwd_setup(kWho[(phase & 3) + (ex ? 4 : 0)], feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0,
-                           feat_state1, F, B, max_D, key_bits, indices, N, offsets, per_sample_weights, pooling_mode,
-                           feat_pooling, grad_out, grad_row_stride, opt, flags, workspace, workspace_bytes, bounds_errors,
-                           feat_window, phase, &a, &w, &wide, &done, ex, ext);
-  if (rc != TBE_OK || done) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (key_bits > 32)
-    return wide ? run_backward<uint64_t, uint64_t>(a, w, max_D, st, phase) : run_backward<uint64_t, uint32_t>(a, w, max_D, st, phase);
-  return wide ? run_backward<uint32_t, uint64_t>(a, w, max_D, st, phase) : run_backward<uint32_t, uint32_t>(a, w, max_D, st, phase);
-}
-
 extern "C" int tbe_backward_fused_f32(
     const uint64_t* feat_weights, const int32_t* feat_D, const int64_t* feat_out_offset,
     const int64_t* feat_rows, const int64_t* feat_row_base, const uint64_t* feat_state0,
@@ -184,10 +159,15 @@ extern "C" int tbe_backward_fused_f32(
     const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
     int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
     size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window, void* stream) {
-  return backward_entry(feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F,
-                        B, max_D, key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out,
-                        grad_row_stride, opt, flags, workspace, workspace_bytes, bounds_errors, feat_window, stream,
-                        kPhasePrepare | kPhaseApply);
+  BwdCall c{feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F, B, max_D,
+            key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out, grad_row_stride,
+            opt, flags, workspace, workspace_bytes};
+  c.stream = stream;
+  c.who = "tbe_backward_fused_f32";
+  c.phase = kPhasePrepare | kPhaseApply;
+  c.bounds_errors = bounds_errors;
+  c.feat_window = feat_window;
+  return backward_entry<float>(c);
 }
 
 extern "C" int tbe_backward_prepare(const int64_t* feat_rows, const int64_t* feat_row_base, int32_t F, int32_t B,
@@ -195,10 +175,26 @@ extern "C" int tbe_backward_prepare(const int64_t* feat_rows, const int64_t* fea
                                     const int64_t* offsets, int32_t pooling_mode, int32_t flags, void* workspace,
                                     size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window,
                                     void* stream) {
-  tbe_optimizer_args opt{};
-  return backward_entry(nullptr, nullptr, nullptr, feat_rows, feat_row_base, nullptr, nullptr, F, B, max_D, key_bits,
-                        indices, N, offsets, nullptr, pooling_mode, nullptr, nullptr, 1, opt, flags & TBE_FLAG_WEIGHTED, workspace,
-                        workspace_bytes, bounds_errors, feat_window, stream, kPhasePrepare);
+  BwdCall c{};  // no tables, no gradient, no optimizer (bwd_setup gives this phase a stride and an optimizer that validate)
+  c.feat_rows = feat_rows;
+  c.feat_row_base = feat_row_base;
+  c.F = F;
+  c.B = B;
+  c.max_D = max_D;
+  c.key_bits = key_bits;
+  c.indices = indices;
+  c.N = N;
+  c.offsets = offsets;
+  c.pooling_mode = pooling_mode;
+  c.flags = flags & TBE_FLAG_WEIGHTED;
+  c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes;
+  c.stream = stream;
+  c.who = "tbe_backward_prepare";
+  c.phase = kPhasePrepare;
+  c.bounds_errors = bounds_errors;
+  c.feat_window = feat_window;
+  return backward_entry<float>(c);
 }
 
 extern "C" int tbe_backward_apply_f32(
@@ -209,9 +205,13 @@ extern "C" int tbe_backward_apply_f32(
     const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
     int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
     size_t workspace_bytes, void* stream) {
-  return backward_entry(feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F,
-                        B, max_D, key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out,
-                        grad_row_stride, opt, flags, workspace, workspace_bytes, nullptr, nullptr, stream, kPhaseApply);
+  BwdCall c{feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F, B, max_D,
+            key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out, grad_row_stride,
+            opt, flags, workspace, workspace_bytes};
+  c.stream = stream;
+  c.who = "tbe_backward_apply_f32";
+  c.phase = kPhaseApply;
+  return backward_entry<float>(c);
 }
 
 // The twins that also take the row-norm optimizer family and gradient clipping (include/tbe_hip.h); with ext == NULL and
@@ -225,10 +225,17 @@ extern "C" int tbe_backward_fused_ex_f32(
     int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
     size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window, const tbe_optimizer_ext* ext,
     void* stream) {
-  return backward_entry(feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F,
-                        B, max_D, key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out,
-                        grad_row_stride, opt, flags, workspace, workspace_bytes, bounds_errors, feat_window, stream,
-                        kPhasePrepare | kPhaseApply, true, ext);
+  BwdCall c{feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F, B, max_D,
+            key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out, grad_row_stride,
+            opt, flags, workspace, workspace_bytes};
+  c.stream = stream;
+  c.who = "tbe_backward_fused_ex_f32";
+  c.phase = kPhasePrepare | kPhaseApply;
+  c.bounds_errors = bounds_errors;
+  c.feat_window = feat_window;
+  c.ex = true;
+  c.ext = ext;
+  return backward_entry<float>(c);
 }
 
 extern "C" int tbe_backward_apply_ex_f32(
@@ -239,10 +246,15 @@ extern "C" int tbe_backward_apply_ex_f32(
     const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
     int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
     size_t workspace_bytes, const tbe_optimizer_ext* ext, void* stream) {
-  return backward_entry(feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F,
-                        B, max_D, key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out,
-                        grad_row_stride, opt, flags, workspace, workspace_bytes, nullptr, nullptr, stream, kPhaseApply,
-                        true, ext);
+  BwdCall c{feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F, B, max_D,
+            key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out, grad_row_stride,
+            opt, flags, workspace, workspace_bytes};
+  c.stream = stream;
+  c.who = "tbe_backward_apply_ex_f32";
+  c.phase = kPhaseApply;
+  c.ex = true;
+  c.ext = ext;
+  return backward_entry<float>(c);
 }
 
 // ---- the pair sort as a public entry (tests, micro-benchmarks) ---------------------------------------

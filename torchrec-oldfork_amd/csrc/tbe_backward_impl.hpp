@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.hpp"
 #include "radix_sort.hpp"
@@ -913,58 +914,87 @@ static int run_apply(const BwdArgs& a, int32_t max_D, hipStream_t st) {
   return launch_update<WT, KeyT, PayT, 64, 8>(a, st);
 }
 
-// Argument validation and workspace carving shared by every backward entry point (`who` names it in
-// error messages).  Nothing is launched.  *done is set when the call has nothing to do.
-static int bwd_setup(
-    const char* who, const uint64_t* feat_weights, const int32_t* feat_D, const int64_t* feat_out_offset,
-    const int64_t* feat_rows, const int64_t* feat_row_base, const uint64_t* feat_state0,
-    const uint64_t* feat_state1, int32_t F, int32_t B, int32_t max_D,
-    int32_t key_bits, const int64_t* indices, int64_t N, const int64_t* offsets,
-    const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
-    int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
-    size_t workspace_bytes, int32_t* bounds_errors, const int64_t* feat_window, int phase,
-    BwdArgs* args, BwdWorkspace* ws, bool* wide_payload, bool* done, bool ex = false,
-    const tbe_optimizer_ext* ext = nullptr) {
-  // ex: called by a tbe_backward_*_ex_* entry, which alone accepts the row-norm family and `ext`
+// One backward call as the ABI passes it: the wrappers of include/tbe_hip.h fill this and hand it to backward_entry.
+// They aggregate-initialise the common arguments only and assign everything after them by name.
+struct BwdCall {
+  // the arguments every apply / fused entry takes, in the ABI's order
+  const uint64_t* feat_weights;
+  const int32_t* feat_D;
+  const int64_t* feat_out_offset;
+  const int64_t* feat_rows;
+  const int64_t* feat_row_base;
+  const uint64_t* feat_state0;
+  const uint64_t* feat_state1;
+  int32_t F, B, max_D, key_bits;
+  const int64_t* indices;
+  int64_t N;
+  const int64_t* offsets;
+  const float* per_sample_weights;
+  int32_t pooling_mode;
+  const int32_t* feat_pooling;
+  const float* grad_out;
+  int64_t grad_row_stride;
+  tbe_optimizer_args opt;
+  int32_t flags;
+  void* workspace;
+  size_t workspace_bytes;
+  // what only some entries take, in the order the ABI appends it
+  int32_t* bounds_errors = nullptr;           // fused, prepare
+  const int64_t* feat_window = nullptr;       // fused, prepare
+  int32_t rounding = TBE_ROUND_NEAREST_EVEN;  // _f16w
+  uint64_t seed = 0;                          // _f16w
+  const tbe_optimizer_ext* ext = nullptr;     // _ex
+  void* stream = nullptr;
+  // not arguments: which entry this is
+  const char* who = nullptr;  // its name, for error messages
+  int phase = 0;              // kPhasePrepare | kPhaseApply
+  bool ex = false;            // a tbe_backward_*_ex_* entry, which alone accepts the row-norm family and `ext`
+};
+
+// Argument validation and workspace carving shared by every backward entry point.  Nothing is launched.  *done is set
+// when the call has nothing to do.
+static int bwd_setup(BwdCall c, BwdArgs* args, BwdWorkspace* ws, bool* wide_payload, bool* done) {
+  const char* const who = c.who;
   *done = false;
-  TBE_REQUIRE(F > 0 && B >= 0 && N >= 0, "%s: bad sizes", who);
-  if (phase == kPhasePrepare) {  // gradient / optimizer arguments are not used by this phase
-    grad_row_stride = 1;
-    opt.optimizer = TBE_OPT_EXACT_SGD;
+  TBE_REQUIRE(c.F > 0 && c.B >= 0 && c.N >= 0, "%s: bad sizes", who);
+  if (c.phase == kPhasePrepare) {  // gradient / optimizer arguments are not used by this phase
+    c.grad_row_stride = 1;
+    c.opt.optimizer = TBE_OPT_EXACT_SGD;
   }
-  TBE_REQUIRE(max_D > 0 && max_D <= 2048, "%s: max_D=%d outside (0, 2048]", who, max_D);
-  TBE_REQUIRE(key_bits >= 1 && key_bits <= 64, "%s: key_bits=%d", who, key_bits);
-  TBE_REQUIRE(pooling_mode == TBE_POOL_SUM || pooling_mode == TBE_POOL_MEAN || pooling_mode == TBE_POOL_NONE,
-              "%s: pooling_mode %d", who, pooling_mode);
-  TBE_REQUIRE(static_cast<int64_t>(F) * B < (1ll << 32), "%s: F*B must be < 2^32", who);
+  TBE_REQUIRE(c.max_D > 0 && c.max_D <= 2048, "%s: max_D=%d outside (0, 2048]", who, c.max_D);
+  TBE_REQUIRE(c.key_bits >= 1 && c.key_bits <= 64, "%s: key_bits=%d", who, c.key_bits);
+  TBE_REQUIRE(c.pooling_mode == TBE_POOL_SUM || c.pooling_mode == TBE_POOL_MEAN || c.pooling_mode == TBE_POOL_NONE,
+              "%s: pooling_mode %d", who, c.pooling_mode);
+  TBE_REQUIRE(static_cast<int64_t>(c.F) * c.B < (1ll << 32), "%s: F*B must be < 2^32", who);
   // the pair sort's histogram words hold {pass tag | count} with a 29-bit count (radix_sort.hpp)
-  TBE_REQUIRE(N < kSortMaxPairs, "%s: N = %lld ids in one call; the limit is 2^29 - 1 (split the batch)", who,
-              static_cast<long long>(N));
-  TBE_REQUIRE(grad_row_stride > 0, "%s: grad_row_stride <= 0", who);
-  if (phase == (kPhasePrepare | kPhaseApply) && per_sample_weights != nullptr) flags |= TBE_FLAG_WEIGHTED;
-  TBE_REQUIRE(per_sample_weights == nullptr || (flags & TBE_FLAG_WEIGHTED) != 0,
+  TBE_REQUIRE(c.N < kSortMaxPairs, "%s: N = %lld ids in one call; the limit is 2^29 - 1 (split the batch)", who,
+              static_cast<long long>(c.N));
+  TBE_REQUIRE(c.grad_row_stride > 0, "%s: grad_row_stride <= 0", who);
+  if (c.phase == (kPhasePrepare | kPhaseApply) && c.per_sample_weights != nullptr) c.flags |= TBE_FLAG_WEIGHTED;
+  TBE_REQUIRE(c.per_sample_weights == nullptr || (c.flags & TBE_FLAG_WEIGHTED) != 0,
               "%s: per_sample_weights given but TBE_FLAG_WEIGHTED not set (it must be set in "
               "both tbe_backward_prepare and the apply call)", who);
+  const tbe_optimizer_args& opt = c.opt;
   switch (opt.optimizer) {
     case TBE_OPT_EXACT_SGD:
       break;
     case TBE_OPT_EXACT_ROWWISE_ADAGRAD:
     case TBE_OPT_EXACT_ADAGRAD:
     case TBE_OPT_DENSE_GRAD:
-      TBE_REQUIRE(feat_state0 != nullptr, "%s: optimizer %d needs feat_state0", who, opt.optimizer);
+      TBE_REQUIRE(c.feat_state0 != nullptr, "%s: optimizer %d needs feat_state0", who, opt.optimizer);
       break;
     case TBE_OPT_ADAM:
-      TBE_REQUIRE(feat_state0 != nullptr && feat_state1 != nullptr, "%s: ADAM needs two states", who);
+      TBE_REQUIRE(c.feat_state0 != nullptr && c.feat_state1 != nullptr, "%s: ADAM needs two states", who);
       TBE_REQUIRE(opt.iteration >= 1, "%s: ADAM iteration must be >= 1", who);
       break;
     case TBE_OPT_LAMB:
     case TBE_OPT_PARTIAL_ROWWISE_ADAM:
     case TBE_OPT_PARTIAL_ROWWISE_LAMB:
     case TBE_OPT_LARS_SGD:
-      if (ex) {
-        TBE_REQUIRE(feat_state0 != nullptr, "%s: optimizer %d needs feat_state0", who, opt.optimizer);
-        TBE_REQUIRE(opt.optimizer == TBE_OPT_LARS_SGD || feat_state1 != nullptr, "%s: optimizer %d needs feat_state1", who,
-                    opt.optimizer);
+      if (c.ex) {
+        TBE_REQUIRE(c.feat_state0 != nullptr, "%s: optimizer %d needs feat_state0", who, opt.optimizer);
+        TBE_REQUIRE(opt.optimizer == TBE_OPT_LARS_SGD || c.feat_state1 != nullptr, "%s: optimizer %d needs feat_state1",
+                    who, opt.optimizer);
         TBE_REQUIRE(opt.optimizer != TBE_OPT_PARTIAL_ROWWISE_ADAM || opt.iteration >= 1,
                     "%s: PARTIAL_ROWWISE_ADAM iteration must be >= 1", who);
         break;
@@ -974,46 +1004,47 @@ static int bwd_setup(
       set_error("%s: unknown optimizer %d", who, opt.optimizer);
       return TBE_ERR_UNSUPPORTED;
   }
+  const tbe_optimizer_ext* const ext = c.ext;
   const bool clip = ext != nullptr && ext->gradient_clipping != 0;
   if (clip)
     TBE_REQUIRE(ext->max_gradient >= 0.f && ext->max_gradient <= 3.402823466e38f,
                 "%s: gradient clipping needs a finite max_gradient >= 0", who);
-  if (N == 0 || B == 0) {
+  if (c.N == 0 || c.B == 0) {
     *done = true;
     return TBE_OK;
   }
-  TBE_REQUIRE(feat_rows && feat_row_base && indices && offsets && workspace, "%s: null pointer", who);
-  if (phase & kPhaseApply)
-    TBE_REQUIRE(feat_weights && feat_D && feat_out_offset && grad_out, "%s: null pointer", who);
-  TBE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-B aligned", who);
+  TBE_REQUIRE(c.feat_rows && c.feat_row_base && c.indices && c.offsets && c.workspace, "%s: null pointer", who);
+  if (c.phase & kPhaseApply)
+    TBE_REQUIRE(c.feat_weights && c.feat_D && c.feat_out_offset && c.grad_out, "%s: null pointer", who);
+  TBE_REQUIRE((reinterpret_cast<uintptr_t>(c.workspace) & 255) == 0, "%s: workspace must be 256-B aligned", who);
   BwdWorkspace& w = *ws;
-  int rc = carve(workspace, N, max_D, key_bits, &w);
+  int rc = carve(c.workspace, c.N, c.max_D, c.key_bits, &w);
   if (rc != TBE_OK) return rc;
-  if (w.total > workspace_bytes) {
-    set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, w.total);
+  if (w.total > c.workspace_bytes) {
+    set_error("%s: workspace too small (%zu < %zu)", who, c.workspace_bytes, w.total);
     return TBE_ERR_WORKSPACE;
   }
   BwdArgs a{};
-  a.feat_weights = feat_weights;
-  a.feat_D = feat_D;
-  a.feat_out_offset = feat_out_offset;
-  a.feat_rows = feat_rows;
-  a.feat_row_base = feat_row_base;
-  a.feat_window = feat_window;
-  a.feat_pooling = feat_pooling;
-  a.feat_state0 = feat_state0;
-  a.feat_state1 = feat_state1;
-  a.indices = indices;
-  a.offsets = offsets;
-  a.psw = per_sample_weights;
-  a.grad_out = grad_out;
-  a.grad_stride = grad_row_stride;
-  a.N = N;
-  a.F = F;
-  a.B = B;
-  a.pooling_mode = pooling_mode;
-  a.key_bits = key_bits;
-  a.C = pick_chunk(N);
+  a.feat_weights = c.feat_weights;
+  a.feat_D = c.feat_D;
+  a.feat_out_offset = c.feat_out_offset;
+  a.feat_rows = c.feat_rows;
+  a.feat_row_base = c.feat_row_base;
+  a.feat_window = c.feat_window;
+  a.feat_pooling = c.feat_pooling;
+  a.feat_state0 = c.feat_state0;
+  a.feat_state1 = c.feat_state1;
+  a.indices = c.indices;
+  a.offsets = c.offsets;
+  a.psw = c.per_sample_weights;
+  a.grad_out = c.grad_out;
+  a.grad_stride = c.grad_row_stride;
+  a.N = c.N;
+  a.F = c.F;
+  a.B = c.B;
+  a.pooling_mode = c.pooling_mode;
+  a.key_bits = c.key_bits;
+  a.C = pick_chunk(c.N);
   a.opt = opt;
   a.bias1 = 1.f;
   a.bias2 = 1.f;
@@ -1028,21 +1059,57 @@ static int bwd_setup(
   a.partial_last = w.partial_last;
   a.origin_list = w.origin_list;
   a.origin_count = w.origin_count;
-  a.max_D_pad = (max_D + 3) / 4 * 4;
-  a.fast_D = ((flags & TBE_FLAG_UNIFORM_ALIGNED) && max_D % 4 == 0 && grad_row_stride % 4 == 0 &&
-              (reinterpret_cast<uintptr_t>(grad_out) & 15) == 0) ? max_D : 0;
-  a.bounds_errors = bounds_errors;
-  a.unique_rows = (phase & kPhaseApply) ? profile_unique_rows_counter() : nullptr;
+  a.max_D_pad = (c.max_D + 3) / 4 * 4;
+  a.fast_D = ((c.flags & TBE_FLAG_UNIFORM_ALIGNED) && c.max_D % 4 == 0 && c.grad_row_stride % 4 == 0 &&
+              (reinterpret_cast<uintptr_t>(c.grad_out) & 15) == 0) ? c.max_D : 0;
+  a.bounds_errors = c.bounds_errors;
+  a.unique_rows = (c.phase & kPhaseApply) ? profile_unique_rows_counter() : nullptr;
   a.rounding = TBE_ROUND_NEAREST_EVEN;
   a.round_hash = 0;
   // the sort ping-pongs between the two buffer pairs: an odd number of passes ends in the second
-  const bool in_second = (radix_passes(key_bits) & 1) != 0;
+  const bool in_second = (radix_passes(c.key_bits) & 1) != 0;
   a.keys_sorted = in_second ? w.keys_out : w.keys_in;
   a.payload_sorted = in_second ? w.pay_out : w.pay_in;
   *args = a;
   // payload width: the bag number alone unless positions are needed (per-sample weights, unpooled rows)
-  *wide_payload = pooling_mode == TBE_POOL_NONE || (flags & TBE_FLAG_WEIGHTED) != 0;
+  *wide_payload = c.pooling_mode == TBE_POOL_NONE || (c.flags & TBE_FLAG_WEIGHTED) != 0;
   return TBE_OK;
+}
+
+// The gradient-independent phase (fill + linearize + sort of the row keys into the workspace): never touches the tables,
+// so it is defined once, in tbe_backward.hip.
+int run_prepare(const BwdArgs& a, const BwdWorkspace& w, bool wide_payload, hipStream_t st);
+
+// Every backward entry point: validate, carve once, sort if the phase mask says so, update + fix-up on tables of WT.
+template <typename WT>
+static int backward_entry(const BwdCall& c) {
+  if constexpr (std::is_same_v<WT, _Float16>) {
+    TBE_REQUIRE(c.rounding == TBE_ROUND_NEAREST_EVEN || c.rounding == TBE_ROUND_STOCHASTIC, "%s: rounding %d", c.who,
+                c.rounding);
+    if (c.opt.optimizer == TBE_OPT_DENSE_GRAD) {
+      set_error("%s: TBE_OPT_DENSE_GRAD is not supported with FP16 tables (dense parameters are float)", c.who);
+      return TBE_ERR_UNSUPPORTED;
+    }
+  }
+  BwdArgs a;
+  BwdWorkspace w;
+  bool wide = false, done = false;
+  const int rc = bwd_setup(c, &a, &w, &wide, &done);
+  if (rc != TBE_OK || done) return rc;
+  if constexpr (std::is_same_v<WT, _Float16>) {
+    a.rounding = c.rounding;
+    a.round_hash = call_hash(c.seed, c.opt.iteration);
+  }
+  hipStream_t st = static_cast<hipStream_t>(c.stream);
+  ProfileSpan total_span(c.phase == kPhasePrepare ? -1 : TBE_PROFILE_BWD_TOTAL, st);
+  if (c.phase & kPhasePrepare) {
+    const int prc = run_prepare(a, w, wide, st);
+    if (prc != TBE_OK) return prc;
+  }
+  if (!(c.phase & kPhaseApply)) return TBE_OK;
+  if (c.key_bits > 32)
+    return wide ? run_apply<WT, uint64_t, uint64_t>(a, c.max_D, st) : run_apply<WT, uint64_t, uint32_t>(a, c.max_D, st);
+  return wide ? run_apply<WT, uint32_t, uint64_t>(a, c.max_D, st) : run_apply<WT, uint32_t, uint32_t>(a, c.max_D, st);
 }
 
 }  // namespace tbe

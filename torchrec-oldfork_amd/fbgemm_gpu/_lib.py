@@ -58,8 +58,30 @@ class CacheDesc(ctypes.Structure):
     ]
 
 
+# The arguments every tbe_backward_{fused,apply}[_ex]_{f32,f16w} entry starts with (feat_weights ... workspace_bytes); each
+# entry adds, in this order: bounds_errors + feat_window (fused), rounding + seed (_f16w), ext (_ex), and the stream.
+_BWD_COMMON = ([c_void_p] * 7 + [c_i32] * 4 + [c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64,
+                                                OptimizerArgs, c_i32, c_void_p, c_size])
+_BWD_ENTRIES = {
+    f"tbe_backward_{kind}{ex}{wt}": (ctypes.c_int, _BWD_COMMON + fused_tail + f16_tail + ext_tail + [c_void_p])
+    for kind, fused_tail in (("fused", [c_void_p, c_void_p]), ("apply", []))
+    for ex, ext_tail in (("", []), ("_ex", [ctypes.POINTER(OptimizerExt)]))
+    for wt, f16_tail in (("_f32", []), ("_f16w", [c_i32, c_u64]))
+}
+# the entries that exist once per table element type: one argument list each
+_PER_TABLE_TYPE = {
+    "tbe_forward_pooled": [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64,
+                           c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p],
+    "tbe_forward_nobag": [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
+                          c_void_p],
+    "tbe_backward_indice_weights": [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64,
+                                    c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p],
+}
+
 # name -> (restype, argtypes); must list every symbol of include/tbe_hip.h
 SIGNATURES = {
+    **_BWD_ENTRIES,
+    **{f"{name}{wt}": (ctypes.c_int, args) for name, args in _PER_TABLE_TYPE.items() for wt in ("_f32", "_f16w")},
     "tbe_last_error": (ctypes.c_char_p, []),
     "tbe_abi_version": (c_i32, []),
     "tbe_fault_status": (ctypes.c_int, [ctypes.POINTER(c_i64)]),
@@ -68,23 +90,7 @@ SIGNATURES = {
     "tbe_profile_enable": (ctypes.c_int, [c_i32]),
     "tbe_profile_read": (ctypes.c_int, [c_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64)]),
     "tbe_profile_read_rows": (ctypes.c_int, [ctypes.POINTER(c_i64)]),
-    "tbe_forward_pooled_f32": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64,
-         c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p],
-    ),
-    "tbe_forward_nobag_f32": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
-         c_void_p],
-    ),
     "tbe_backward_workspace_bytes": (c_size, [c_i64, c_i32, c_i32, c_i32, c_i32]),
-    "tbe_backward_fused_f32": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
-         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
-         c_i32, c_void_p, c_size, c_void_p, c_void_p, c_void_p],
-    ),
     "tbe_backward_prepare": (
         ctypes.c_int,
         [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_i32, c_i32, c_void_p,
@@ -96,68 +102,6 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_size, c_void_p],
     ),
     "tbe_debug_sort_timeouts": (ctypes.c_int, [ctypes.POINTER(c_i64)]),
-    "tbe_backward_apply_f32": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
-         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
-         c_i32, c_void_p, c_size, c_void_p],
-    ),
-    "tbe_forward_pooled_f16w": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64,
-         c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p],
-    ),
-    "tbe_forward_nobag_f16w": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
-         c_void_p],
-    ),
-    "tbe_backward_fused_f16w": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
-         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
-         c_i32, c_void_p, c_size, c_void_p, c_void_p, c_i32, c_u64, c_void_p],
-    ),
-    "tbe_backward_apply_f16w": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
-         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
-         c_i32, c_void_p, c_size, c_i32, c_u64, c_void_p],
-    ),
-    "tbe_backward_fused_ex_f32": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
-         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
-         c_i32, c_void_p, c_size, c_void_p, c_void_p, ctypes.POINTER(OptimizerExt), c_void_p],
-    ),
-    "tbe_backward_apply_ex_f32": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
-         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
-         c_i32, c_void_p, c_size, ctypes.POINTER(OptimizerExt), c_void_p],
-    ),
-    "tbe_backward_fused_ex_f16w": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
-         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
-         c_i32, c_void_p, c_size, c_void_p, c_void_p, c_i32, c_u64, ctypes.POINTER(OptimizerExt), c_void_p],
-    ),
-    "tbe_backward_apply_ex_f16w": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32,
-         c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, OptimizerArgs,
-         c_i32, c_void_p, c_size, c_i32, c_u64, ctypes.POINTER(OptimizerExt), c_void_p],
-    ),
-    "tbe_backward_indice_weights_f32": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64,
-         c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p],
-    ),
-    "tbe_backward_indice_weights_f16w": (
-        ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64,
-         c_void_p, c_i32, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p],
-    ),
     "tbe_cache_prefetch_workspace_bytes": (c_size, [c_i64, c_i32]),
     "tbe_cache_prefetch": (
         ctypes.c_int,

@@ -378,6 +378,12 @@ class _TBEBase(nn.Module):
         self._row_windows = None  # see set_row_windows
         self._feature_pooling = None  # see set_feature_pooling
         self._side_stream = None
+        self._pinned_key = None  # see _ensure_pinned
+        self._ctor_pooling_mode = self.pooling_mode  # what set_feature_pooling(None) restores
+        self._a2a_world, self._a2a_cache = 0, {}  # see set_a2a_output_layout
+        self.bounds_check_mode = BoundsCheckMode.WARNING
+        self._fatal_seen = 0  # bounds errors BoundsCheckMode.FATAL has raised for already
+        self._rounding, self._sr_seed = 0, 0  # FP16 tables only: TBE_ROUND_* and the seed of the random bits
         # sort the batch's row keys on a side stream during forward (see _prepare_backward)
         # "auto": only for lookups small enough to leave CUs idle (measured on MI355X: at 1.7 M ids the
         # side-stream sort steals bandwidth from the GEMMs, -2 %; at 213 K ids it hides, +4 %)
@@ -445,7 +451,7 @@ class _TBEBase(nn.Module):
         names = [n for n, b in self._buffers.items() if n.endswith("_uvm") and b is not None and b.numel() > 0
                  and b.device.type == "cpu"]
         key = tuple(self._buffers[n].data_ptr() for n in names)
-        if key == getattr(self, "_pinned_key", None):
+        if key == self._pinned_key:
             return
         for n in names:
             if not self._buffers[n].is_pinned():
@@ -497,13 +503,11 @@ class _TBEBase(nn.Module):
         listed as SUM are not divided.  None restores the uniform mode given at construction."""
         if modes is None:
             self._feature_pooling = None
-            self.pooling_mode = getattr(self, "_ctor_pooling_mode", self.pooling_mode)
+            self.pooling_mode = self._ctor_pooling_mode
             return
         modes = [PoolingMode(int(m)) for m in modes]
         if len(modes) != self.F or any(m == PoolingMode.NONE for m in modes) or self.pooling_mode == PoolingMode.NONE:
             raise ValueError("set_feature_pooling: one of SUM / MEAN per feature, on a pooled module")
-        if not hasattr(self, "_ctor_pooling_mode"):
-            self._ctor_pooling_mode = self.pooling_mode
         if all(m == modes[0] for m in modes):
             self._feature_pooling, self.pooling_mode = None, modes[0]
             return
@@ -530,7 +534,7 @@ class _TBEBase(nn.Module):
     def _errors_ptr(self) -> Optional[int]:
         """The counter the kernels increment, or NULL for BoundsCheckMode.IGNORE / NONE (an out-of-range id still
         contributes a zero row and is never dereferenced: this build has no unchecked mode)."""
-        if getattr(self, "bounds_check_mode", BoundsCheckMode.WARNING) in (BoundsCheckMode.IGNORE, BoundsCheckMode.NONE):
+        if self.bounds_check_mode in (BoundsCheckMode.IGNORE, BoundsCheckMode.NONE):
             return None
         return ptr(self._errors())
 
@@ -545,13 +549,12 @@ class _TBEBase(nn.Module):
     def _enforce_bounds_check_mode(self) -> None:
         """BoundsCheckMode.FATAL: raise as soon as a lookup has seen a bad id (costs a host sync per call);
         WARNING: warn once per new batch of errors is left to the caller reading bounds_check_errors()."""
-        if getattr(self, "bounds_check_mode", BoundsCheckMode.WARNING) != BoundsCheckMode.FATAL:
+        if self.bounds_check_mode != BoundsCheckMode.FATAL:
             return
         n = self.bounds_check_errors()
-        seen = getattr(self, "_fatal_seen", 0)
-        if n > seen:
-            self._fatal_seen = n
-            raise RuntimeError(f"BoundsCheckMode.FATAL: {n - seen} out-of-range indices or malformed bags in this lookup")
+        if n > self._fatal_seen:
+            new, self._fatal_seen = n - self._fatal_seen, n
+            raise RuntimeError(f"BoundsCheckMode.FATAL: {new} out-of-range indices or malformed bags in this lookup")
 
     # -- launches ---------------------------------------------------------------------------
     def _check_inputs(self, indices, offsets, per_sample_weights) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], int]:
@@ -576,6 +579,18 @@ class _TBEBase(nn.Module):
                 raise RuntimeError("per_sample_weights must have one entry per index")
         return indices, offsets, per_sample_weights, B
 
+    def _begin_lookup(self, indices, offsets, per_sample_weights, training: bool, explicit: bool = False):
+        """What every lookup starts with: the input checks, the ids' trip through the row cache, and whether the sort of
+        this lookup's backward goes on the side stream (see _prepare_backward).  `explicit`: a lookup_no_autograd call,
+        which has a threshold of its own.  Returns (indices, offsets, per_sample_weights, B, overlap)."""
+        indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
+        if self._cache is not None:
+            indices = self._cache.prefetch(self._real_layout(), indices, offsets, B, training)
+        mode = self.overlap_backward_sort
+        max_ids = self.overlap_backward_sort_max_ids_explicit if explicit else self.overlap_backward_sort_max_ids
+        overlap = training and (mode in (True, "1") or (mode == "auto" and indices.numel() <= max_ids))
+        return indices, offsets, per_sample_weights, B, overlap
+
     # -- output layout --------------------------------------------------------------------
     def set_a2a_output_layout(self, world_size: int) -> None:
         """Pooled output (and the gradient read by backward) laid out all-to-all-ready:
@@ -591,7 +606,7 @@ class _TBEBase(nn.Module):
     def _pooled_layout(self, B: int):
         """(feat_out_offset tensor, row_stride, out_shape) for batch size B."""
         lay = self._get_layout()
-        W = getattr(self, "_a2a_world", 0)
+        W = self._a2a_world
         if not W:
             return lay.feat_out_offset, self.total_D, (B, self.total_D)
         hit = self._a2a_cache.get(B)
@@ -647,25 +662,39 @@ class _TBEBase(nn.Module):
             )
         return out
 
-    def _prepare_or_defer(self, ctx, indices, offsets, B: int, weighted: bool):
-        """The side-stream sort of this lookup's backward: started now, or — with `defer_backward_sort` — when the
-        owner calls launch_deferred_backward_sort() (a model that knows its schedule puts the sort next to its
-        MFMA-bound GEMMs instead of next to HBM-bound kernels: DESIGN.md §3)."""
-        if not getattr(self, "defer_backward_sort", False):
-            return self._prepare_backward(indices, offsets, B, weighted)
-        self._deferred_sort = (ctx, indices, offsets, B, weighted)
-        return None
+    def lookup_no_autograd(self, indices: torch.Tensor, offsets: torch.Tensor,
+                           per_sample_weights: Optional[torch.Tensor] = None, into=None, defer_sort: bool = False):
+        """The training forward without an autograd node: returns (output, LookupRecord).  `into` = (buffer,
+        per-feature offsets, row stride) as in forward_into.  The caller owes exactly one
+        backward_no_autograd(record, grad) per call.  The side-stream sort of the backward is already running, unless
+        `defer_sort` left it to start_backward_sort(record): a caller that knows its schedule puts the sort's launches
+        behind whatever the GPU is waiting for."""
+        indices, offsets, per_sample_weights, B, overlap = self._begin_lookup(indices, offsets, per_sample_weights, True,
+                                                                              explicit=True)
+        rec = LookupRecord(indices, offsets, per_sample_weights, B, (into[1], int(into[2])) if into is not None else None)
+        out = self._forward_impl(indices, offsets, per_sample_weights, B, into=into)
+        rec.sort_pending = overlap
+        if not defer_sort:
+            self.start_backward_sort(rec)
+        self._enforce_bounds_check_mode()
+        return out, rec
 
-    def launch_deferred_backward_sort(self) -> bool:
-        """Starts the deferred sort of the latest forward (if any) on the side stream, ordered after the work
-        enqueued so far on the current stream.  Without this call the backward sorts inline (fused call)."""
-        d = getattr(self, "_deferred_sort", None)
-        if d is None:
+    def start_backward_sort(self, rec: "LookupRecord") -> bool:
+        """Starts the sort that lookup_no_autograd(..., defer_sort=True) left pending on `rec` (if it did), on the side
+        stream, ordered after the work enqueued so far on the current stream.  Without this call the backward sorts
+        inline (fused call)."""
+        if not rec.sort_pending:
             return False
-        self._deferred_sort = None
-        ctx, indices, offsets, B, weighted = d
-        ctx.prepared = self._prepare_backward(indices, offsets, B, weighted)
+        rec.sort_pending = False
+        rec.prepared = self._prepare_backward(rec.indices, rec.offsets, rec.B, rec.per_sample_weights is not None)
         return True
+
+    def _backward_workspace(self, N: int, B: int) -> torch.Tensor:
+        nbytes = _lib.load().tbe_backward_workspace_bytes(N, self.F, B, self.max_D, self.key_bits)
+        if nbytes == 0:
+            raise RuntimeError(f"TBE backward: {N} ids in one call is beyond the limit of 2^29 - 1 (include/tbe_hip.h): "
+                               "split the batch")
+        return workspace(nbytes, self.current_device)
 
     def _prepare_backward(self, indices, offsets, B: int, weighted: bool = False):
         """Enqueues the gradient-independent half of backward (linearize + stable sort of the row
@@ -678,11 +707,7 @@ class _TBEBase(nn.Module):
         dev = self.current_device
         lib = _lib.load()
         with torch.cuda.device(dev):
-            nbytes = lib.tbe_backward_workspace_bytes(N, self.F, B, self.max_D, self.key_bits)
-            if nbytes == 0:
-                raise RuntimeError(f"TBE backward: {N} ids in one call is beyond the limit of 2^29 - 1 (include/tbe_hip.h): "
-                                   "split the batch")
-            ws = workspace(nbytes, dev)
+            ws = self._backward_workspace(N, B)
             side = self._side_stream
             if side is None or side.device != dev:
                 side = self._side_stream = _streams.side_stream(dev)
@@ -706,7 +731,8 @@ class _TBEBase(nn.Module):
                        prepared=None, layout=None, state0_aligned: bool = False,
                        ext: Optional[OptimizerExt] = None) -> None:
         """`ext` (momentum / eta / gradient clipping: include/tbe_hip.h tbe_optimizer_ext) selects the _ex entries, which
-        alone take the row-norm optimizers and clipping; without it the call is the one it always was."""
+        alone take the row-norm optimizers and clipping.  `prepared` (the sort already ran on the side stream: see
+        _prepare_backward) selects the apply entries, the tables' element type the _f32 / _f16w ones."""
         lay = self._get_layout()
         dev = self.current_device
         lib = _lib.load()
@@ -731,45 +757,29 @@ class _TBEBase(nn.Module):
         f16 = self._fp16_tables()
         flags = 1 if (len(set(self.dims_per_table)) == 1 and self.max_D % (8 if f16 else 4) == 0 and stride % 4 == 0
                       and (state0_override is None or state0_aligned)) else 0
-        # FP16 tables: how the float result of a row update is rounded (include/tbe_hip.h TBE_ROUND_*)
-        rounding = (int(getattr(self, "_rounding", 0)), int(getattr(self, "_sr_seed", 0))) if f16 else ()
-        extra = (ctypes_byref(ext),) if ext is not None else ()
-        ex = "_ex" if ext is not None else ""
         if per_sample_weights is not None:
             flags |= _FLAG_WEIGHTED  # the sort payload then carries positions too (set in prepare as well)
         with torch.cuda.device(dev):
+            # the entry, and what it takes beyond the common list
             if prepared is not None:
                 ws, ev = prepared
                 torch.cuda.current_stream(dev).wait_event(ev)
-                apply_name = f"tbe_backward_apply{ex}_f16w" if f16 else f"tbe_backward_apply{ex}_f32"
-                apply = getattr(lib, apply_name)
-                check(
-                    apply(ptr(lay.feat_weights), ptr(lay.feat_D), ptr(out_off),
-                          ptr(lay.feat_rows), ptr(lay.feat_row_base), ptr(feat_state0),
-                          ptr(lay.feat_state1), self.F, B, self.max_D, self.key_bits,
-                          ptr(indices), N, ptr(offsets), ptr(per_sample_weights),
-                          int(self.pooling_mode), ptr(lay.feat_pooling), ptr(grad_out), stride, opt, flags,
-                          ptr(ws), ws.numel(), *rounding, *extra, stream_ptr(dev)),
-                    apply_name,
-                )
-                return
-            nbytes = lib.tbe_backward_workspace_bytes(N, self.F, B, self.max_D, self.key_bits)
-            if nbytes == 0:
-                raise RuntimeError(f"TBE backward: {N} ids in one call is beyond the limit of 2^29 - 1 (include/tbe_hip.h): "
-                                   "split the batch")
-            ws = workspace(nbytes, dev)
-            fused_name = f"tbe_backward_fused{ex}_f16w" if f16 else f"tbe_backward_fused{ex}_f32"
-            fused = getattr(lib, fused_name)
+                kind, tail = "apply", []
+            else:  # no sort yet
+                ws = self._backward_workspace(N, B)
+                kind, tail = "fused", [self._errors_ptr(), ptr(lay.feat_window)]
+            if f16:  # how the float result of a row update is rounded (include/tbe_hip.h TBE_ROUND_*)
+                tail += [self._rounding, self._sr_seed]
+            if ext is not None:
+                tail.append(ctypes_byref(ext))
+            name = f"tbe_backward_{kind}{'_ex' if ext is not None else ''}{'_f16w' if f16 else '_f32'}"
             check(
-                fused(ptr(lay.feat_weights), ptr(lay.feat_D),
-                      ptr(out_off), ptr(lay.feat_rows),
-                      ptr(lay.feat_row_base), ptr(feat_state0),
-                      ptr(lay.feat_state1), self.F, B,
-                      self.max_D, self.key_bits, ptr(indices), N, ptr(offsets),
-                      ptr(per_sample_weights), int(self.pooling_mode), ptr(lay.feat_pooling),
-                      ptr(grad_out), stride, opt, flags, ptr(ws), ws.numel(),
-                      self._errors_ptr(), ptr(lay.feat_window), *rounding, *extra, stream_ptr(dev)),
-                fused_name,
+                getattr(lib, name)(
+                    ptr(lay.feat_weights), ptr(lay.feat_D), ptr(out_off), ptr(lay.feat_rows), ptr(lay.feat_row_base),
+                    ptr(feat_state0), ptr(lay.feat_state1), self.F, B, self.max_D, self.key_bits, ptr(indices), N,
+                    ptr(offsets), ptr(per_sample_weights), int(self.pooling_mode), ptr(lay.feat_pooling), ptr(grad_out),
+                    stride, opt, flags, ptr(ws), ws.numel(), *tail, stream_ptr(dev)),
+                name,
             )
 
     def _indice_weights_grad(self, grad_out, indices, offsets, B: int, layout=None,
@@ -831,24 +841,31 @@ class LookupRecord:
     autograd context: a train step that knows its own schedule — models/dlrm.py, HIP-graph mode — drives forward and
     backward itself and skips the autograd engine, its per-node Python hand-offs and its worker thread)."""
 
-    __slots__ = ("indices", "offsets", "per_sample_weights", "B", "layout", "prepared")
+    __slots__ = ("indices", "offsets", "per_sample_weights", "B", "layout", "prepared", "sort_pending")
 
     def __init__(self, indices, offsets, per_sample_weights, B, layout) -> None:
         self.indices, self.offsets, self.per_sample_weights, self.B, self.layout = indices, offsets, per_sample_weights, B, layout
-        self.prepared = None
+        self.prepared = None  # (workspace, event) of the backward's sort once it runs on the side stream
+        self.sort_pending = False  # the lookup wants that sort but left starting it to start_backward_sort()
 
 
-class _FusedLookupInto(torch.autograd.Function):
-    """Like _FusedLookup, but writes its column blocks into a caller-provided [B, stride] buffer."""
+class _FusedLookup(torch.autograd.Function):
+    """forward = TBE gather/pool, into the caller's `out` buffer (addressed by out_off / stride, marked dirty) when one is
+    given; backward = coalesce + fused optimizer (no table grad), plus the per_sample_weights gradient when those
+    require grad."""
 
     @staticmethod
-    def forward(ctx, out, placeholder, module, indices, offsets, per_sample_weights, B, out_off, stride, prepare,
-                feature_requires_grad=None):
-        ctx.module, ctx.B, ctx.layout, ctx.frg = module, B, (out_off, stride), feature_requires_grad
+    def forward(ctx, placeholder, module, indices, offsets, per_sample_weights, B, prepare, feature_requires_grad=None,
+                out=None, out_off=None, stride=0):
+        ctx.module, ctx.B, ctx.frg = module, B, feature_requires_grad
+        ctx.layout = (out_off, stride) if out is not None else None
         ctx.save_for_backward(indices, offsets, per_sample_weights)
-        module._forward_impl(indices, offsets, per_sample_weights, B, into=(out, out_off, stride))
-        ctx.prepared = module._prepare_or_defer(ctx, indices, offsets, B, per_sample_weights is not None) if prepare else None
-        ctx.mark_dirty(out)
+        if out is None:
+            out = module._forward_impl(indices, offsets, per_sample_weights, B)
+        else:
+            module._forward_impl(indices, offsets, per_sample_weights, B, into=(out, out_off, stride))
+            ctx.mark_dirty(out)
+        ctx.prepared = module._prepare_backward(indices, offsets, B, per_sample_weights is not None) if prepare else None
         return out
 
     @staticmethod
@@ -857,68 +874,14 @@ class _FusedLookupInto(torch.autograd.Function):
         module = ctx.module
         # before the update: it reads the rows the update rewrites (same stream)
         giw = (module._indice_weights_grad(grad_out, indices, offsets, ctx.B, ctx.layout, ctx.frg)
-               if ctx.needs_input_grad[5] else None)
+               if ctx.needs_input_grad[4] else None)
         module.iter += 1
         module._backward_impl(grad_out, indices, offsets, psw, ctx.B, module._optimizer_struct(),
                               prepared=ctx.prepared, layout=ctx.layout, ext=module._optimizer_ext())
         ctx.prepared = None
         if module._cache is not None:
             module._cache.after_backward()
-        return (grad_out, None, None, None, None, giw) + (None,) * 5
-
-
-class _DenseLookupInto(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, out, weights, module, indices, offsets, per_sample_weights, B, out_off, stride,
-                feature_requires_grad=None):
-        ctx.module, ctx.B, ctx.layout, ctx.frg = module, B, (out_off, stride), feature_requires_grad
-        ctx.save_for_backward(indices, offsets, per_sample_weights)
-        module._forward_impl(indices, offsets, per_sample_weights, B, into=(out, out_off, stride))
-        ctx.mark_dirty(out)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        indices, offsets, psw = ctx.saved_tensors
-        module = ctx.module
-        grad_w = torch.zeros_like(module.weights)
-        state0 = module._dense_grad_ptrs(grad_w)
-        opt = OptimizerArgs(_OPT_DENSE_GRAD, 0.0, 0.0, 0.0, 0.0, 0.0, 1)
-        module._backward_impl(grad_out, indices, offsets, psw, ctx.B, opt, state0_override=state0, layout=ctx.layout,
-                              state0_aligned=grad_w.data_ptr() % 16 == 0)
-        giw = (module._indice_weights_grad(grad_out, indices, offsets, ctx.B, ctx.layout, ctx.frg)
-               if ctx.needs_input_grad[5] else None)
-        return (grad_out, grad_w, None, None, None, giw) + (None,) * 4
-
-
-class _FusedLookup(torch.autograd.Function):
-    """forward = TBE gather/pool; backward = coalesce + fused optimizer (no table grad), plus the per_sample_weights
-    gradient when those require grad."""
-
-    @staticmethod
-    def forward(ctx, placeholder, module, indices, offsets, per_sample_weights, B, prepare, feature_requires_grad=None):
-        ctx.module = module
-        ctx.B = B
-        ctx.frg = feature_requires_grad
-        ctx.save_for_backward(indices, offsets, per_sample_weights)
-        out = module._forward_impl(indices, offsets, per_sample_weights, B)
-        ctx.prepared = module._prepare_or_defer(ctx, indices, offsets, B, per_sample_weights is not None) if prepare else None
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        indices, offsets, psw = ctx.saved_tensors
-        module = ctx.module
-        # before the update: it reads the rows the update rewrites (same stream)
-        giw = (module._indice_weights_grad(grad_out, indices, offsets, ctx.B, None, ctx.frg)
-               if ctx.needs_input_grad[4] else None)
-        module.iter += 1
-        module._backward_impl(grad_out, indices, offsets, psw, ctx.B, module._optimizer_struct(),
-                              prepared=ctx.prepared, ext=module._optimizer_ext())
-        ctx.prepared = None
-        if module._cache is not None:
-            module._cache.after_backward()
-        return None, None, None, None, giw, None, None, None
+        return (None, None, None, None, giw, None, None, None, grad_out if ctx.layout is not None else None, None, None)
 
 
 class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
@@ -1119,7 +1082,7 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
 
     def _optimizer_ext(self) -> Optional[OptimizerExt]:
         """The extension struct of the _ex backward entries, for a module that needs them (a row-norm optimizer or
-        gradient clipping); None keeps a module on the entries it always called."""
+        gradient clipping); None for every other module, which calls the plain entries."""
         a = self.optimizer_args
         if _OPT_CODE[self.optimizer] not in _NORM_FAMILY and not a.gradient_clipping:
             return None
@@ -1135,50 +1098,23 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
     def forward(self, indices: torch.Tensor, offsets: torch.Tensor,
                 per_sample_weights: Optional[torch.Tensor] = None,
                 feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
-        self._refuse_clipped_indice_weights_grad(per_sample_weights)
-        indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
-        if self._cache is not None:
-            indices = self._cache.prefetch(self._real_layout(), indices, offsets, B, torch.is_grad_enabled())
-        mode = self.overlap_backward_sort
-        prepare = torch.is_grad_enabled() and (
-            mode in (True, "1") or (mode == "auto" and indices.numel() <= self.overlap_backward_sort_max_ids))
-        out = _FusedLookup.apply(self.placeholder_autograd_tensor, self, indices, offsets,
-                                 per_sample_weights, B, prepare, feature_requires_grad)
-        self._enforce_bounds_check_mode()
-        return out
+        return self._lookup(indices, offsets, per_sample_weights, feature_requires_grad)
 
     def forward_into(self, out: torch.Tensor, out_offsets: torch.Tensor, row_stride: int, indices: torch.Tensor,
                      offsets: torch.Tensor, per_sample_weights: Optional[torch.Tensor] = None,
                      feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Pooled lookup whose feature blocks land at `out[b * row_stride + out_offsets[f] + d]` of the
         given buffer (returned, marked dirty for autograd)."""
+        return self._lookup(indices, offsets, per_sample_weights, feature_requires_grad, out, out_offsets, int(row_stride))
+
+    def _lookup(self, indices, offsets, per_sample_weights, feature_requires_grad, *into) -> torch.Tensor:
         self._refuse_clipped_indice_weights_grad(per_sample_weights)
-        indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
-        if self._cache is not None:
-            indices = self._cache.prefetch(self._real_layout(), indices, offsets, B, torch.is_grad_enabled())
-        mode = self.overlap_backward_sort
-        prepare = torch.is_grad_enabled() and (
-            mode in (True, "1") or (mode == "auto" and indices.numel() <= self.overlap_backward_sort_max_ids))
-        out = _FusedLookupInto.apply(out, self.placeholder_autograd_tensor, self, indices, offsets,
-                                     per_sample_weights, B, out_offsets, int(row_stride), prepare, feature_requires_grad)
+        indices, offsets, per_sample_weights, B, prepare = self._begin_lookup(indices, offsets, per_sample_weights,
+                                                                              torch.is_grad_enabled())
+        out = _FusedLookup.apply(self.placeholder_autograd_tensor, self, indices, offsets, per_sample_weights, B, prepare,
+                                 feature_requires_grad, *into)
         self._enforce_bounds_check_mode()
         return out
-
-    def lookup_no_autograd(self, indices: torch.Tensor, offsets: torch.Tensor,
-                           per_sample_weights: Optional[torch.Tensor] = None, into=None):
-        """The training forward without an autograd node: returns (output, LookupRecord).  `into` = (buffer,
-        per-feature offsets, row stride) as in forward_into.  The caller owes exactly one
-        backward_no_autograd(record, grad) per call (the side-stream sort of the backward is already running)."""
-        indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
-        if self._cache is not None:
-            indices = self._cache.prefetch(self._real_layout(), indices, offsets, B, True)
-        rec = LookupRecord(indices, offsets, per_sample_weights, B, (into[1], int(into[2])) if into is not None else None)
-        out = self._forward_impl(indices, offsets, per_sample_weights, B, into=into)
-        mode = self.overlap_backward_sort
-        if mode in (True, "1") or (mode == "auto" and indices.numel() <= self.overlap_backward_sort_max_ids_explicit):
-            rec.prepared = self._prepare_or_defer(rec, indices, offsets, B, per_sample_weights is not None)
-        self._enforce_bounds_check_mode()
-        return out, rec
 
     def gather_layout(self):
         """(feat_weights, feat_rows, feat_window) device arrays for a consumer that fetches the rows itself
@@ -1199,12 +1135,10 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         backward_no_autograd(record, grad) with the gradient of the pooled output it never materialised."""
         if self._cache is not None:
             raise RuntimeError("lookup_deferred: not available with MANAGED_CACHING tables (the cache rewrites the ids)")
-        indices, offsets, _, B = self._check_inputs(indices, offsets, None)
+        indices, offsets, _, B, overlap = self._begin_lookup(indices, offsets, None, torch.is_grad_enabled())
         rec = LookupRecord(indices, offsets, None, B, None)
-        mode = self.overlap_backward_sort
-        if torch.is_grad_enabled() and (
-                mode in (True, "1") or (mode == "auto" and indices.numel() <= self.overlap_backward_sort_max_ids)):
-            rec.prepared = self._prepare_or_defer(rec, indices, offsets, B, False)
+        if overlap:
+            rec.prepared = self._prepare_backward(indices, offsets, B)
         self._enforce_bounds_check_mode()
         return rec
 
@@ -1219,13 +1153,19 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
 
 
 class _DenseLookup(torch.autograd.Function):
+    """forward as _FusedLookup's; backward = the dense gradient of `.weights`."""
+
     @staticmethod
-    def forward(ctx, weights, module, indices, offsets, per_sample_weights, B, feature_requires_grad=None):
-        ctx.module = module
-        ctx.B = B
-        ctx.frg = feature_requires_grad
+    def forward(ctx, weights, module, indices, offsets, per_sample_weights, B, feature_requires_grad=None,
+                out=None, out_off=None, stride=0):
+        ctx.module, ctx.B, ctx.frg = module, B, feature_requires_grad
+        ctx.layout = (out_off, stride) if out is not None else None
         ctx.save_for_backward(indices, offsets, per_sample_weights)
-        return module._forward_impl(indices, offsets, per_sample_weights, B)
+        if out is None:
+            return module._forward_impl(indices, offsets, per_sample_weights, B)
+        module._forward_impl(indices, offsets, per_sample_weights, B, into=(out, out_off, stride))
+        ctx.mark_dirty(out)
+        return out
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -1234,11 +1174,11 @@ class _DenseLookup(torch.autograd.Function):
         grad_w = torch.zeros_like(module.weights)
         state0 = module._dense_grad_ptrs(grad_w)
         opt = OptimizerArgs(_OPT_DENSE_GRAD, 0.0, 0.0, 0.0, 0.0, 0.0, 1)
-        module._backward_impl(grad_out, indices, offsets, psw, ctx.B, opt, state0_override=state0,
+        module._backward_impl(grad_out, indices, offsets, psw, ctx.B, opt, state0_override=state0, layout=ctx.layout,
                               state0_aligned=grad_w.data_ptr() % 16 == 0)
-        giw = (module._indice_weights_grad(grad_out, indices, offsets, ctx.B, None, ctx.frg)
+        giw = (module._indice_weights_grad(grad_out, indices, offsets, ctx.B, ctx.layout, ctx.frg)
                if ctx.needs_input_grad[4] else None)
-        return grad_w, None, None, None, giw, None, None
+        return (grad_w, None, None, None, giw, None, None, grad_out if ctx.layout is not None else None, None, None)
 
 
 class DenseTableBatchedEmbeddingBagsCodegen(_TBEBase):
@@ -1261,6 +1201,13 @@ class DenseTableBatchedEmbeddingBagsCodegen(_TBEBase):
         self.weights = nn.Parameter(torch.zeros(self._flat_sizes["dev"], dtype=torch.float32,
                                                 device=self.current_device))
         self._empty = torch.zeros(0, dtype=torch.float32)
+        self._dense_rel = None  # see _dense_grad_ptrs
+        self._dense_ptrs_cache = None  # (address of a persistent gradient buffer, its per-feature address table)
+
+    def __getstate__(self):
+        d = super().__getstate__()
+        d["_dense_ptrs_cache"] = None
+        return d
 
     def _flat_weights(self, placement: str) -> torch.Tensor:
         return self.weights if placement == "dev" else self._empty
@@ -1274,7 +1221,7 @@ class DenseTableBatchedEmbeddingBagsCodegen(_TBEBase):
     def _dense_grad_ptrs(self, grad_w: torch.Tensor) -> torch.Tensor:
         """Per-feature base addresses inside a dense gradient buffer, computed on the device (a
         host-built table would cost a blocking H2D copy in every backward)."""
-        rel = getattr(self, "_dense_rel", None)
+        rel = self._dense_rel
         if rel is None or rel.device != grad_w.device:
             rel = torch.tensor([4 * self.weights_offsets[t] for t in self.feature_table_map], dtype=torch.int64).to(grad_w.device)
             self._dense_rel = rel
@@ -1291,28 +1238,16 @@ class DenseTableBatchedEmbeddingBagsCodegen(_TBEBase):
     def forward(self, indices: torch.Tensor, offsets: torch.Tensor,
                 per_sample_weights: Optional[torch.Tensor] = None,
                 feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
-        indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
-        return _DenseLookup.apply(self.weights, self, indices, offsets, per_sample_weights, B, feature_requires_grad)
+        return self._lookup(indices, offsets, per_sample_weights, feature_requires_grad)
 
     def forward_into(self, out: torch.Tensor, out_offsets: torch.Tensor, row_stride: int, indices: torch.Tensor,
                      offsets: torch.Tensor, per_sample_weights: Optional[torch.Tensor] = None,
                      feature_requires_grad: Optional[torch.Tensor] = None) -> torch.Tensor:
-        indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
-        return _DenseLookupInto.apply(out, self.weights, self, indices, offsets, per_sample_weights, B, out_offsets,
-                                      int(row_stride), feature_requires_grad)
+        return self._lookup(indices, offsets, per_sample_weights, feature_requires_grad, out, out_offsets, int(row_stride))
 
-    def lookup_no_autograd(self, indices: torch.Tensor, offsets: torch.Tensor,
-                           per_sample_weights: Optional[torch.Tensor] = None, into=None):
-        """Forward without an autograd node: (output, LookupRecord); see the fused class."""
+    def _lookup(self, indices, offsets, per_sample_weights, feature_requires_grad, *into) -> torch.Tensor:
         indices, offsets, per_sample_weights, B = self._check_inputs(indices, offsets, per_sample_weights)
-        rec = LookupRecord(indices, offsets, per_sample_weights, B, (into[1], int(into[2])) if into is not None else None)
-        out = self._forward_impl(indices, offsets, per_sample_weights, B, into=into)
-        # the gradient-independent half of the backward (linearize + sort: 5 dependent launches, ~25 us of latency for the
-        # ~90 K ids of the replicated tiny tables) starts now on the module's side stream, as the fused module's does
-        mode = self.overlap_backward_sort
-        if mode in (True, "1") or (mode == "auto" and indices.numel() <= self.overlap_backward_sort_max_ids_explicit):
-            rec.prepared = self._prepare_or_defer(rec, indices, offsets, B, per_sample_weights is not None)
-        return out, rec
+        return _DenseLookup.apply(self.weights, self, indices, offsets, per_sample_weights, B, feature_requires_grad, *into)
 
     def backward_no_autograd(self, rec: "LookupRecord", grad_out: torch.Tensor,
                              into: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1325,7 +1260,7 @@ class DenseTableBatchedEmbeddingBagsCodegen(_TBEBase):
                     or into.device != self.weights.device):
                 raise RuntimeError("backward_no_autograd: `into` must be a contiguous float32 tensor shaped like .weights")
             grad_w = into.zero_()
-            cached = getattr(self, "_dense_ptrs_cache", None)
+            cached = self._dense_ptrs_cache
             if cached is None or cached[0] != grad_w.data_ptr():
                 cached = self._dense_ptrs_cache = (grad_w.data_ptr(), self._dense_grad_ptrs(grad_w))
             ptrs = cached[1]

@@ -1535,16 +1535,15 @@ class ExplicitLookupStep:
         if owner._exchange:
             # order of the HOST calls: lookup kernel, pooled all-to-all, THEN the backward's side-stream sort (6 launches,
             # ~60 us of host time): the all-to-all is on the step's critical path, the sort is not
+            # (a TBE module from `tbe_factory` without start_backward_sort sorts where it looks up)
             m = owner._emb_module
-            can_defer = hasattr(m, "launch_deferred_backward_sort") and not getattr(m, "defer_backward_sort", False)
-            if can_defer:
-                m.defer_backward_sort = True
-            try:
-                with label("## tbe_lookup ##"):
-                    emb, self.rec = m.lookup_no_autograd(dist_input.values, dist_input.offsets, dist_input.weights)
-            finally:
+            can_defer = hasattr(m, "start_backward_sort")
+            with label("## tbe_lookup ##"):
                 if can_defer:
-                    m.defer_backward_sort = False
+                    emb, self.rec = m.lookup_no_autograd(dist_input.values, dist_input.offsets, dist_input.weights,
+                                                         defer_sort=True)
+                else:
+                    emb, self.rec = m.lookup_no_autograd(dist_input.values, dist_input.offsets, dist_input.weights)
             self.state = _ExchangeState(owner, dist_input.batch_size)
             if self.halves:
                 self.state.start_forward_halves(emb)
@@ -1561,7 +1560,7 @@ class ExplicitLookupStep:
                     _, self.dp_rec = owner._dp_module.lookup_no_autograd(
                         v, offs, w, into=(self.state.output_destination(), owner._dp_out_off, owner._D_total))
             if can_defer:
-                m.launch_deferred_backward_sort()
+                m.start_backward_sort(self.rec)
             self._out = None
         else:
             out = owner._alias_output_buffer(dist_input.batch_size)
@@ -1590,21 +1589,18 @@ class ExplicitLookupStep:
             # its backward's side-stream sort (5 launches of host time) goes behind the unpack launch: the host is what the
             # GPU waits for at this point of the step
             m = o._dp_module
-            can_defer = hasattr(m, "launch_deferred_backward_sort") and not getattr(m, "defer_backward_sort", False)
-            if can_defer:
-                m.defer_backward_sort = True
-            try:
-                with label("## tbe_lookup ##"):
-                    _, self.dp_rec = m.lookup_no_autograd(v, offs, w, into=(dest, o._dp_out_off, o._D_total))
-            finally:
-                if can_defer:
-                    m.defer_backward_sort = False
-            self._dp_sort_pending = can_defer
+            into = (dest, o._dp_out_off, o._D_total)
+            self._dp_sort_pending = hasattr(m, "start_backward_sort")
+            with label("## tbe_lookup ##"):
+                if self._dp_sort_pending:
+                    _, self.dp_rec = m.lookup_no_autograd(v, offs, w, into=into, defer_sort=True)
+                else:
+                    _, self.dp_rec = m.lookup_no_autograd(v, offs, w, into=into)
 
     def _launch_late_dp_sort(self) -> None:
         if self._dp_sort_pending:
             self._dp_sort_pending = False
-            self.o._dp_module.launch_deferred_backward_sort()
+            self.o._dp_module.start_backward_sort(self.dp_rec)
 
     def finish_half(self, h: int) -> torch.Tensor:
         """Half-batch mode: rows [h B/2, (h + 1) B/2) of the pooled output, complete (the replicated tables' columns were
