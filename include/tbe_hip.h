@@ -727,6 +727,26 @@ size_t tbe_bce_with_logits_workspace_bytes(void);
 int tbe_bce_with_logits_f32(const float* logits, const void* labels, int32_t label_elem_size, int64_t B, float* loss,
                             float* dlogits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Exact binary AUROC and thresholded accuracy of an evaluation set, as integer counts — what the reference's _evaluate
+ * feeds torchmetrics.AUROC / Accuracy for (examples/dlrm/dlrm_main.py:252-265).  preds [n] float32 (probabilities or any
+ * score), labels [n] float32 (label_elem_size 4) or int64 (8) with values 0 / 1.  counts: DEVICE int64 [6], 8-B aligned,
+ * written (not accumulated) by the call:
+ *   0  2U = sum over positives p of ( 2 * #{negatives with x < x_p} + #{negatives with x == x_p} );  AUROC = 2U / (2 P N)
+ *   1  P, 2  N (labels equal to 1 / 0),  3  n_correct = #{ (x >= threshold) == (label == 1) },
+ *   4  n_nan (NaN predictions),  5  n_bad_label (labels that are neither 0 nor 1)
+ * -0.0 ties with +0.0, the infinities are ordinary values, denormals are not flushed.  With n_nan > 0 or n_bad_label > 0
+ * slots 0 .. 3 are unspecified.  Integer arithmetic only: two runs are bit-identical.  The inputs are not modified; keys,
+ * payloads and scratch live in `workspace` (tbe_auroc_workspace_bytes(n) bytes, 256-B aligned, no zeroing needed).
+ * n == 0 is legal (preds / labels may be NULL then; all six counters are 0).
+ * Errors, before anything is launched: TBE_ERR_INVALID_ARGUMENT for n < 0, n >= 2^29 (the pair sort's limit;
+ * tbe_auroc_workspace_bytes returns 0), a label_elem_size other than 4 / 8, a null or misaligned pointer;
+ * TBE_ERR_WORKSPACE for a short workspace.  A give-up inside the sort is reported through tbe_fault_status. */
+/* examples/dlrm/dlrm_main.py:252-265 */
+size_t tbe_auroc_workspace_bytes(int64_t n);
+/* examples/dlrm/dlrm_main.py:252-265 */
+int tbe_auroc_counts_f32(const float* preds, const void* labels, int32_t label_elem_size, int64_t n, float threshold,
+                         int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* torch.ops.fbgemm.jagged_2d_to_dense (examples/bert4rec/models/bert4rec.py:394-400):
  * values [N, D] + offsets [B+1] -> dense [B, max_L, D], zero padded / truncated. */
 int tbe_jagged_2d_to_dense_f32(const float* values, const int64_t* offsets, int32_t B,

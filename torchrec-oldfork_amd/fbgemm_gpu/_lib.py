@@ -181,6 +181,9 @@ SIGNATURES = {
     "tbe_bce_with_logits_workspace_bytes": (c_size, []),
     "tbe_bce_with_logits_f32": (
         ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "tbe_auroc_workspace_bytes": (c_size, [c_i64]),
+    "tbe_auroc_counts_f32": (
+        ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i64, c_float, c_void_p, c_void_p, c_size, c_void_p]),
     "tbe_jagged_2d_to_dense_f32": (
         ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p]),
     "tbe_dense_to_jagged_2d_f32": (
