@@ -717,6 +717,42 @@ int tbe_multi_chunk_sum_f32(const int64_t* seg_table, int32_t nseg, int64_t max_
 int tbe_multi_chunk_sum_host_table_f32(const int64_t* host_seg_table, int32_t nseg, int64_t max_numel, float* dst,
                                        float scale, void* stream);
 
+/* Backward epilogue of one layer of a GEMM-based cross network — CrossNet (torchrec/modules/crossnet.py:19-89, the
+ * layer at :85-87) and LowRankCrossNet (:92-188, the layer at :177-186):  x_{l+1} = x_0 * t + x_l,  t = y + b,
+ * y = x_l K^T  or  (x_l V^T) W^T.  Given grad_out = dL/dx_{l+1}, ONE pass over [B, N]:
+ *   grad_y[b, c] = grad_out[b, c] * x0[b, c]                 (the gradient of y, and of b before its column sum)
+ *   acc[b, c]    = grad_out[b, c] * t[b, c]                  if first != 0
+ *   acc[b, c]    = acc[b, c] + grad_out[b, c] * t[b, c]      otherwise (the running gradient of x_0)
+ *   bias_grad[c] = sum_b grad_y[b, c]                        (row-block sums, then a fixed-order second stage)
+ * Each product and each add is rounded on its own; no float atomics; two runs are bit-identical.  The forward of these nets
+ * needs no entry: torch.addmm carries the bias and torch.addcmul forms x_0 * t + x_l.
+ * fp32, [B, N] row-major and contiguous, N a positive multiple of 4, every base 16-B aligned, no two buffers overlapping;
+ * workspace: tbe_cross_backward_workspace_bytes(B, N) bytes.  B == 0 zeroes bias_grad and touches nothing else.
+ * Errors, before anything is launched: TBE_ERR_INVALID_ARGUMENT for a bad N, a null or misaligned pointer, a short
+ * workspace, or more than 65535 row blocks (B > 65535 * 64 for N < 512, * 256 otherwise). */
+size_t tbe_cross_backward_workspace_bytes(int64_t B, int32_t N);
+int tbe_cross_backward_f32(const float* grad_out, const float* x0, const float* t, int64_t B, int32_t N, int32_t first,
+                           float* grad_y, float* acc, float* bias_grad, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
+/* VectorCrossNet (torchrec/modules/crossnet.py:191-268; the layer at :257-266), all L layers in one kernel each way:
+ *   s[l, b] = x_l[b, :] . weights[l, :];   x_{l+1} = (x_0 * s[l] + bias[l, :]) + x_l   (the reference's operation order)
+ * forward: reads x0 [B, N] once, writes out = x_L [B, N] and s [L, B].
+ * backward: reads grad_out, x0 and s, recomputes every x_l in the forward's operation order (bit for bit the forward's) and
+ * writes grad_in [B, N] and grad_params [2 L, N]: rows 0 .. L-1 the gradients of bias[l], rows L .. 2L-1 those of
+ * weights[l] — row-block sums in `workspace` (tbe_vector_cross_backward_workspace_bytes(B, N, L) bytes), finished in fixed
+ * order by one launch over 2 L N columns.  Row dots and column sums run in an order that depends on (B, N, L) only: two
+ * runs are bit-identical.  weights, bias: [L, N] (the module stacks its L [N, 1] parameters).
+ * Limits: N <= 4096 and a multiple of 4, 1 <= L <= 8; beyond them TBE_ERR_INVALID_ARGUMENT with a message that names the
+ * limits, as for a null or misaligned (16 B; s and grad_params 4 B) pointer or a short workspace, before anything is
+ * launched.  B == 0: the forward does nothing, the backward zeroes grad_params and touches nothing else. */
+size_t tbe_vector_cross_backward_workspace_bytes(int64_t B, int32_t N, int32_t L);
+int tbe_vector_cross_forward_f32(const float* x0, const float* weights, const float* bias, int64_t B, int32_t N, int32_t L,
+                                 float* out, float* s, void* stream);
+int tbe_vector_cross_backward_f32(const float* grad_out, const float* x0, const float* s, const float* weights,
+                                  const float* bias, int64_t B, int32_t N, int32_t L, float* grad_in, float* grad_params,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* nn.BCEWithLogitsLoss (mean) forward + gradient in one launch — the loss of the reference's train wrapper
  * (examples/dlrm/modules/dlrm_train.py):  loss = mean_i [max(x_i, 0) - x_i y_i + log1p(exp(-|x_i|))],
  * dlogits_i = (sigmoid(x_i) - y_i) / B  (dlogits may be NULL).  labels: float32 (label_elem_size 4) or int64 (8).

@@ -1,0 +1,428 @@
+// Cross networks (DCN / DCN-v2) on gfx950: the element-wise work between the library GEMMs, and all of VectorCrossNet.
+//
+// Reference: torchrec/modules/crossnet.py — CrossNet :19-89, LowRankCrossNet :92-188, VectorCrossNet :191-268 — trained
+// through autograd.  A layer of the two GEMM-based nets is  x_{l+1} = x_0 * t + x_l,  t = y + b,  y = x_l K^T  or
+// (x_l V^T) W^T.
+//
+// The FORWARD of the GEMM-based nets needs no kernel of this file: the bias rides in the GEMM (torch.addmm with
+// bias.view(N)) and x_0 * t + x_l is one torch.addcmul; t is what the backward saves.
+//
+// Their BACKWARD through autograd is, per layer, a chain of HBM-bound kernels over [B, N]: mul (G * x_0), mul (G * t),
+// AccumulateGrad add into x_0's gradient, a column sum for the bias.  cross_bwd_kernel does all of it in one pass: it
+// reads G, x_0, t (and acc, unless `first`), writes g_y = G * x_0 and acc (+)= G * t and leaves the column sums of g_y per
+// row block, which a fixed-order second stage adds (deterministic, no float atomics) — the scheme of mlp_epilogue.hip.
+//
+// VectorCrossNet is element-wise work plus row dots only:  s_l[b] = x_l[b, :] . w_l,  x_{l+1} = x_0 * s_l + b_l + x_l.
+// One forward kernel runs all L layers with the row in registers; one backward kernel recomputes every x_l from x_0, s and
+// the biases in the forward's own operation order (so bit for bit the forward's x_l) and produces the input gradient and
+// the row-block partial sums of all 2 L parameter gradients, which ONE second-stage launch over 2 L N columns finishes.
+//
+// Every product and every add is rounded on its own (the Makefile builds with -ffp-contract=off; no fmaf here), so a float32
+// restatement in numpy reproduces the element-wise results bit for bit.
+#include <algorithm>
+
+#include "common.hpp"
+
+namespace tbe {
+
+// rows of [B, N] per workgroup of cross_bwd_kernel: the rule of mlp_epilogue.hip (tbe_colsum_row_blocks)
+__host__ __device__ inline int cross_rows_per_block(int N) { return N >= 512 ? 256 : 64; }
+
+// block = 256 threads = TY rows x TX float4-columns; grid = (column tiles, row blocks)
+template <int TX>
+__global__ __launch_bounds__(256) void cross_bwd_kernel(const float* __restrict__ G, const float* __restrict__ x0,
+                                                        const float* __restrict__ t, float* __restrict__ gy,
+                                                        float* __restrict__ acc, float* __restrict__ partial, int64_t B,
+                                                        int N, int first) {
+  constexpr int TY = 256 / TX;
+  __shared__ float4 red[TY][TX];
+  const int tx = threadIdx.x % TX;
+  const int ty = threadIdx.x / TX;
+  const int col = (blockIdx.x * TX + tx) * 4;
+  const int rpb = cross_rows_per_block(N);
+  const int64_t row0 = static_cast<int64_t>(blockIdx.y) * rpb;
+  const int64_t row1 = min(B, row0 + rpb);
+  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (col < N) {
+#pragma unroll 4
+    for (int64_t r = row0 + ty; r < row1; r += TY) {
+      const int64_t o = r * N + col;
+      const float4 g = ld4(G + o);
+      const float4 x = ld4(x0 + o);
+      const float4 tt = ld4(t + o);
+      const float4 y = make_float4(g.x * x.x, g.y * x.y, g.z * x.z, g.w * x.w);
+      float4 a = make_float4(g.x * tt.x, g.y * tt.y, g.z * tt.z, g.w * tt.w);
+      if (!first) {
+        const float4 p = ld4(acc + o);
+        a.x = p.x + a.x;
+        a.y = p.y + a.y;
+        a.z = p.z + a.z;
+        a.w = p.w + a.w;
+      }
+      st4(gy + o, y);
+      st4(acc + o, a);
+      sum.x += y.x;
+      sum.y += y.y;
+      sum.z += y.z;
+      sum.w += y.w;
+    }
+  }
+  red[ty][tx] = sum;
+  __syncthreads();
+  if (ty == 0 && col < N) {
+    float4 s = red[0][tx];
+#pragma unroll
+    for (int y = 1; y < TY; ++y) {
+      const float4 o = red[y][tx];
+      s.x += o.x;
+      s.y += o.y;
+      s.z += o.z;
+      s.w += o.w;
+    }
+    st4(partial + static_cast<int64_t>(blockIdx.y) * N + col, s);
+  }
+}
+
+// out[c] = sum over row blocks of partial[rb][c], fixed order: wave w takes blocks w, w+4, ... — the twin of
+// mlp_epilogue.hip's colsum_partials_kernel (a kernel of another translation unit cannot be launched from here)
+__global__ __launch_bounds__(256) void cross_colsum_partials_kernel(const float* __restrict__ partial, int64_t nblocks, int N,
+                                                                    float* __restrict__ out) {
+  __shared__ float red[4][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  float acc = 0.f;
+  if (c < N) {
+#pragma unroll 8
+    for (int64_t rb = wave; rb < nblocks; rb += 4) acc += partial[rb * N + c];
+  }
+  red[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && c < N) out[c] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+}
+
+// ---- VectorCrossNet ---------------------------------------------------------------------------------------------------
+constexpr int kVecMaxN = 4096;
+constexpr int kVecMaxL = 8;
+constexpr int kVecK = 4;            // float4 slots per thread: a row of up to TPR * 16 floats lives in registers
+constexpr int kVecRowsPerBlock = 128;  // rows per workgroup = rows per partial sum
+
+// Sum of `v` over the TPR threads that share a row, the same value in every one of them.  Fixed order: xor butterfly inside
+// the wave, then (TPR = 256) the four wave sums in wave order through `red`; consecutive calls alternate `phase`, so one
+// barrier per call is enough (a slot is rewritten only after the barrier of the call in between).
+template <int TPR>
+__device__ __forceinline__ float row_sum(float v, float (*red)[4], int& phase) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  if constexpr (TPR == 256) {
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) red[phase][wave] = v;
+    __syncthreads();
+    v = ((red[phase][0] + red[phase][1]) + red[phase][2]) + red[phase][3];
+    phase ^= 1;
+  }
+  return v;
+}
+
+__device__ __forceinline__ float dot4(const float4 a, const float4 b, float acc) {
+  acc += a.x * b.x;
+  acc += a.y * b.y;
+  acc += a.z * b.z;
+  acc += a.w * b.w;
+  return acc;
+}
+
+// x <- (x0 * s + b) + x: the reference's order (torchrec/modules/crossnet.py:266), each operation rounded
+__device__ __forceinline__ float4 cross_step(const float4 x0, const float s, const float4 b, const float4 x) {
+  return make_float4((x0.x * s + b.x) + x.x, (x0.y * s + b.y) + x.y, (x0.z * s + b.z) + x.z, (x0.w * s + b.w) + x.w);
+}
+
+// TPR threads per row (64: one wave per row, four rows of the block in flight; 256: the block per row).  Thread `lane` of a
+// row holds the float4 columns lane, lane + TPR, ... (kVecK of them).  grid = row blocks of kVecRowsPerBlock rows.
+template <int TPR>
+__global__ __launch_bounds__(256) void vector_cross_fwd_kernel(const float* __restrict__ x0g, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, float* __restrict__ out,
+                                                               float* __restrict__ s_out, int64_t B, int N, int L) {
+  __shared__ float red[2][4];
+  int phase = 0;
+  constexpr int RP = 256 / TPR;  // rows in flight per block
+  const int lane = threadIdx.x % TPR;
+  const int sub = threadIdx.x / TPR;
+  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kVecRowsPerBlock;
+  const int64_t row1 = min(B, row0 + kVecRowsPerBlock);
+  // the trip count is the same for every thread of the block (TPR = 256: sub = 0 everywhere; TPR = 64 has no barrier)
+  for (int64_t r = row0 + sub; r < row1; r += RP) {
+    float4 x0[kVecK], x[kVecK];
+#pragma unroll
+    for (int k = 0; k < kVecK; ++k) {
+      const int col = (k * TPR + lane) * 4;
+      x0[k] = col < N ? ld4(x0g + r * N + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+      x[k] = x0[k];
+    }
+    for (int l = 0; l < L; ++l) {
+      float part = 0.f;
+#pragma unroll
+      for (int k = 0; k < kVecK; ++k) {
+        const int col = (k * TPR + lane) * 4;
+        if (col < N) part = dot4(x[k], ld4(w + l * N + col), part);
+      }
+      const float s = row_sum<TPR>(part, red, phase);
+      if (lane == 0) s_out[static_cast<int64_t>(l) * B + r] = s;
+#pragma unroll
+      for (int k = 0; k < kVecK; ++k) {
+        const int col = (k * TPR + lane) * 4;
+        if (col < N) x[k] = cross_step(x0[k], s, ld4(bias + l * N + col), x[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kVecK; ++k) {
+      const int col = (k * TPR + lane) * 4;
+      if (col < N) st4(out + r * N + col, x[k]);
+    }
+  }
+}
+
+__device__ __forceinline__ void add4(float4& a, const float4 b) {
+  a.x += b.x;
+  a.y += b.y;
+  a.z += b.z;
+  a.w += b.w;
+}
+
+// L is a template parameter, so that the 2 * L * kVecK float4 column sums of a thread stay in registers.
+// partial: [row blocks][2 L][N] — rows 0 .. L-1 the bias gradients, L .. 2L-1 the weight gradients of the row block.
+template <int TPR, int L>
+__global__ __launch_bounds__(256) void vector_cross_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ x0g,
+                                                               const float* __restrict__ sg, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, float* __restrict__ gin,
+                                                               float* __restrict__ partial, int64_t B, int N) {
+  __shared__ float red[2][4];
+  __shared__ float4 fin[4][64];
+  int phase = 0;
+  constexpr int RP = 256 / TPR;
+  const int lane = threadIdx.x % TPR;
+  const int sub = threadIdx.x / TPR;
+  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kVecRowsPerBlock;
+  const int64_t row1 = min(B, row0 + kVecRowsPerBlock);
+  float4 sum_b[L][kVecK], sum_w[L][kVecK];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+#pragma unroll
+    for (int k = 0; k < kVecK; ++k) sum_b[l][k] = sum_w[l][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  for (int64_t r = row0 + sub; r < row1; r += RP) {
+    float4 x0[kVecK], g[kVecK], acc[kVecK];
+#pragma unroll
+    for (int k = 0; k < kVecK; ++k) {
+      const int col = (k * TPR + lane) * 4;
+      const bool in = col < N;
+      x0[k] = in ? ld4(x0g + r * N + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+      g[k] = in ? ld4(gout + r * N + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+      acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float s[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) s[l] = sg[static_cast<int64_t>(l) * B + r];
+#pragma unroll
+    for (int l = L - 1; l >= 0; --l) {
+      // x_l, recomputed in the forward's order
+      float4 x[kVecK];
+#pragma unroll
+      for (int k = 0; k < kVecK; ++k) x[k] = x0[k];
+#pragma unroll
+      for (int j = 0; j < l; ++j) {
+#pragma unroll
+        for (int k = 0; k < kVecK; ++k) {
+          const int col = (k * TPR + lane) * 4;
+          if (col < N) x[k] = cross_step(x0[k], s[j], ld4(bias + j * N + col), x[k]);
+        }
+      }
+      float part = 0.f;
+#pragma unroll
+      for (int k = 0; k < kVecK; ++k) part = dot4(g[k], x0[k], part);  // columns beyond N hold zeros
+      const float d = row_sum<TPR>(part, red, phase);
+#pragma unroll
+      for (int k = 0; k < kVecK; ++k) {
+        const int col = (k * TPR + lane) * 4;
+        if (col < N) {
+          const float4 gk = g[k];
+          const float sl = s[l];
+          add4(acc[k], make_float4(gk.x * sl, gk.y * sl, gk.z * sl, gk.w * sl));
+          add4(sum_b[l][k], gk);
+          add4(sum_w[l][k], make_float4(d * x[k].x, d * x[k].y, d * x[k].z, d * x[k].w));
+          const float4 wl = ld4(w + l * N + col);
+          add4(g[k], make_float4(d * wl.x, d * wl.y, d * wl.z, d * wl.w));
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kVecK; ++k) {
+      const int col = (k * TPR + lane) * 4;
+      if (col < N) {
+        add4(g[k], acc[k]);
+        st4(gin + r * N + col, g[k]);
+      }
+    }
+  }
+  // the row block's column sums: TPR = 256 — every thread owns its columns alone; TPR = 64 — the four waves hold the sums of
+  // rows sub, sub + 4, ... and are added in wave order through LDS
+  float* pb = partial + static_cast<int64_t>(blockIdx.x) * 2 * L * N;
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+      for (int k = 0; k < kVecK; ++k) {
+        const int col = (k * TPR + lane) * 4;
+        float4 v = half == 0 ? sum_b[l][k] : sum_w[l][k];
+        float* dst = pb + static_cast<int64_t>(half * L + l) * N + col;
+        if constexpr (TPR == 256) {
+          if (col < N) st4(dst, v);
+        } else {
+          if (k * TPR * 4 < N) {  // block-uniform: some lane of this slot holds a column
+            __syncthreads();      // the previous round's reads of `fin` are done
+            fin[sub][lane] = v;
+            __syncthreads();
+            if (sub == 0 && col < N) {
+              v = fin[0][lane];
+              add4(v, fin[1][lane]);
+              add4(v, fin[2][lane]);
+              add4(v, fin[3][lane]);
+              st4(dst, v);
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+static int64_t vec_row_blocks(int64_t B) { return (B + kVecRowsPerBlock - 1) / kVecRowsPerBlock; }
+
+}  // namespace tbe
+
+using namespace tbe;
+
+extern "C" size_t tbe_cross_backward_workspace_bytes(int64_t B, int32_t N) {
+  if (B <= 0 || N <= 0) return 256;
+  const int rpb = cross_rows_per_block(N);
+  return align_up(static_cast<size_t>((B + rpb - 1) / rpb) * N * sizeof(float), 256);
+}
+
+extern "C" int tbe_cross_backward_f32(const float* grad_out, const float* x0, const float* t, int64_t B, int32_t N,
+                                      int32_t first, float* grad_y, float* acc, float* bias_grad, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  TBE_REQUIRE(B >= 0 && N > 0 && (N & 3) == 0, "tbe_cross_backward_f32: N=%d must be a positive multiple of 4", N);
+  TBE_REQUIRE(bias_grad != nullptr, "tbe_cross_backward_f32: null bias_grad");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (B == 0) {
+    if (hipMemsetAsync(bias_grad, 0, sizeof(float) * N, st) != hipSuccess) return TBE_ERR_LAUNCH;
+    return TBE_OK;
+  }
+  TBE_REQUIRE(grad_out && x0 && t && grad_y && acc && workspace, "tbe_cross_backward_f32: null pointer");
+  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(t) |
+                reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(acc) |
+                reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
+              "tbe_cross_backward_f32: tensors must be 16-B aligned");
+  TBE_REQUIRE(workspace_bytes >= tbe_cross_backward_workspace_bytes(B, N), "tbe_cross_backward_f32: workspace too small");
+  const int rpb = cross_rows_per_block(N);
+  const int64_t nrb = (B + rpb - 1) / rpb;
+  TBE_REQUIRE(nrb <= 65535, "tbe_cross_backward_f32: B=%lld too large (more than 65535 row blocks)", (long long)B);
+  float* partial = static_cast<float*>(workspace);
+  const int vecs = N / 4;
+  const int f = first != 0;
+  if (vecs >= 64) {
+    hipLaunchKernelGGL(cross_bwd_kernel<64>, dim3((vecs + 63) / 64, static_cast<unsigned>(nrb)), dim3(256), 0, st, grad_out, x0,
+                       t, grad_y, acc, partial, B, N, f);
+  } else if (vecs >= 32) {
+    hipLaunchKernelGGL(cross_bwd_kernel<32>, dim3((vecs + 31) / 32, static_cast<unsigned>(nrb)), dim3(256), 0, st, grad_out, x0,
+                       t, grad_y, acc, partial, B, N, f);
+  } else {
+    hipLaunchKernelGGL(cross_bwd_kernel<16>, dim3((vecs + 15) / 16, static_cast<unsigned>(nrb)), dim3(256), 0, st, grad_out, x0,
+                       t, grad_y, acc, partial, B, N, f);
+  }
+  TBE_CHECK_LAUNCH("tbe_cross_backward_f32");
+  hipLaunchKernelGGL(cross_colsum_partials_kernel, dim3((N + 63) / 64), dim3(256), 0, st, partial, nrb, N, bias_grad);
+  TBE_CHECK_LAUNCH("tbe_cross_backward_f32 colsum");
+  return TBE_OK;
+}
+
+#define TBE_VEC_CROSS_LIMITS(what)                                                                                      \
+  TBE_REQUIRE(B >= 0 && N > 0 && (N & 3) == 0 && L >= 1, what ": N=%d must be a positive multiple of 4 and L=%d >= 1", N, L); \
+  TBE_REQUIRE(N <= kVecMaxN && L <= kVecMaxL, what ": N=%d, L=%d beyond the limits N <= %d, L <= %d", N, L, kVecMaxN, kVecMaxL)
+
+extern "C" size_t tbe_vector_cross_backward_workspace_bytes(int64_t B, int32_t N, int32_t L) {
+  if (B <= 0 || N <= 0 || L <= 0) return 256;
+  return align_up(static_cast<size_t>(vec_row_blocks(B)) * 2 * L * N * sizeof(float), 256);
+}
+
+extern "C" int tbe_vector_cross_forward_f32(const float* x0, const float* weights, const float* bias, int64_t B, int32_t N,
+                                            int32_t L, float* out, float* s, void* stream) {
+  TBE_VEC_CROSS_LIMITS("tbe_vector_cross_forward_f32");
+  if (B == 0) return TBE_OK;
+  TBE_REQUIRE(x0 && weights && bias && out && s, "tbe_vector_cross_forward_f32: null pointer");
+  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(bias) |
+                reinterpret_cast<uintptr_t>(out)) & 15) == 0 && (reinterpret_cast<uintptr_t>(s) & 3) == 0,
+              "tbe_vector_cross_forward_f32: tensors must be 16-B aligned");
+  const int64_t nrb = vec_row_blocks(B);
+  TBE_REQUIRE(nrb < (1ll << 31), "tbe_vector_cross_forward_f32: B=%lld too large", (long long)B);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (N <= 64 * kVecK * 4)
+    hipLaunchKernelGGL(vector_cross_fwd_kernel<64>, dim3(static_cast<unsigned>(nrb)), dim3(256), 0, st, x0, weights, bias, out, s,
+                       B, N, L);
+  else
+    hipLaunchKernelGGL(vector_cross_fwd_kernel<256>, dim3(static_cast<unsigned>(nrb)), dim3(256), 0, st, x0, weights, bias, out,
+                       s, B, N, L);
+  TBE_CHECK_LAUNCH("tbe_vector_cross_forward_f32");
+  return TBE_OK;
+}
+
+extern "C" int tbe_vector_cross_backward_f32(const float* grad_out, const float* x0, const float* s, const float* weights,
+                                             const float* bias, int64_t B, int32_t N, int32_t L, float* grad_in,
+                                             float* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
+  TBE_VEC_CROSS_LIMITS("tbe_vector_cross_backward_f32");
+  TBE_REQUIRE(grad_params != nullptr, "tbe_vector_cross_backward_f32: null grad_params");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (B == 0) {
+    if (hipMemsetAsync(grad_params, 0, sizeof(float) * 2 * L * N, st) != hipSuccess) return TBE_ERR_LAUNCH;
+    return TBE_OK;
+  }
+  TBE_REQUIRE(grad_out && x0 && s && weights && bias && grad_in && workspace, "tbe_vector_cross_backward_f32: null pointer");
+  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(weights) |
+                reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(grad_in) |
+                reinterpret_cast<uintptr_t>(workspace)) & 15) == 0 &&
+                  ((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(grad_params)) & 3) == 0,
+              "tbe_vector_cross_backward_f32: tensors must be 16-B aligned");
+  TBE_REQUIRE(workspace_bytes >= tbe_vector_cross_backward_workspace_bytes(B, N, L),
+              "tbe_vector_cross_backward_f32: workspace too small");
+  const int64_t nrb = vec_row_blocks(B);
+  TBE_REQUIRE(nrb < (1ll << 31), "tbe_vector_cross_backward_f32: B=%lld too large", (long long)B);
+  float* partial = static_cast<float*>(workspace);
+  const dim3 grid(static_cast<unsigned>(nrb));
+  const bool narrow = N <= 64 * kVecK * 4;
+#define TBE_VEC_BWD(LL)                                                                                                    \
+  case LL:                                                                                                                 \
+    if (narrow)                                                                                                            \
+      hipLaunchKernelGGL((vector_cross_bwd_kernel<64, LL>), grid, dim3(256), 0, st, grad_out, x0, s, weights, bias, grad_in, \
+                         partial, B, N);                                                                                   \
+    else                                                                                                                   \
+      hipLaunchKernelGGL((vector_cross_bwd_kernel<256, LL>), grid, dim3(256), 0, st, grad_out, x0, s, weights, bias, grad_in, \
+                         partial, B, N);                                                                                   \
+    break
+  switch (L) {
+    TBE_VEC_BWD(1);
+    TBE_VEC_BWD(2);
+    TBE_VEC_BWD(3);
+    TBE_VEC_BWD(4);
+    TBE_VEC_BWD(5);
+    TBE_VEC_BWD(6);
+    TBE_VEC_BWD(7);
+    TBE_VEC_BWD(8);
+  }
+#undef TBE_VEC_BWD
+  TBE_CHECK_LAUNCH("tbe_vector_cross_backward_f32");
+  const int cols = 2 * L * N;
+  hipLaunchKernelGGL(cross_colsum_partials_kernel, dim3((cols + 63) / 64), dim3(256), 0, st, partial, nrb, cols, grad_params);
+  TBE_CHECK_LAUNCH("tbe_vector_cross_backward_f32 colsum");
+  return TBE_OK;
+}

@@ -178,6 +178,17 @@ SIGNATURES = {
         ctypes.c_int, [c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_size, c_void_p]),
     "tbe_multi_chunk_sum_f32": (ctypes.c_int, [c_void_p, c_i32, c_i64, c_void_p, c_float, c_void_p]),
     "tbe_multi_chunk_sum_host_table_f32": (ctypes.c_int, [c_void_p, c_i32, c_i64, c_void_p, c_float, c_void_p]),
+    "tbe_cross_backward_workspace_bytes": (c_size, [c_i64, c_i32]),
+    "tbe_cross_backward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "tbe_vector_cross_backward_workspace_bytes": (c_size, [c_i64, c_i32, c_i32]),
+    "tbe_vector_cross_forward_f32": (
+        ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
+    "tbe_vector_cross_backward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_size,
+         c_void_p]),
     "tbe_bce_with_logits_workspace_bytes": (c_size, []),
     "tbe_bce_with_logits_f32": (
         ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i64, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),

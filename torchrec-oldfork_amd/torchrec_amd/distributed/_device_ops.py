@@ -24,6 +24,9 @@ _def.define("relu_backward_bias_partials(Tensor grad_out, Tensor act) -> (Tensor
 _def.define("weighted_colsum_partials(Tensor x, Tensor w) -> Tensor")
 _def.define("multi_chunk_sum(Tensor seg_table, int nseg, int max_numel, Tensor(a!) dst, float scale) -> Tensor(a!)")
 _def.define("bce_with_logits(Tensor logits, Tensor labels) -> (Tensor, Tensor)")
+_def.define("cross_backward(Tensor grad_out, Tensor x0, Tensor t, Tensor(a!) acc, bool first) -> (Tensor, Tensor)")
+_def.define("vector_cross_forward(Tensor x0, Tensor weights, Tensor bias) -> (Tensor, Tensor)")
+_def.define("vector_cross_backward(Tensor grad_out, Tensor x0, Tensor s, Tensor weights, Tensor bias) -> (Tensor, Tensor)")
 _impl = torch.library.Library("tbe_hip", "IMPL", "CUDA")
 
 
@@ -110,6 +113,67 @@ def _weighted_colsum_partials(x, w):
         check(lib.tbe_weighted_colsum_partials_f32(ptr(x), ptr(w), B, N, ptr(partial), partial.numel() * 4, stream_ptr(dev)),
               "tbe_weighted_colsum_partials_f32")
     return partial
+
+
+def _cross_backward(grad_out, x0, t, acc, first):
+    """One layer's backward epilogue of CrossNet / LowRankCrossNet (csrc/crossnet.hip): returns (grad_out * x0, its column
+    sums) and writes acc = grad_out * t (`first`) or acc += grad_out * t in place."""
+    from fbgemm_gpu._lib import workspace
+
+    dev = require_gpu(grad_out, x0, t, acc)
+    if (grad_out.dim() != 2 or any(a.shape != grad_out.shape or a.dtype != torch.float32 or not a.is_contiguous()
+                                   for a in (grad_out, x0, t, acc))):
+        raise RuntimeError(f"cross_backward: need four contiguous float32 [B, N] tensors of one shape, got "
+                           f"{[tuple(a.shape) for a in (grad_out, x0, t, acc)]}")
+    B, N = grad_out.shape
+    gy = torch.empty_like(grad_out)
+    gb = torch.empty(N, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = workspace(lib.tbe_cross_backward_workspace_bytes(B, N), dev)
+        check(lib.tbe_cross_backward_f32(ptr(grad_out), ptr(x0), ptr(t), B, N, int(bool(first)), ptr(gy), ptr(acc), ptr(gb),
+                                         ptr(ws), ws.numel(), stream_ptr(dev)), "tbe_cross_backward_f32")
+    return gy, gb
+
+
+def _vector_cross_check(name, x0, weights, bias, *more):
+    dev = require_gpu(x0, weights, bias, *more)
+    if (x0.dim() != 2 or weights.dim() != 2 or weights.shape[1] != x0.shape[1] or bias.shape != weights.shape
+            or any(a.dtype != torch.float32 or not a.is_contiguous() for a in (x0, weights, bias) + more)):
+        raise RuntimeError(f"{name}: need contiguous float32 x0 [B, N], weights [L, N], bias [L, N], got "
+                           f"{tuple(x0.shape)}, {tuple(weights.shape)}, {tuple(bias.shape)}")
+    return dev
+
+
+def _vector_cross_forward(x0, weights, bias):
+    """(x_L [B, N], s [L, B]) of VectorCrossNet, all layers in one kernel (csrc/crossnet.hip)."""
+    dev = _vector_cross_check("vector_cross_forward", x0, weights, bias)
+    (B, N), L = x0.shape, weights.shape[0]
+    out = torch.empty_like(x0)
+    s = torch.empty((L, B), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_vector_cross_forward_f32(ptr(x0), ptr(weights), ptr(bias), B, N, L, ptr(out), ptr(s),
+                                                       stream_ptr(dev)), "tbe_vector_cross_forward_f32")
+    return out, s
+
+
+def _vector_cross_backward(grad_out, x0, s, weights, bias):
+    """(input gradient [B, N], parameter gradients [2 L, N]: bias rows first, then weight rows) (csrc/crossnet.hip)."""
+    from fbgemm_gpu._lib import workspace
+
+    dev = _vector_cross_check("vector_cross_backward", x0, weights, bias, grad_out, s)
+    (B, N), L = x0.shape, weights.shape[0]
+    if grad_out.shape != x0.shape or s.shape != (L, B):
+        raise RuntimeError(f"vector_cross_backward: grad_out {tuple(grad_out.shape)} / s {tuple(s.shape)} do not fit "
+                           f"x0 {tuple(x0.shape)}, L = {L}")
+    gin = torch.empty_like(x0)
+    gp = torch.empty((2 * L, N), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = workspace(lib.tbe_vector_cross_backward_workspace_bytes(B, N, L), dev)
+        check(lib.tbe_vector_cross_backward_f32(ptr(grad_out), ptr(x0), ptr(s), ptr(weights), ptr(bias), B, N, L, ptr(gin),
+                                                ptr(gp), ptr(ws), ws.numel(), stream_ptr(dev)), "tbe_vector_cross_backward_f32")
+    return gin, gp
 
 
 def _multi_chunk_sum(seg_table, nseg, max_numel, dst, scale):
@@ -231,6 +295,9 @@ _impl.impl("weighted_colsum", _weighted_colsum)
 _impl.impl("copy_rows", _copy_rows)
 _impl.impl("relu_backward_bias_partials", _relu_backward_bias_partials)
 _impl.impl("weighted_colsum_partials", _weighted_colsum_partials)
+_impl.impl("cross_backward", _cross_backward)
+_impl.impl("vector_cross_forward", _vector_cross_forward)
+_impl.impl("vector_cross_backward", _vector_cross_backward)
 _impl.impl("multi_chunk_sum", _multi_chunk_sum)
 _impl.impl("bce_with_logits", _bce_with_logits)
 _impl.impl("pooled_exchange_unpack", _unpack)
