@@ -155,12 +155,10 @@ def main():
     gout = torch.randn(Bl, sebc._D_total, device=dev)
 
     def unpack(i):
-        torch.ops.tbe_hip.pooled_exchange_unpack(recv, lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"],
-                                                 lay["slab_offset"], lay["slab_stride"], Bl, sebc._D_total, sebc._vec_ok, 1.0)
+        sebc._unpack_pooled(recv, Bl)
 
     def pack(i):
-        torch.ops.tbe_hip.pooled_exchange_pack(gout, lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"],
-                                               lay["slab_offset"], lay["slab_stride"], lay["recv_numel"], sebc._vec_ok, 1.0 / W)
+        sebc._pack_pooled(gout, 1.0 / W)
 
     us["pooled_exchange_unpack"] = events(unpack, args.iters)
     us["pooled_exchange_pack"] = events(pack, args.iters)

@@ -13,7 +13,6 @@ from torch import nn
 
 from ..sparse.jagged_tensor import KeyedJaggedTensor
 from ..profiling import label
-from .comm_ops import alltoall_pooled, reduce_scatter_pooled
 from .types import Awaitable, LazyAwaitable, NoWait
 
 
@@ -35,6 +34,36 @@ def _get_recat(local_split: int, num_splits: int, stagger: int = 1,
     as_tensor = lambda x: torch.tensor(x, dtype=torch.int32, device=device)  # noqa: E731
     return torch.ops.fbgemm.expand_into_jagged_permute(as_tensor(recat), as_tensor(input_offset), as_tensor(output_offset),
                                                        output_offset[-1])
+
+
+def ids_per_destination(length_per_key: List[int], feats_per_rank: List[int]) -> List[int]:
+    """Ids this rank sends to each destination: `length_per_key` is in send order, feats_per_rank[r] keys for rank r."""
+    val_in, k = [], 0
+    for n in feats_per_rank:
+        val_in.append(sum(length_per_key[k:k + n]))
+        k += n
+    return val_in
+
+
+def exchange_ids(pg: dist.ProcessGroup, values: torch.Tensor, weights: Optional[torch.Tensor], val_out: List[int],
+                 val_in: List[int]):
+    """The second phase of every id exchange (dist_data.py:190, :213): starts the all-to-all of the 1-D ids, and of the
+    per-sample weights if given, with the split sizes the caller has worked out.  Returns (recv_values, recv_weights,
+    wait); wait() waits for both."""
+    recv_v = torch.empty(sum(val_out), dtype=values.dtype, device=values.device)
+    with label("## all2all_data:indices ##"):  # dist_data.py:190
+        work = [dist.all_to_all_single(recv_v, values, val_out, val_in, group=pg, async_op=True)]
+    recv_w = None
+    if weights is not None:
+        recv_w = torch.empty(sum(val_out), dtype=weights.dtype, device=weights.device)
+        with label("## all2all_data:weights ##"):  # dist_data.py:213
+            work.append(dist.all_to_all_single(recv_w, weights, val_out, val_in, group=pg, async_op=True))
+
+    def wait() -> None:
+        for w in work:
+            w.wait()
+
+    return recv_v, recv_w, wait
 
 
 def variable_batch_exchange(pg: dist.ProcessGroup, n_per_rank: List[int], val_in: List[int], lengths: torch.Tensor,
@@ -62,21 +91,12 @@ def variable_batch_exchange(pg: dist.ProcessGroup, n_per_rank: List[int], val_in
             val_out = [int(cum[r + 1] - cum[r]) for r in range(W)]
         else:
             val_out = [0] * W
-    recv_v = torch.empty(sum(val_out), dtype=values.dtype, device=dev)
-    with label("## all2all_data:indices ##"):  # dist_data.py:190
-        wk = dist.all_to_all_single(recv_v, values, val_out, list(val_in), group=pg, async_op=True)
-    recv_w, wk2 = None, None
-    if weights is not None:
-        recv_w = torch.empty(sum(val_out), dtype=weights.dtype, device=dev)
-        with label("## all2all_data:weights ##"):  # dist_data.py:213
-            wk2 = dist.all_to_all_single(recv_w, weights, val_out, list(val_in), group=pg, async_op=True)
+    recv_v, recv_w, wait = exchange_ids(pg, values, weights, val_out, list(val_in))
     with label("## all2all_data:recat_permute_gen ##"):  # dist_data.py:67, while the ids are on the links
         recat = _get_recat(F_local, W, stagger, dev, bpr)
 
     def finish():
-        wk.wait()
-        if wk2 is not None:
-            wk2.wait()
+        wait()
         if recat.numel() == 0:  # no local feature, or no sample anywhere: nothing to reorder
             return recv_l, recv_v, recv_w
         with label("## all2all_data:recat_values ##"):  # dist_data.py:246
@@ -114,15 +134,11 @@ class KJTAllToAll(nn.Module):
         B = kjt.stride()
         F_local = self._splits[me]
         lengths, values, weights = kjt.lengths(), kjt.values(), kjt.weights_or_none()
-        lpk = kjt.length_per_key()
         keys = kjt.keys()
         start = sum(self._splits[:me])
         local_keys = keys[start:start + F_local]
+        val_in = ids_per_destination(kjt.length_per_key(), self._splits)
         if self._variable_batch_size:
-            val_in, k = [], 0
-            for s in self._splits:
-                val_in.append(sum(lpk[k:k + s]))
-                k += s
             bpr, finish_var = variable_batch_exchange(pg, self._splits, val_in, lengths, values, weights, B, self._stagger)
 
             def finish_variable() -> KeyedJaggedTensor:
@@ -133,22 +149,11 @@ class KJTAllToAll(nn.Module):
         len_in = [s * B for s in self._splits]
         recv_l = torch.empty(W * F_local * B, dtype=lengths.dtype, device=lengths.device)
         dist.all_to_all_single(recv_l, lengths, [F_local * B] * W, len_in, group=pg)
-        val_in, k = [], 0
-        for s in self._splits:
-            val_in.append(sum(lpk[k:k + s]))
-            k += s
         val_out = recv_l.view(W, -1).sum(dim=1).cpu().tolist()
-        recv_v = torch.empty(sum(val_out), dtype=values.dtype, device=values.device)
-        wk = dist.all_to_all_single(recv_v, values, val_out, val_in, group=pg, async_op=True)
-        recv_w, wk2 = None, None
-        if weights is not None:
-            recv_w = torch.empty(sum(val_out), dtype=weights.dtype, device=weights.device)
-            wk2 = dist.all_to_all_single(recv_w, weights, val_out, val_in, group=pg, async_op=True)
+        recv_v, recv_w, wait = exchange_ids(pg, values, weights, val_out, val_in)
 
         def finish() -> KeyedJaggedTensor:
-            wk.wait()
-            if wk2 is not None:
-                wk2.wait()
+            wait()
             if F_local == 0:
                 return KeyedJaggedTensor(keys=[], values=recv_v, weights=recv_w, lengths=recv_l, stride=W * B)
             l2, v2, w2 = torch.ops.fbgemm.permute_2D_sparse_data(
@@ -171,6 +176,8 @@ class PooledEmbeddingsAllToAll(nn.Module):
         W = dist.get_world_size(self._pg)
         if batch_size_per_rank is None:
             batch_size_per_rank = [local_embs.shape[0] // W] * W
+        from .comm_ops import alltoall_pooled  # (not at module level: comm_ops -> embeddingbag -> this module)
+
         aw = alltoall_pooled(local_embs, batch_size_per_rank, self._dims, self._dim_sum_per_rank_tensor, None, self._pg)
         if not self._callbacks:
             return aw
@@ -194,4 +201,6 @@ class PooledEmbeddingsReduceScatter(nn.Module):
     def forward(self, local_embs: torch.Tensor) -> Awaitable[torch.Tensor]:
         W = dist.get_world_size(self._pg)
         B_l = local_embs.shape[0] // W
+        from .comm_ops import reduce_scatter_pooled  # (see PooledEmbeddingsAllToAll.forward)
+
         return reduce_scatter_pooled([local_embs[r * B_l:(r + 1) * B_l] for r in range(W)], self._pg)

@@ -32,6 +32,7 @@ from torch import nn
 
 from ..modules.embedding_configs import EmbeddingConfig, sharded_tables_precision
 from ..sparse.jagged_tensor import JaggedTensor, KeyedJaggedTensor
+from .dist_data import exchange_ids, ids_per_destination
 from .planner import rw_block_size, rw_shard_rows
 from .types import Awaitable, LazyAwaitable, NoWait, ParameterSharding, ShardingEnv, ShardingType
 
@@ -243,8 +244,8 @@ class ShardedEmbeddingCollection(nn.Module):
             recv_l = torch.empty(W * Frw * B, dtype=nl.dtype, device=nl.device)
             dist.all_to_all_single(recv_l, nl, [Frw * B] * W, [Frw * B] * W, group=pg)
             val_out = recv_l.view(W, -1).sum(dim=1).cpu().tolist()
-            recv_v = torch.empty(sum(val_out), dtype=ni.dtype, device=ni.device)
-            dist.all_to_all_single(recv_v, ni, val_out, val_in, group=pg)
+            recv_v, _, wait = exchange_ids(pg, ni, None, val_out, val_in)
+            wait()
         else:
             recv_l, recv_v, val_in, val_out = nl, ni, None, None
         offsets = torch.ops.fbgemm.asynchronous_complete_cumsum(recv_l).long()
@@ -269,17 +270,13 @@ class ShardedEmbeddingCollection(nn.Module):
         order = [pos[self._feature_names[g]] for g in self._send_order]
         sent = features if order == list(range(len(features.keys()))) else features.permute(order)
         lengths, values = sent.lengths(), sent.values()
-        lpk = sent.length_per_key()
-        val_in, k = [], 0
-        for n in self._send_per_rank:
-            val_in.append(sum(lpk[k:k + n]))
-            k += n
+        val_in = ids_per_destination(sent.length_per_key(), self._send_per_rank)
         if W > 1:
             recv_l = torch.empty(W * self._F_local * B, dtype=lengths.dtype, device=lengths.device)
             dist.all_to_all_single(recv_l, lengths, [self._F_local * B] * W, [n * B for n in self._send_per_rank], group=pg)
             val_out = recv_l.view(W, -1).sum(dim=1).cpu().tolist() if self._F_local else [0] * W
-            recv_v = torch.empty(sum(val_out), dtype=values.dtype, device=values.device)
-            dist.all_to_all_single(recv_v, values, val_out, val_in, group=pg)
+            recv_v, _, wait = exchange_ids(pg, values, None, val_out, val_in)
+            wait()
         else:
             recv_l, recv_v, val_out = lengths, values, val_in
         D = self.embedding_dim

@@ -52,7 +52,9 @@ from ..modules.embedding_modules import EmbeddingBagCollection
 from ..profiling import label
 from ..sparse.jagged_tensor import KeyedJaggedTensor, KeyedTensor
 from . import _device_ops  # noqa: F401  (registers torch.ops.tbe_hip.*)
-from .planner import rw_block_size, rw_shard_rows
+from .dist_data import exchange_ids, ids_per_destination, variable_batch_exchange
+from .planner import rw_shard_rows
+from .sharding_geometry import _LocalTable, sharding_geometry
 from .types import Awaitable, LazyAwaitable, NoWait, ParameterSharding, ShardingEnv, ShardingType
 
 GRADIENT_DIVISION = True  # torchrec/distributed/comm_ops.py:35-40
@@ -198,48 +200,6 @@ def unwrap_local(value):
     return value
 
 
-class _LocalTable:
-    """One table of this rank's fused lookup: a whole table (table-wise), a row block (row-wise) or ONE column shard of a
-    column-wise table (`column_shard` = (shard number in column order, shards of the table); columns
-    [col_offset, col_offset + cols) of every row)."""
-
-    def __init__(self, cfg: EmbeddingBagConfig, local_rows: int, row_offset: int, row_wise: bool,
-                 compute_kernel: str = "batched_fused", col_offset: int = 0, cols: Optional[int] = None,
-                 column_shard: Optional[Tuple[int, int]] = None) -> None:
-        self.cfg, self.local_rows, self.row_offset, self.row_wise = cfg, local_rows, row_offset, row_wise
-        self.compute_kernel = compute_kernel
-        self.col_offset, self.cols = col_offset, (cfg.embedding_dim if cols is None else cols)
-        self.column_shard = column_shard
-
-
-def _column_shards(name: str, cfg: EmbeddingBagConfig, ps: ParameterSharding, W: int) -> List[Tuple[int, int, int]]:
-    """[(first column, width, rank)] of a column-wise table in column order, validated: the shards tile [0, D) without
-    gaps or overlap, every shard has all rows, every rank exists.  ValueError names the table otherwise."""
-    spec, ranks = ps.sharding_spec, ps.ranks
-    if not spec or ranks is None or len(ranks) != len(spec):
-        raise ValueError(f"table {name}: a column-wise plan needs one rank per shard of its sharding_spec "
-                         f"({0 if ranks is None else len(ranks)} ranks, {len(spec or [])} shards)")
-    shards = []
-    for sm, r in zip(spec, ranks):
-        if list(sm.shard_offsets)[0] != 0 or list(sm.shard_sizes)[0] != cfg.num_embeddings:
-            raise ValueError(f"table {name}: column shard at {list(sm.shard_offsets)} of size {list(sm.shard_sizes)} does not "
-                             f"hold all {cfg.num_embeddings} rows")
-        if not 0 <= int(r) < W:
-            raise ValueError(f"table {name}: column shard at column {sm.shard_offsets[1]} is placed on rank {r}, "
-                             f"outside the world of {W}")
-        shards.append((int(sm.shard_offsets[1]), int(sm.shard_sizes[1]), int(r)))
-    shards.sort(key=lambda x: x[0])
-    col = 0
-    for c, w, _ in shards:
-        if c != col or w <= 0:
-            raise ValueError(f"table {name}: column shards {[(c, w) for c, w, _ in shards]} do not tile [0, {cfg.embedding_dim}) "
-                             f"(gap or overlap at column {col})")
-        col += w
-    if col != cfg.embedding_dim:
-        raise ValueError(f"table {name}: column shards {[(c, w) for c, w, _ in shards]} do not tile [0, {cfg.embedding_dim})")
-    return shards
-
-
 class SparseFeaturesDist:
     """What input_dist hands to compute (embedding_types.py `SparseFeatures`, after the a2a):
     ids in [src rank][local feature][sample] order + offsets for the local TBE."""
@@ -295,11 +255,21 @@ class _ExchangeWait(torch.autograd.Function):
 
 
 class _ExchangeState:
-    """One step's pooled exchange: buffers, split sizes and in-flight work handles."""
+    """One step's pooled exchange: buffers, split sizes and in-flight work handles.
 
-    def __init__(self, owner: "ShardedEmbeddingBagCollection", B: int) -> None:
-        self.o, self.B = owner, B
-        self.lay = owner._exchange_layout(B)
+    `B` is the per-rank batch size, or the list of every rank's own (sharding/vb_tw_sharding.py, vb_cw_sharding.py in the
+    reference).  The lookup then ran once at batch sum(B_r) over [local piece][src rank][sample] ids, so the rows for
+    destination r are the contiguous block [sum(B[:r]), sum(B[:r + 1])) of its [sum(B_r), D_local] output: the all-to-all
+    sends B_r * D_local straight from that matrix and receives B_me * D_local_src per source.  The exchange kernels depend
+    on the RECEIVING rank's batch only: unpack / pack run with the layout of B_me, as in the fixed-batch exchange."""
+
+    def __init__(self, owner: "ShardedEmbeddingBagCollection", B) -> None:
+        bpr = list(B) if isinstance(B, (list, tuple)) else None
+        self.o, self.B = owner, (B if bpr is None else bpr[owner._rank])
+        self.lay = owner._exchange_layout(self.B)
+        self.variable = bpr is not None
+        self.send_splits = self.lay["send_splits"] if bpr is None else [b * owner._D_local for b in bpr]
+        self.grad_rows = owner._world_size * self.B if bpr is None else sum(bpr)  # rows of the lookup's output and gradient
         self.recv_fwd: Optional[torch.Tensor] = None
         self.work = None
         self.grad_recv: Optional[torch.Tensor] = None
@@ -313,14 +283,14 @@ class _ExchangeState:
         o, lay = self.o, self.lay
         # (the persistent buffers serve the explicit train step only: an eval forward between two steps must not receive
         # into the buffer that holds the next step's prefetched embeddings)
-        static = o._static_exchange if (allow_static and o._static_exchange is not None
+        static = o._static_exchange if (allow_static and not self.variable and o._static_exchange is not None
                                         and o._static_exchange["B"] == self.B) else None
         self.static = static  # persistent receive / send buffers: the owner's graphs unpack / pack (set_graph_exchange)
         self.recv_fwd = (static["recv_fwd"] if static is not None
                          else torch.empty(lay["recv_numel"], dtype=torch.float32, device=emb.device))
         with label("## alltoall_fwd_single ##"):  # comm_ops.py:489
             self.work = dist.all_to_all_single(self.recv_fwd, emb.reshape(-1), output_split_sizes=lay["recv_splits"],
-                                               input_split_sizes=lay["send_splits"], group=o._pg, async_op=True)
+                                               input_split_sizes=self.send_splits, group=o._pg, async_op=True)
 
     def output_destination(self) -> torch.Tensor:
         """The [B, sum D] tensor finish_forward() unpacks into: the consumer's own buffer (e.g. the static input of a
@@ -351,16 +321,11 @@ class _ExchangeState:
         with label("## alltoall_fwd_wait ##"):
             self.work.wait()
         self.work = None
-        lay = self.lay
         if self._dest is not None or (self.o._output_buffer is not None
                                       and self.o._output_buffer.numel() == self.B * self.o._D_total):
             dest, self._dest = self.output_destination(), None
-            return torch.ops.tbe_hip.pooled_exchange_unpack_into(
-                self.recv_fwd, lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"], lay["slab_offset"],
-                lay["slab_stride"], self.B, self.o._D_total, self.o._vec_ok, 1.0, dest)
-        return torch.ops.tbe_hip.pooled_exchange_unpack(
-            self.recv_fwd, lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"], lay["slab_offset"],
-            lay["slab_stride"], self.B, self.o._D_total, self.o._vec_ok, 1.0)
+            return self.o._unpack_pooled(self.recv_fwd, self.B, dest)
+        return self.o._unpack_pooled(self.recv_fwd, self.B)
 
     def dummy_grad(self) -> torch.Tensor:
         # gradient placeholder for recv_fwd: its real gradient travels through the all-to-all
@@ -368,13 +333,10 @@ class _ExchangeState:
 
     def start_backward(self, grad_out: torch.Tensor) -> None:
         o, lay = self.o, self.lay
-        scale = 1.0 / o._world_size if GRADIENT_DIVISION else 1.0
-        send = torch.ops.tbe_hip.pooled_exchange_pack(
-            grad_out, lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"], lay["slab_offset"],
-            lay["slab_stride"], lay["recv_numel"], o._vec_ok, scale)
-        self.grad_recv = torch.empty(lay["send_numel"], dtype=torch.float32, device=grad_out.device)
-        with label("## alltoall_bwd_single ##"):  # comm_ops.py:591
-            self.bwd_work = dist.all_to_all_single(self.grad_recv, send, output_split_sizes=lay["send_splits"],
+        send = o._pack_pooled(grad_out, 1.0 / o._world_size if GRADIENT_DIVISION else 1.0)
+        self.grad_recv = torch.empty(self.grad_rows * o._D_local, dtype=torch.float32, device=grad_out.device)
+        with label("## alltoall_bwd_single ##"):  # comm_ops.py:591, the forward's two split lists swapped
+            self.bwd_work = dist.all_to_all_single(self.grad_recv, send, output_split_sizes=self.send_splits,
                                                    input_split_sizes=lay["recv_splits"], group=o._pg, async_op=True)
         self._send_keepalive = send
 
@@ -387,7 +349,7 @@ class _ExchangeState:
         self.bwd_work = None
         self._half_bwd_work = []
         self._send_keepalive = None
-        return self.grad_recv.view(self.o._world_size * self.B, self.o._D_local)
+        return self.grad_recv.view(self.grad_rows, self.o._D_local)
 
     # ---- the same exchange in two half-batches (rows [0, B/2) and [B/2, B) of every rank's local batch) -------------
     # Each half is its own all-to-all (list form: the pieces are row ranges of the slabs, contiguous but not adjacent),
@@ -417,11 +379,9 @@ class _ExchangeState:
         with label("## alltoall_fwd_wait ##"):
             self._half_work[h].wait()
         self._half_work[h] = None
-        layh, Bh, o = self.lay_half, self.B // 2, self.o
+        Bh = self.B // 2
         rows = self.output_destination()[h * Bh:(h + 1) * Bh]
-        torch.ops.tbe_hip.pooled_exchange_unpack_into(
-            self._half_recv[h], layh["feat_out_col"], layh["feat_src"], layh["feat_slab_col"], layh["slab_offset"],
-            layh["slab_stride"], Bh, o._D_total, o._vec_ok, 1.0, rows)
+        self.o._unpack_pooled(self._half_recv[h], Bh, rows)
         self._half_recv[h] = None
         if h == 1:
             self._emb_keepalive = None
@@ -431,10 +391,7 @@ class _ExchangeState:
         """grad_rows: [B/2, sum D] gradient of rows [h B/2, (h + 1) B/2) of the pooled output, contiguous."""
         o, W, B = self.o, self.o._world_size, self.B
         Bh, layh = B // 2, self.lay_half
-        scale = 1.0 / W if GRADIENT_DIVISION else 1.0
-        send = torch.ops.tbe_hip.pooled_exchange_pack(
-            grad_rows, layh["feat_out_col"], layh["feat_src"], layh["feat_slab_col"], layh["slab_offset"],
-            layh["slab_stride"], layh["recv_numel"], o._vec_ok, scale)
+        send = o._pack_pooled(grad_rows, 1.0 / W if GRADIENT_DIVISION else 1.0)
         if self.grad_recv is None:
             self.grad_recv = torch.empty(self.lay["send_numel"], dtype=torch.float32, device=grad_rows.device)
         dst = self.grad_recv.view(W, B, o._D_local)
@@ -443,45 +400,6 @@ class _ExchangeState:
                                    group=o._pg, async_op=True)
         self._half_bwd_work.append(work)
         self._half_send_keepalive.append(send)
-
-
-class _VariableExchangeState(_ExchangeState):
-    """The pooled exchange when every rank brings its own batch size (sharding/vb_tw_sharding.py, vb_cw_sharding.py in the
-    reference).  The lookup ran once at batch sum(B_r) over [local piece][src rank][sample] ids, so the rows for
-    destination r are the contiguous block [sum(B[:r]), sum(B[:r + 1])) of its [sum(B_r), D_local] output: the all-to-all
-    sends B_r * D_local straight from that matrix and receives B_me * D_local_src per source.  The exchange kernels depend
-    on the RECEIVING rank's batch only: unpack / pack run with the layout of B_me, as in the fixed-batch exchange."""
-
-    def __init__(self, owner: "ShardedEmbeddingBagCollection", batch_size_per_rank: List[int]) -> None:
-        super().__init__(owner, batch_size_per_rank[owner._rank])
-        self.bpr = list(batch_size_per_rank)
-        self.send_splits = [b * owner._D_local for b in self.bpr]
-
-    def start_forward(self, emb: torch.Tensor, allow_static: bool = False) -> None:
-        o, lay = self.o, self.lay
-        self.recv_fwd = torch.empty(lay["recv_numel"], dtype=torch.float32, device=emb.device)
-        with label("## alltoall_fwd_single ##"):  # comm_ops.py:489
-            self.work = dist.all_to_all_single(self.recv_fwd, emb.reshape(-1), output_split_sizes=lay["recv_splits"],
-                                               input_split_sizes=self.send_splits, group=o._pg, async_op=True)
-
-    def start_backward(self, grad_out: torch.Tensor) -> None:
-        o, lay = self.o, self.lay
-        scale = 1.0 / o._world_size if GRADIENT_DIVISION else 1.0
-        send = torch.ops.tbe_hip.pooled_exchange_pack(
-            grad_out, lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"], lay["slab_offset"],
-            lay["slab_stride"], lay["recv_numel"], o._vec_ok, scale)
-        self.grad_recv = torch.empty(sum(self.send_splits), dtype=torch.float32, device=grad_out.device)
-        with label("## alltoall_bwd_single ##"):  # comm_ops.py:591, the forward's two split lists swapped
-            self.bwd_work = dist.all_to_all_single(self.grad_recv, send, output_split_sizes=self.send_splits,
-                                                   input_split_sizes=lay["recv_splits"], group=o._pg, async_op=True)
-        self._send_keepalive = send
-
-    def finish_backward(self) -> torch.Tensor:
-        with label("## alltoall_bwd_wait ##"):
-            self.bwd_work.wait()
-        self.bwd_work = None
-        self._send_keepalive = None
-        return self.grad_recv.view(sum(self.bpr), self.o._D_local)
 
 
 class _OutputAwaitable(LazyAwaitable):
@@ -632,129 +550,27 @@ class ShardedEmbeddingBagCollection(nn.Module):
         # tables of different pooling types (and dims, and placements) share ONE lookup per rank: pooling is
         # per-feature metadata of the kernels, not a reason for a second module + cat (the reference groups by
         # pooling / data type / compute kernel: embedding_sharding.py:393-490, embedding_lookup.py:219-253)
-        # ---- global feature list, in the collection's output order -----------------------------
-        self._feature_names: List[str] = []
-        g_table: List[int] = []
-        for t, c in enumerate(cfgs):
-            for f in c.feature_names:
-                self._feature_names.append(f)
-                g_table.append(t)
-        Fg = len(self._feature_names)
-        g_dim = [cfgs[t].embedding_dim for t in g_table]
-        self._lengths_per_embedding = g_dim
-        self._D_total = sum(g_dim)
-        # ---- who holds what --------------------------------------------------------------------
-        kind: List[int] = []  # per table: -3 column-wise, -2 replicated, -1 row-wise, else owning rank
-        cw_shards: Dict[int, List[Tuple[int, int, int]]] = {}  # column-wise table -> [(first column, width, rank)]
-        for t, c in enumerate(cfgs):
-            ps = table_name_to_parameter_sharding[c.name]
-            if ps.sharding_type == ShardingType.DATA_PARALLEL.value:
-                kind.append(-2)
-            elif ps.sharding_type == ShardingType.ROW_WISE.value:
-                if self._variable_batch:
-                    raise NotImplementedError(
-                        f"table {c.name}: row_wise sharding in a variable_batch_size collection (the reference has no "
-                        "variable-batch row-wise sharding either); shard it table-wise or column-wise, or replicate it")
-                kind.append(-1)
-            elif ps.sharding_type == ShardingType.TABLE_WISE.value:
-                kind.append(int(ps.ranks[0]))
-            elif ps.sharding_type in (ShardingType.COLUMN_WISE.value, ShardingType.TABLE_COLUMN_WISE.value):
-                # (one node, no host hierarchy: the two types are the same thing here)
-                kind.append(-3)
-                cw_shards[t] = _column_shards(c.name, c, ps, W)
-                if (ps.compute_kernel == "batched_fused_uvm_caching" and len({w for _, w, _ in cw_shards[t]}) > 1):
-                    raise NotImplementedError(
-                        f"table {c.name}: column shards of different widths {[w for _, w, _ in cw_shards[t]]} behind the HBM row "
-                        "cache (batched_fused_uvm_caching): the cache holds rows of ONE width; choose a min_partition that "
-                        "divides the embedding dim, or another compute kernel")
-            else:
-                raise NotImplementedError(f"sharding type {ps.sharding_type} is outside the MI355X hot path "
-                                          "(table_wise / row_wise / column_wise / data_parallel)")
-        self._table_kind = kind
-        self._has_cw = bool(cw_shards)
-        # LAMB, PARTIAL_ROWWISE_LAMB and LARS_SGD scale a row's step by norms over the WHOLE row, PARTIAL_ROWWISE_ADAM keeps
-        # one second moment per row: a column shard sees only its columns, so the result would depend on the sharding
-        # (table-wise and row-wise shards hold whole rows and are invariant).  Gradient clipping is element-wise: allowed.
-        opt = (fused_params or {}).get("optimizer")
-        if cw_shards and getattr(opt, "name", None) in ("LAMB", "PARTIAL_ROWWISE_ADAM", "PARTIAL_ROWWISE_LAMB", "LARS_SGD"):
-            raise NotImplementedError(
-                f"column-wise table(s) {[cfgs[t].name for t in cw_shards]} with optimizer {opt.name}: its row norms / row-wise "
-                "state are taken over a whole row, which a column shard does not hold; shard these tables table-wise or "
-                "row-wise, or use an element-wise optimizer")
-        if self._has_cw and rw_input_dist == "bucketize":
-            raise NotImplementedError(
-                "rw_input_dist='bucketize' with column-wise tables "
-                f"({[cfgs[t].name for t in cw_shards]}): the bucketized input dist is not built for column shards; use "
-                "'windows' (or 'auto', which does) for such collections")
-        # ---- pieces: the unit of everything below.  A piece is (feature, column shard); tables that are not column-wise
-        #      have ONE piece per feature, so piece number == feature number for them and every list is what it was -------
-        p_feat: List[int] = []   # feature of the piece
-        p_col: List[int] = []    # first column of the piece inside its feature
-        p_dim: List[int] = []    # width
-        p_kind: List[int] = []   # -2 replicated, -1 row-wise, else owning rank
-        p_shard: List[int] = []  # column shard number (0 for whole-width pieces)
-        for g in range(Fg):
-            t = g_table[g]
-            for i, (c0, w, r) in enumerate(cw_shards[t] if kind[t] == -3 else [(0, g_dim[g], kind[t])]):
-                p_feat.append(g)
-                p_col.append(c0)
-                p_dim.append(w)
-                p_kind.append(r)
-                p_shard.append(i)
-        P = len(p_feat)
-        self._piece_feat, self._piece_dim = p_feat, p_dim
-        # local piece list of every rank: row-wise features first (same columns on every rank).  The ids of a feature
-        # travel to every rank that holds one of its pieces — twice to a rank that holds two (the reference duplicates the
-        # feature per shard too: sharding/cw_sharding.py _id_list_features_per_rank)
-        rw_feats = [p for p in range(P) if p_kind[p] == -1]
-        self._dp_feats = [g for g in range(Fg) if kind[g_table[g]] == -2]
-        self._sharded_feats = [g for g in range(Fg) if kind[g_table[g]] != -2]
-        local_feats = [rw_feats + [p for p in range(P) if p_kind[p] == r] for r in range(W)]
-        self._local_feats = local_feats
-        self._D_local_per_rank = [sum(p_dim[p] for p in lf) for lf in local_feats]
-        self._D_local = self._D_local_per_rank[me]
+        # who holds what, for all ranks: sharding_geometry.py (pure lists; every refusal of a plan is raised there)
+        geo = self._geometry = sharding_geometry(cfgs, table_name_to_parameter_sharding, W, self._variable_batch, rw_input_dist,
+                                                 getattr((fused_params or {}).get("optimizer"), "name", None))
+        self._feature_names, self._lengths_per_embedding, self._D_total = geo.feature_names, geo.feature_dim, geo.D_total
+        kind = self._table_kind = geo.table_kind
+        self._has_cw = bool(geo.cw_shards)
+        self._cw_shards = {cfgs[t].name: sh for t, sh in geo.cw_shards.items()}
+        self._dp_feats = geo.dp_feats
+        local_feats = self._local_feats = geo.local_pieces  # per rank, in units of PIECES (module docstring)
+        self._D_local_per_rank, self._D_local = geo.D_local_per_rank, geo.D_local_per_rank[me]
         self._F_local = len(local_feats[me])
-        self._send_feature_order = [p_feat[p] for lf in local_feats for p in lf]
-        self._send_feats_per_rank = [len(lf) for lf in local_feats]
-        # bucketized row-wise input dist: row-wise features (bucketized, one block per destination) and the table-wise
-        # features in destination order travel as separate pieces of one exchange
-        rw_feats = [p_feat[p] for p in rw_feats]
-        self._rw_feats = rw_feats
-        self._tw_send_order = [p_feat[p] for r in range(W) for p in local_feats[r] if p_kind[p] != -1]
-        self._tw_per_rank = [sum(1 for p in local_feats[r] if p_kind[p] != -1) for r in range(W)]
-        self._rw_block_sizes = torch.tensor([rw_block_size(cfgs[g_table[g]].num_embeddings, W) for g in rw_feats],
-                                            dtype=torch.int64, device=self._device if self._device.type != "meta" else "cpu")
-        self._rw_mean = any(pooling_type_to_pooling_mode(cfgs[g_table[g]].pooling) == 1 for g in rw_feats)
-        if self._rw_mean and rw_input_dist == "bucketize":
-            raise NotImplementedError(
-                "rw_input_dist='bucketize' with MEAN-pooled row-wise tables: a rank would divide its partial sum by the number "
-                "of ids in ITS row block, not by the bag length; use 'windows' (or 'auto', which does) for such collections")
-        # exchange descriptors (batch-independent part), one entry per piece: the kernels (csrc/pooled_exchange.hip) copy
-        # column ranges and do not care whether a range is a whole feature
-        feat_src, feat_slab_col = [0] * P, [0] * P
-        for r in range(W):
-            col = 0
-            for p in local_feats[r]:
-                if p_kind[p] == -1:
-                    feat_src[p], feat_slab_col[p] = -1, col
-                elif p_kind[p] == r:
-                    feat_src[p], feat_slab_col[p] = r, col
-                col += p_dim[p]
-        for p in range(P):
-            if p_kind[p] == -2:
-                feat_src[p] = -2
-        out_col = [0]
-        for d in g_dim:
-            out_col.append(out_col[-1] + d)
-        self._out_col = out_col
-        # the pieces of a feature are consecutive in the output matrix: out_col(piece) = out_col(feature) + first column
-        piece_out_col = [out_col[p_feat[p]] + p_col[p] for p in range(P)]
+        self._send_feature_order, self._send_feats_per_rank = geo.send_feature_order, geo.send_feats_per_rank
+        self._rw_feats, self._rw_mean = geo.rw_feats, geo.rw_mean
+        self._tw_send_order, self._tw_per_rank, self._tw_first = geo.tw_send_order, geo.tw_per_rank, geo.tw_first
         dev = self._device
-        self._feat_out_col = torch.tensor(piece_out_col + [self._D_total], dtype=torch.int32, device=dev)
-        self._feat_src = torch.tensor(feat_src, dtype=torch.int32, device=dev)
-        self._feat_slab_col = torch.tensor(feat_slab_col, dtype=torch.int32, device=dev)
-        self._slab_stride = torch.tensor(self._D_local_per_rank, dtype=torch.int32, device=dev)
-        self._vec_ok = all(d % 4 == 0 for d in p_dim)
+        self._rw_block_sizes = torch.tensor(geo.rw_block_sizes, dtype=torch.int64, device=dev if dev.type != "meta" else "cpu")
+        self._feat_out_col = torch.tensor(geo.piece_out_col + [geo.D_total], dtype=torch.int32, device=dev)
+        self._feat_src = torch.tensor(geo.feat_src, dtype=torch.int32, device=dev)
+        self._feat_slab_col = torch.tensor(geo.feat_slab_col, dtype=torch.int32, device=dev)
+        self._slab_stride = torch.tensor(geo.D_local_per_rank, dtype=torch.int32, device=dev)
+        self._vec_ok = geo.vec_ok
         self._layout_cache: Dict[int, Dict[str, Any]] = {}
         # state_dict() / fused-optimizer state as torch ShardedTensors whenever a process group exists (the reference's
         # behaviour); False hands out the plain local shards
@@ -766,25 +582,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
         self._static_exchange: Optional[Dict[str, Any]] = None  # see set_graph_exchange
         self._weights_epoch = 0  # bumped by everything that rewrites tables outside a train step (see ExplicitLookupStep.epoch)
         # ---- local tables + TBE ----------------------------------------------------------------
-        self._local_tables: List[_LocalTable] = []
-        local_table_index: Dict[Tuple[int, int], int] = {}  # (table, column shard) -> local TBE table
-        for p in local_feats[me]:
-            t = g_table[p_feat[p]]
-            if (t, p_shard[p]) in local_table_index:
-                continue
-            c = cfgs[t]
-            ck = table_name_to_parameter_sharding[c.name].compute_kernel
-            if kind[t] == -1:
-                rows = rw_shard_rows(c.num_embeddings, W)[me]
-                self._local_tables.append(_LocalTable(c, rows, me * rw_block_size(c.num_embeddings, W), True, ck))
-            elif kind[t] == -3:  # each local column shard is its own TBE table [rows, width]
-                self._local_tables.append(_LocalTable(c, c.num_embeddings, 0, False, ck, p_col[p], p_dim[p],
-                                                      (p_shard[p], len(cw_shards[t]))))
-            else:
-                self._local_tables.append(_LocalTable(c, c.num_embeddings, 0, False, ck))
-            local_table_index[(t, p_shard[p])] = len(self._local_tables) - 1
-        self._cw_shards = {cfgs[t].name: sh for t, sh in cw_shards.items()}
-        ftm_local = [local_table_index[(g_table[p_feat[p]], p_shard[p])] for p in local_feats[me]]
+        self._local_tables, ftm_local = geo.local_tables(me)
         # row-wise shards see un-bucketized GLOBAL ids: (first global row, global rows) per local feature
         win_first = [self._local_tables[i].row_offset for i in ftm_local]
         win_global = [self._local_tables[i].cfg.num_embeddings for i in ftm_local]
@@ -825,11 +623,12 @@ class ShardedEmbeddingBagCollection(nn.Module):
         else:
             self._optim = None
         # global-column addressing of the sharded features for the world_size == 1 "write into one buffer" path
-        self._sharded_out_off = torch.tensor([piece_out_col[p] for p in local_feats[me]], dtype=torch.int64, device=dev)
+        self._sharded_out_off = torch.tensor([geo.piece_out_col[p] for p in local_feats[me]], dtype=torch.int64, device=dev)
         # ---- data-parallel (replicated) tables -------------------------------------------------------
         self._dp_module = None
         self._dp_table_ids: List[int] = []
         if self._dp_feats:
+            g_table = geo.feature_table
             for g in self._dp_feats:
                 if g_table[g] not in self._dp_table_ids:
                     self._dp_table_ids.append(g_table[g])
@@ -843,7 +642,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
             self._dp_module._owned_by_sharded_module = True  # its weights load / save as embedding_bags.<t>.weight
             for t, w in zip(self._dp_table_ids, self._dp_module.split_embedding_weights()):
                 w.uniform_(cfgs[t].get_weight_init_min(), cfgs[t].get_weight_init_max())
-            self._dp_out_off = torch.tensor([out_col[g] for g in self._dp_feats], dtype=torch.int64, device=dev)
+            self._dp_out_off = torch.tensor([geo.out_col[g] for g in self._dp_feats], dtype=torch.int64, device=dev)
 
     def set_output_buffer(self, buf: Optional[torch.Tensor]) -> None:
         """A persistent float32 buffer of B_local * sum(D) elements that receives the pooled output of every
@@ -884,14 +683,10 @@ class ShardedEmbeddingBagCollection(nn.Module):
         scale = 1.0 / self._world_size if GRADIENT_DIVISION else 1.0
 
         def unpack() -> None:
-            torch.ops.tbe_hip.pooled_exchange_unpack_into(
-                st["recv_fwd"], lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"], lay["slab_offset"],
-                lay["slab_stride"], B, self._D_total, self._vec_ok, 1.0, self._alias_output_buffer(B))
+            self._unpack_pooled(st["recv_fwd"], B, self._alias_output_buffer(B))
 
         def pack(grad: torch.Tensor) -> None:
-            torch.ops.tbe_hip.pooled_exchange_pack_into(
-                grad.view(B, self._D_total), lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"], lay["slab_offset"],
-                lay["slab_stride"], self._vec_ok, scale, st["send_bwd"])
+            self._pack_pooled(grad.view(B, self._D_total), scale, st["send_bwd"])
 
         return unpack, pack
 
@@ -1117,16 +912,35 @@ class ShardedEmbeddingBagCollection(nn.Module):
             self._layout_cache[B] = lay
         return lay
 
+    def _unpack_pooled(self, recv: torch.Tensor, B: int, dest: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The received slabs of a batch of B as [B, sum D] (csrc/pooled_exchange.hip): into `dest`, or a fresh tensor."""
+        lay = self._exchange_layout(B)
+        args = (recv, lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"], lay["slab_offset"], lay["slab_stride"], B,
+                self._D_total, self._vec_ok, 1.0)
+        if dest is None:
+            return torch.ops.tbe_hip.pooled_exchange_unpack(*args)
+        return torch.ops.tbe_hip.pooled_exchange_unpack_into(*args, dest)
+
+    def _pack_pooled(self, grad: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The [B, sum D] gradient times `scale` as the slabs the sources expect: into `out`, or a fresh send buffer."""
+        lay = self._exchange_layout(grad.shape[0])
+        args = (grad, lay["feat_out_col"], lay["feat_src"], lay["feat_slab_col"], lay["slab_offset"], lay["slab_stride"])
+        if out is None:
+            return torch.ops.tbe_hip.pooled_exchange_pack(*args, lay["recv_numel"], self._vec_ok, scale)
+        return torch.ops.tbe_hip.pooled_exchange_pack_into(*args, self._vec_ok, scale, out)
+
     # ---- input dist -----------------------------------------------------------------------------
-    def _send_perm(self, keys: List[str]) -> torch.Tensor:
-        ck = ("perm", tuple(keys))
+    def _key_positions(self, what: str, feats: List[int], keys: List[str]) -> Tuple[List[int], torch.Tensor]:
+        """Where the global features `feats` stand among a KeyedJaggedTensor's `keys`: (positions, the same as a device int32
+        tensor), cached per (what, keys)."""
+        ck = (what, tuple(keys))
         hit = self._kjt_cache.get(ck)
         if hit is None:
             pos = {k: i for i, k in enumerate(keys)}
             missing = [n for n in self._feature_names if n not in pos]
             if missing:
                 raise KeyError(f"KeyedJaggedTensor is missing features {missing[:3]}...")
-            order = [pos[self._feature_names[g]] for g in self._send_feature_order]
+            order = [pos[self._feature_names[g]] for g in feats]
             hit = (order, torch.tensor(order, dtype=torch.int32, device=self._device))
             self._kjt_cache[ck] = hit
         return hit
@@ -1136,14 +950,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
         if self._dp_module is None:
             return None
         keys = features.keys()
-        ck = ("dp", tuple(keys))
-        hit = self._kjt_cache.get(ck)
-        if hit is None:
-            pos = {k: i for i, k in enumerate(keys)}
-            order = [pos[self._feature_names[g]] for g in self._dp_feats]
-            hit = (order, torch.tensor(order, dtype=torch.int32, device=self._device))
-            self._kjt_cache[ck] = hit
-        order, order_t = hit
+        order, order_t = self._key_positions("dp", self._dp_feats, keys)
         B = features.stride()
         fixed = features.fixed_lengths()
         weights = features.weights_or_none() if self._is_weighted else None
@@ -1186,25 +993,6 @@ class ShardedEmbeddingBagCollection(nn.Module):
                 self._emb_module.set_row_windows(None)
         self._rw_mode_active = mode
 
-    def _bucketize_perm(self, keys: List[str]):
-        ck = ("bkt", tuple(keys))
-        hit = self._kjt_cache.get(ck)
-        if hit is None:
-            pos = {k: i for i, k in enumerate(keys)}
-            missing = [n for n in self._feature_names if n not in pos]
-            if missing:
-                raise KeyError(f"KeyedJaggedTensor is missing features {missing[:3]}...")
-            rw_pos = [pos[self._feature_names[g]] for g in self._rw_feats]
-            tw_pos = [pos[self._feature_names[g]] for g in self._tw_send_order]
-            dev = self._device
-            tw_first = [0]
-            for n in self._tw_per_rank:
-                tw_first.append(tw_first[-1] + n)
-            hit = (rw_pos, torch.tensor(rw_pos, dtype=torch.int32, device=dev), tw_pos,
-                   torch.tensor(tw_pos, dtype=torch.int32, device=dev), tw_first)
-            self._kjt_cache[ck] = hit
-        return hit
-
     def _input_dist_bucketized(self, features: KeyedJaggedTensor, dp_in) -> Awaitable[SparseFeaturesDist]:
         """The reference's row-wise input dist (bucketize_kjt_before_all2all + KJTAllToAll: embedding_sharding.py:121-184,
         dist_data.py:137-524) folded into this collection's ONE exchange: the piece for destination r is
@@ -1213,7 +1001,9 @@ class ShardedEmbeddingBagCollection(nn.Module):
         jagged_tensor.py:502-509), then the ids (and per-sample weights).  The receiver's layout is the usual
         [src rank][local feature][sample]; row-wise ids arrive as LOCAL rows of this rank's block."""
         W, B = self._world_size, features.stride()
-        rw_pos, rw_pos_t, tw_pos, tw_pos_t, tw_first = self._bucketize_perm(features.keys())
+        rw_pos, rw_pos_t = self._key_positions("rw", self._rw_feats, features.keys())
+        tw_pos, tw_pos_t = self._key_positions("tw", self._tw_send_order, features.keys())
+        tw_first = self._tw_first
         n_rw = len(rw_pos)
         weighted = self._is_weighted and features.weights_or_none() is not None
         rw = features.permute(rw_pos, rw_pos_t)
@@ -1265,22 +1055,13 @@ class ShardedEmbeddingBagCollection(nn.Module):
         send_v = assemble(bi, tw.values() if tw is not None else None)
         send_w = assemble(bw, tw.weights() if tw is not None else None) if weighted else None
         if self._exchange:
-            recv_v = torch.empty(sum(val_out), dtype=send_v.dtype, device=send_v.device)
-            with label("## all2all_data:indices ##"):  # dist_data.py:190
-                wk = dist.all_to_all_single(recv_v, send_v, val_out, val_in, group=self._pg, async_op=True)
-            recv_w, wk2 = None, None
-            if send_w is not None:
-                recv_w = torch.empty(sum(val_out), dtype=send_w.dtype, device=send_w.device)
-                with label("## all2all_data:weights ##"):  # dist_data.py:213
-                    wk2 = dist.all_to_all_single(recv_w, send_w, val_out, val_in, group=self._pg, async_op=True)
+            recv_v, recv_w, wait = exchange_ids(self._pg, send_v, send_w, val_out, val_in)
         else:
-            recv_v, recv_w, wk, wk2 = send_v, send_w, None, None
+            recv_v, recv_w, wait = send_v, send_w, None
 
         def finish() -> SparseFeaturesDist:
-            if wk is not None:
-                wk.wait()
-            if wk2 is not None:
-                wk2.wait()
+            if wait is not None:
+                wait()
             offsets = torch.ops.fbgemm.asynchronous_complete_cumsum(recv_l).long()
             return SparseFeaturesDist(recv_v, offsets, recv_w, B, dp_in)
 
@@ -1291,10 +1072,8 @@ class ShardedEmbeddingBagCollection(nn.Module):
         D2H read of the id counts, ids and weights, recat with expand_into_jagged_permute + permute_1D_sparse_data).  The
         pieces travel in `_send_feature_order`, a column-wise feature once per shard as always; a local batch of 0 sends
         nothing and still takes part in every collective."""
-        from .dist_data import variable_batch_exchange
-
         B = features.stride()
-        order, _ = self._send_perm(features.keys())
+        order, _ = self._key_positions("send", self._send_feature_order, features.keys())
         weighted = self._is_weighted and features.weights_or_none() is not None
         if B > 0 and order:
             sent = features.permute(order, None)
@@ -1303,10 +1082,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
         else:
             lengths, values, lpk = features.lengths()[:0], features.values()[:0], [0] * len(order)
             weights = features.weights()[:0] if weighted else None
-        val_in, k = [], 0
-        for n in self._send_feats_per_rank:
-            val_in.append(sum(lpk[k:k + n]))
-            k += n
+        val_in = ids_per_destination(lpk, self._send_feats_per_rank)
         dp_in = None
         if self._dp_module is not None:
             if B > 0:
@@ -1332,7 +1108,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
         self._set_rw_mode(mode)
         if mode == "bucketize":
             return self._input_dist_bucketized(features, dp_in)
-        order, order_t = self._send_perm(features.keys())
+        order, order_t = self._key_positions("send", self._send_feature_order, features.keys())
         fixed = features.fixed_lengths()
         weights = features.weights_or_none() if self._is_weighted else None
         if fixed is not None and len(set(fixed)) == 1 and fixed[0] > 0:
@@ -1347,23 +1123,14 @@ class ShardedEmbeddingBagCollection(nn.Module):
             in_splits = [n * B * L for n in self._send_feats_per_rank]
             out_splits = [self._F_local * B * L] * W
             if self._exchange:
-                recv_v = torch.empty(sum(out_splits), dtype=send_v.dtype, device=send_v.device)
-                with label("## all2all_data:indices ##"):  # dist_data.py:190
-                    wk = dist.all_to_all_single(recv_v, send_v.view(-1), out_splits, in_splits, group=self._pg, async_op=True)
-                recv_w, wk2 = None, None
-                if send_w is not None:
-                    recv_w = torch.empty(sum(out_splits), dtype=send_w.dtype, device=send_w.device)
-                    with label("## all2all_data:weights ##"):  # dist_data.py:213
-                        wk2 = dist.all_to_all_single(recv_w, send_w.view(-1), out_splits, in_splits, group=self._pg,
-                                                     async_op=True)
+                recv_v, recv_w, wait = exchange_ids(self._pg, send_v.view(-1), send_w.view(-1) if send_w is not None else None,
+                                                    out_splits, in_splits)
             else:
-                recv_v, recv_w, wk, wk2 = send_v.reshape(-1), (send_w.reshape(-1) if send_w is not None else None), None, None
+                recv_v, recv_w, wait = send_v.reshape(-1), (send_w.reshape(-1) if send_w is not None else None), None
 
             def finish() -> SparseFeaturesDist:
-                if wk is not None:
-                    wk.wait()
-                if wk2 is not None:
-                    wk2.wait()
+                if wait is not None:
+                    wait()
                 ck = ("off", B, L)
                 offsets = self._kjt_cache.get(ck)
                 if offsets is None:
@@ -1380,32 +1147,21 @@ class ShardedEmbeddingBagCollection(nn.Module):
         n_per_rank = self._send_feats_per_rank
         len_in = [n * B for n in n_per_rank]
         len_out = [self._F_local * B] * W
-        val_in, k = [], 0
-        for n in n_per_rank:
-            val_in.append(sum(lpk[k:k + n]))
-            k += n
+        val_in = ids_per_destination(lpk, n_per_rank)
         if self._exchange:
             recv_l = torch.empty(sum(len_out), dtype=lengths.dtype, device=lengths.device)
             with label("## all2all_data:lengths ##"):  # dist_data.py:366
                 dist.all_to_all_single(recv_l, lengths, len_out, len_in, group=self._pg)
             with label("## all2all_data:split length for a2a ##"):  # dist_data.py:388
                 val_out = recv_l.view(W, -1).sum(dim=1).cpu().tolist()  # host sync (dist_data.py:396-398)
-            recv_v = torch.empty(sum(val_out), dtype=sent.values().dtype, device=lengths.device)
-            with label("## all2all_data:indices ##"):
-                wk = dist.all_to_all_single(recv_v, sent.values(), val_out, val_in, group=self._pg, async_op=True)
-            recv_w, wk2 = None, None
-            if weights is not None:
-                recv_w = torch.empty(sum(val_out), dtype=weights.dtype, device=lengths.device)
-                with label("## all2all_data:weights ##"):
-                    wk2 = dist.all_to_all_single(recv_w, sent.weights(), val_out, val_in, group=self._pg, async_op=True)
+            recv_v, recv_w, wait = exchange_ids(self._pg, sent.values(), sent.weights() if weights is not None else None,
+                                                val_out, val_in)
         else:
-            recv_l, recv_v, recv_w, wk, wk2 = lengths, sent.values(), sent.weights_or_none() if weights is not None else None, None, None
+            recv_l, recv_v, recv_w, wait = lengths, sent.values(), sent.weights_or_none() if weights is not None else None, None
 
         def finish_var() -> SparseFeaturesDist:
-            if wk is not None:
-                wk.wait()
-            if wk2 is not None:
-                wk2.wait()
+            if wait is not None:
+                wait()
             offsets = torch.ops.fbgemm.asynchronous_complete_cumsum(recv_l).long()
             return SparseFeaturesDist(recv_v, offsets, recv_w, B, dp_in)
 
@@ -1440,7 +1196,7 @@ class ShardedEmbeddingBagCollection(nn.Module):
         else:
             rows = sum(dist_input.batch_size_per_rank) if self._variable_batch else self._world_size * B
             emb = torch.zeros((rows, 0), dtype=torch.float32, device=self._device, requires_grad=True)
-        state = _VariableExchangeState(self, dist_input.batch_size_per_rank) if self._variable_batch else _ExchangeState(self, B)
+        state = _ExchangeState(self, dist_input.batch_size_per_rank if self._variable_batch else B)
         recv = _ExchangeReq.apply(emb, state)
         return _OutputAwaitable(
             lambda: KeyedTensor(keys, lpe, self._dp_fill(_ExchangeWait.apply(recv, state), dist_input)))
