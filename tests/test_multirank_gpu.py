@@ -11,6 +11,8 @@
 Checks follow the reference's sharded-vs-unsharded pattern
 (torchrec/distributed/test_utils/test_model_parallel_base.py:148-294).
 """
+import contextlib
+import json
 import os
 
 import numpy as np
@@ -21,6 +23,7 @@ import torch.multiprocessing as mp
 
 import _paths  # noqa: F401
 from _results import ResultStore
+from _schedule_recorder import record_schedule
 from test_sharded_gloo import _free_port
 
 pytestmark = pytest.mark.gpu
@@ -384,6 +387,7 @@ E_ROWS = [3000, 9, 31000, 170, 8, 5, 999]
 E_B = 64  # per rank
 E_STEPS = 4
 E_LR = 0.05
+SCHEDULE_MODES = ("flat", "flat-halves", "flat-early")  # tests/golden/explicit_step_schedule.json holds one list for each
 
 
 def _e2e_batches(W):
@@ -473,10 +477,16 @@ def _e2e_worker(rank, W, port, ret, hip_graphs=False):
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     dist.init_process_group("gloo", rank=rank, world_size=W)
+    recorder = contextlib.ExitStack()
     try:
         _stage_a2a_through_host()
         from torchrec_amd.distributed.types import ShardingEnv
 
+        # rank 0 of the flat modes records its host call schedule: graph replays (numbered in capture order), collectives,
+        # lookup stages, optimizer steps (_schedule_recorder.py; behind the host staging above, which calls the real
+        # all-to-all itself)
+        recorded = rank == 0 and hip_graphs in SCHEDULE_MODES
+        schedule = recorder.enter_context(record_schedule()) if recorded else None
         halves = hip_graphs == "flat-halves"  # the exchange in two half-batches (capture_hip_graphs(half_batches=True))
         if hip_graphs == "flat-early":  # every piece of the flat gradient all-reduced as soon as it exists (split mode "early")
             os.environ["TORCHREC_AMD_WGRAD_SPLIT_MODE"] = "early"
@@ -500,7 +510,10 @@ def _e2e_worker(rank, W, port, ret, hip_graphs=False):
         # flat-gradient graph mode runs forward AND backward by hand (DLRMTrain._explicit_step), no autograd engine
         assert (getattr(model.module, "explicit_steps", 0) == E_STEPS) == (hip_graphs == "flat")
         assert getattr(model.module, "half_batch_steps", 0) == (E_STEPS if halves else 0)
+        if recorded:
+            ret["schedule"] = list(schedule)
     finally:
+        recorder.close()
         dist.destroy_process_group()
 
 
@@ -522,6 +535,11 @@ def test_dlrm_train_world2_on_one_gpu_matches_world1(hip_graphs):
     keys, model, opt = _e2e_model(ShardingEnv.from_local(1, 0), dev, dp_max_rows=0)
     _e2e_init_tables(model)
     losses1, tabs1, dense1 = _e2e_run(model, opt, keys, _e2e_batches(W), 0, 1, dev)
+    if hip_graphs in SCHEDULE_MODES:
+        # the explicit step's launches, collectives and their order are pinned: whoever moves one changes the golden file
+        # (tests/golden/make_schedule_golden.py) on purpose
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "explicit_step_schedule.json")) as fh:
+            assert ret["schedule"] == json.load(fh)[hip_graphs]
     l0, t0, d0 = ret[0]
     l1, t1, d1 = ret[1]
     # mean loss over the global batch = mean of the two ranks' local means

@@ -47,9 +47,9 @@ class _Replay(torch.autograd.Function):
             if s is not None and g is not None and g.data_ptr() != s.data_ptr():
                 s.copy_(g)
         seg.bwd_graph.replay()
-        if getattr(seg, "bwd_graph2", None) is not None:
+        if seg.bwd_graph2 is not None:
             seg.bwd_graph2.replay()  # deferred weight gradients (capture_backward(defer_wgrad=True))
-        if getattr(seg, "bwd_graph3", None) is not None:
+        if seg.bwd_graph3 is not None:
             seg.bwd_graph3.replay()  # ... the late part of them (late_params)
         if seg.param_grad_sinks is not None:
             # parameter gradients were written (scaled) into the caller's flat buffer inside the graph;
@@ -85,6 +85,9 @@ class GraphedSegment(nn.Module):
         self._pool = pool if pool is not None else torch.cuda.graph_pool_handle()
         self.fwd_graph = torch.cuda.CUDAGraph()
         self.bwd_graph: Optional[torch.cuda.CUDAGraph] = None
+        # capture_backward(defer_wgrad=True): the weight gradients' graph, and the one of their late part (late_params)
+        self.bwd_graph2: Optional[torch.cuda.CUDAGraph] = None
+        self.bwd_graph3: Optional[torch.cuda.CUDAGraph] = None
         self.static_grad_outputs: List[Optional[torch.Tensor]] = []
         self.static_grad_inputs: List[Optional[torch.Tensor]] = []
         self.param_grad_sinks: Optional[List[torch.Tensor]] = None
@@ -206,8 +209,7 @@ class GraphedSegment(nn.Module):
             self.param_grad_sinks = list(param_grad_sinks)
 
         self.bwd_graph = torch.cuda.CUDAGraph()
-        self.bwd_graph2: Optional[torch.cuda.CUDAGraph] = None
-        self.bwd_graph3: Optional[torch.cuda.CUDAGraph] = None
+        self.bwd_graph2 = self.bwd_graph3 = None
         self._sink_tables = []  # (device segment table, its rows, the source tensors kept alive)
         # ordinary allocations: NOT in the graphs' pool (see write_sinks); one per write_sinks call
         sink_tables = ([torch.zeros((len(param_grad_sinks), 4), dtype=torch.int64, device=param_grad_sinks[0].device)

@@ -145,7 +145,7 @@ class TrainPipelineSparseDist:
             if hasattr(root, "capture_hip_graphs"):
                 B = int(self._batch_i.dense_features.shape[0])
                 have = getattr(root, "_graphs", None)
-                if have is not None and have[0] == B:
+                if have is not None and have.batch == B:
                     # the owner captured already (the documented N > 1 flow: DistributedModelParallel(init_data_parallel=
                     # False) -> capture_hip_graphs(B, flat_grads=True, process_group=pg) -> init_data_parallel()).  Capturing
                     # again would replace the flat gradient state by a world-1 one — the dense all-reduce would silently

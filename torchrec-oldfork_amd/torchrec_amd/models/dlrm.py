@@ -7,6 +7,9 @@ import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
+import torch.distributed as dist  # called as dist.all_reduce(...): distributed/_rehearsal.py replaces the module's functions
+from fbgemm_gpu import _lib
+from fbgemm_gpu._lib import check, ptr, stream_ptr
 from torch import nn
 
 from ..modules.mlp import MLP, LinearOut
@@ -90,10 +93,6 @@ _HALF_BATCHES = os.environ.get("TORCHREC_AMD_HALF_BATCHES", "auto")
 _HALF_BATCH_MIN = int(os.environ.get("TORCHREC_AMD_HALF_BATCH_MIN", "32768"))
 
 
-def _pad64(n: int) -> int:
-    return (n + 63) // 64 * 64
-
-
 class DenseArch(nn.Module):
     def __init__(self, in_features: int, layer_sizes: List[int], device: Optional[torch.device] = None) -> None:
         super().__init__()
@@ -101,6 +100,21 @@ class DenseArch(nn.Module):
 
     def forward(self, features: torch.Tensor) -> torch.Tensor:
         return self.model(features)
+
+
+def _interaction_row(F: int, D: int, pad_rows: bool = False) -> Tuple[int, int]:
+    """(width, stride) of the interaction's result rows: D + F (F + 1) / 2 floats; pad_rows rounds the pairs up to 4 floats."""
+    pairs = (F + 1) * F // 2
+    return D + pairs, (D + (pairs + 3) // 4 * 4) if pad_rows else D + pairs
+
+
+def _readable_grad_out(grad_out: torch.Tensor, B: int, width: int) -> torch.Tensor:
+    """The gradient of the interaction's result as the backward kernels read it: float32 rows of unit stride."""
+    if grad_out.shape != (B, width):
+        raise RuntimeError(f"dot interaction backward: grad_out {tuple(grad_out.shape)} has the wrong shape")
+    if grad_out.dtype != torch.float32 or grad_out.stride(1) != 1 or grad_out.stride(0) < width:
+        return grad_out.float().contiguous()
+    return grad_out  # padded rows (stride >= width) are read in place
 
 
 class _FusedDotInteraction(torch.autograd.Function):
@@ -113,16 +127,12 @@ class _FusedDotInteraction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dense, sparse, pad_rows=False, grad_sinks=None):
-        from fbgemm_gpu import _lib
-        from fbgemm_gpu._lib import check, ptr, stream_ptr
-
         dense, sparse = dense.contiguous(), sparse.contiguous()
         B, F, D = sparse.shape
         if dense.shape != (B, D) or sparse.device != dense.device:
             raise RuntimeError(f"dot interaction: dense {tuple(dense.shape)} does not match sparse {tuple(sparse.shape)} "
                                "(same batch, same embedding dim, same device required)")
-        width = D + (F + 1) * F // 2
-        stride = (D + ((F + 1) * F // 2 + 3) // 4 * 4) if pad_rows else width
+        width, stride = _interaction_row(F, D, pad_rows)
         buf = torch.empty((B, stride), dtype=torch.float32, device=dense.device)
         with torch.cuda.device(dense.device):
             check(_lib.load().tbe_dlrm_interaction_forward_f32(ptr(dense), ptr(sparse), B, F, D, ptr(buf), stride,
@@ -136,16 +146,9 @@ class _FusedDotInteraction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from fbgemm_gpu import _lib
-        from fbgemm_gpu._lib import check, ptr, stream_ptr
-
         dense, sparse = ctx.saved_tensors
         B, F, D = sparse.shape
-        width = D + (F + 1) * F // 2
-        if grad_out.shape != (B, width):
-            raise RuntimeError(f"dot interaction backward: grad_out {tuple(grad_out.shape)} has the wrong shape")
-        if grad_out.dtype != torch.float32 or grad_out.stride(1) != 1 or grad_out.stride(0) < width:
-            grad_out = grad_out.float().contiguous()  # padded rows (stride >= width) are read in place
+        grad_out = _readable_grad_out(grad_out, B, _interaction_row(F, D)[0])
         if ctx.grad_sinks is not None:
             gd, gs = ctx.grad_sinks
             if (gd.shape != dense.shape or gs.shape != sparse.shape or not gd.is_contiguous() or not gs.is_contiguous()
@@ -168,16 +171,12 @@ class _FusedGatherInteraction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dense, placeholder, lookup, pad_rows=False):
-        from fbgemm_gpu import _lib
-        from fbgemm_gpu._lib import check, ptr, stream_ptr
-
         dense = dense.contiguous()
         B, F, D = lookup.B, lookup.F, lookup.D
         if dense.shape != (B, D) or dense.dtype != torch.float32 or dense.device != lookup.module.current_device:
             raise RuntimeError(f"dot interaction: dense {tuple(dense.shape)} {dense.dtype} on {dense.device} does not match "
                                f"the lookup (batch {B}, dim {D}, float32 on {lookup.module.current_device})")
-        width = D + (F + 1) * F // 2
-        stride = (D + ((F + 1) * F // 2 + 3) // 4 * 4) if pad_rows else width
+        width, stride = _interaction_row(F, D, pad_rows)
         buf = torch.empty((B, stride), dtype=torch.float32, device=dense.device)
         with torch.cuda.device(dense.device):
             check(_lib.load().tbe_dlrm_interaction_gather_forward_f32(
@@ -190,17 +189,10 @@ class _FusedGatherInteraction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from fbgemm_gpu import _lib
-        from fbgemm_gpu._lib import check, ptr, stream_ptr
-
         (dense,) = ctx.saved_tensors
         lookup, ctx.lookup = ctx.lookup, None
         B, F, D = lookup.B, lookup.F, lookup.D
-        width = D + (F + 1) * F // 2
-        if grad_out.shape != (B, width):
-            raise RuntimeError(f"dot interaction backward: grad_out {tuple(grad_out.shape)} has the wrong shape")
-        if grad_out.dtype != torch.float32 or grad_out.stride(1) != 1 or grad_out.stride(0) < width:
-            grad_out = grad_out.float().contiguous()  # padded rows (stride >= width) are read in place
+        grad_out = _readable_grad_out(grad_out, B, _interaction_row(F, D)[0])
         gd = torch.empty_like(dense)
         gs = torch.empty((B, F * D), dtype=torch.float32, device=dense.device)
         with torch.cuda.device(dense.device):
@@ -364,6 +356,151 @@ class _Head(nn.Module):
         return bce_with_logits_mean(self.loss_fn, logits, labels), logits.detach()
 
 
+def _flat_layout(head, dense, rest) -> Tuple[List[int], int]:
+    """[head | pad | bottom MLP | pad | rest | pad] in a flat float32 buffer: the segments' offsets and the total, in elements.
+    The flat parameter AND gradient buffers are cut from this one result (optim/flat.py walks them with one index).  Segments
+    start on 256-B boundaries (the head ends with a 1-element bias: unpadded, what follows would sit at 4 mod 16 bytes)."""
+    offsets, total = [], 0
+    for seg in (head, dense, rest):
+        offsets.append(total)
+        total = (total + sum(q.numel() for q in seg) + 63) // 64 * 64
+    return offsets, total
+
+
+def _views(buffer: torch.Tensor, params, offset: int) -> List[torch.Tensor]:
+    """Consecutive slices of the flat `buffer` from `offset` on, one per parameter and shaped like it."""
+    out = []
+    for q in params:
+        out.append(buffer[offset:offset + q.numel()].view_as(q))
+        offset += q.numel()
+    return out
+
+
+def _fold_grads(pairs, scale: float) -> None:
+    """(parameter, its view of the flat gradient buffer) pairs: brings what autograd left in `.grad` into the view, scaled."""
+    for q, v in pairs:
+        if q.grad is None:
+            v.zero_()
+        elif q.grad.data_ptr() != v.data_ptr():
+            torch.mul(q.grad, scale, out=v)
+        elif scale != 1.0:
+            v.mul_(scale)  # autograd accumulated in place (zero_grad(set_to_none=False))
+
+
+class _FlatDenseGrads:
+    """The flat dense-gradient buffer of capture_hip_graphs(flat_grads=True) and the protocol that all-reduces it piece by
+    piece while a step runs.  Set once per capture: buffers, parameters and their views, slice bounds (`n_late`: 0 until the
+    backward graphs exist), process group.  Per step: the collectives in flight and the flags wait_and_attach() clears."""
+
+    __slots__ = ("flat", "flat_param", "params", "views", "extras", "n_head", "n_dense", "n_late", "pg", "world", "scale",
+                 "reduce", "split_mode", "works", "head_replayed", "dense_replayed", "extras_folded", "rest_started",
+                 "pieces_done")
+
+    def __init__(self, segments, offsets, total: int, flat_param, dev, process_group, split_mode: str) -> None:
+        head, dense, extras = segments  # (with their _flat_layout, and the parameter buffer cut from the same layout)
+        world = dist.get_world_size(process_group) if process_group is not None else 1
+        # TORCHREC_AMD_FORCE_DENSE_REDUCE=1 (rehearsal of the N > 1 path on one rank): issue the dense all-reduces — and
+        # create their communicator — although a one-rank group needs none
+        reduce = world > 1 or (process_group is not None and os.environ.get("TORCHREC_AMD_FORCE_DENSE_REDUCE") == "1")
+        pg = process_group
+        if reduce and dist.get_backend(process_group) == "nccl" and os.environ.get("TORCHREC_AMD_DENSE_PG", "1") == "1":
+            # the dense all-reduces get a communicator (and stream) of their own: on the collection's they would queue
+            # behind a pooled all-to-all that is waiting for its links (the prefetched one, above all)
+            from ..distributed.comm import new_rccl_group
+
+            pg = new_rccl_group(process_group)
+        self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.flat_param = flat_param  # None: the parameters are not all float32 on one device and stayed where they were
+        self.params = list(head) + list(dense) + list(extras)
+        self.views = [v for seg, off in zip(segments, offsets) for v in _views(self.flat, seg, off)]
+        # every trainable dense parameter outside the graphed segments (the replicated tiny tables of a sharded
+        # collection): its gradient arrives through autograd and joins the flat buffer after backward
+        self.extras = list(zip(extras, self.views[len(head) + len(dense):]))
+        self.n_head, self.n_dense, self.n_late = offsets[1], offsets[2] - offsets[1], 0
+        self.pg, self.world, self.scale, self.reduce, self.split_mode = pg, world, 1.0 / world, reduce, split_mode
+        self.works = []
+        # both graphed segments ran their backward replays this step: finish_dense_grads() tells a replayed step from an
+        # eager one (another batch size, eval) by these
+        self.head_replayed = self.dense_replayed = False
+        self.extras_folded = self.rest_started = self.pieces_done = False
+
+    def _all_reduce(self, lo: int, hi: int) -> None:
+        if self.reduce:
+            self.works.append(dist.all_reduce(self.flat[lo:hi], group=self.pg, async_op=True))
+
+    def head_done(self, early: bool = False) -> None:
+        """The head's backward runs first: its slice overlaps the rest of backward."""
+        self.head_replayed = True
+        # with a late part (its gradients do not exist yet) what is left of the head's slice is two small layers: they ride
+        # with the rest of the buffer (start_rest) instead of paying for a collective of their own
+        if not self.n_late:
+            self._all_reduce(0, self.n_head)
+        elif early:  # "early" split mode: the late part is on its way (reduce_late), the slice behind it follows at once
+            self._all_reduce(self.n_late, self.n_head)
+            self.pieces_done = True
+
+    def dense_done(self) -> None:
+        self.dense_replayed = True
+
+    def reduce_late(self) -> None:
+        if self.n_late:
+            self._all_reduce(0, self.n_late)
+
+    def fold_extras(self) -> None:
+        if not self.extras_folded:
+            _fold_grads(self.extras, self.scale)
+            self.extras_folded = True
+
+    def early_extras(self) -> None:
+        """"early" split mode, behind the embedding collection's start_backward: the replicated tables' slice."""
+        self.fold_extras()
+        self._all_reduce(self.n_head + self.n_dense, self.flat.numel())
+
+    def start_rest(self) -> None:
+        """Graph-replayed step: folds the autograd / explicit gradients of the non-graphed dense parameters (the replicated
+        tiny tables) into the flat buffer and starts the all-reduce of everything behind the head's slice (bottom MLP +
+        those).  The explicit step calls this as soon as the bottom MLP's backward graph is enqueued — before the fused
+        embedding backward and before the next step's prefetched lookup + pooled all-to-all, so that on the collective
+        stream the (small) dense reduction is queued AHEAD of that all-to-all and overlaps the embedding update."""
+        if self.rest_started:
+            return
+        self.fold_extras()
+        if self.pieces_done:  # "early" split mode: head and replicated tables are on their way, the bottom MLP is left
+            self._all_reduce(self.n_head, self.n_head + self.n_dense)
+        else:
+            self._all_reduce(self.n_late or self.n_head, self.flat.numel())  # (see head_done)
+        self.rest_started = True
+        self.pieces_done = False
+
+    def fold_all_and_reduce(self) -> None:
+        """This step ran eagerly (another batch size, ...): every gradient came through autograd; all are folded and reduced."""
+        for w in self.works:
+            w.wait()
+        self.works.clear()
+        _fold_grads(zip(self.params, self.views), self.scale)
+        self._all_reduce(0, self.flat.numel())
+
+    def wait_and_attach(self) -> None:
+        self.rest_started = self.extras_folded = False
+        for w in self.works:
+            w.wait()
+        self.works.clear()
+        for q, v in zip(self.params, self.views):
+            q.grad = v
+
+
+class _Captured:
+    """What one capture_hip_graphs() call produced; DLRMTrain._graphs.  `dense`: the bottom-MLP segment; `heads`: the head
+    segment, or one per half batch (heads[-1] holds the parameter-gradient sinks of the flat buffer either way); `half`:
+    the whole-batch buffers those two share by halves, or None.  Not sub-modules: state_dict keys unchanged."""
+
+    __slots__ = ("batch", "dense", "heads", "half", "graph_exchange", "loss_grad_ready")
+
+    def __init__(self, batch: int, dense, heads, half, graph_exchange: bool) -> None:
+        self.batch, self.dense, self.heads, self.half, self.graph_exchange = batch, dense, heads, half, graph_exchange
+        self.loss_grad_ready = False  # the explicit step fills d(loss) into the heads' grad-output buffers (zeros) once
+
+
 class DLRMTrain(nn.Module):
     """examples/dlrm/modules/dlrm_train.py: BCEWithLogits wrapper used by the train pipeline."""
 
@@ -374,7 +511,14 @@ class DLRMTrain(nn.Module):
         self.model = DLRM(embedding_bag_collection, dense_in_features, dense_arch_layer_sizes,
                           over_arch_layer_sizes, dense_device)
         self.loss_fn = nn.BCEWithLogitsLoss()
-        self._graphs = None  # (batch size, bottom-MLP segment, head segment)
+        self._graphs: Optional[_Captured] = None  # (`_flat_dense` exists only once a flat capture has assigned it: _flat())
+        # per-step hand-offs of the explicit step (set_between_forward_and_backward, take_backward_done)
+        self._between = self._prefetch = self._prefetched = None
+        self._backward_done = False
+        self.explicit_steps = self.half_batch_steps = self.prefetched_lookups = 0  # for tests / bench.py's line
+
+    def _flat(self) -> Optional[_FlatDenseGrads]:
+        return self.__dict__.get("_flat_dense")
 
     def capture_hip_graphs(self, batch_size: int, flat_grads: bool = False, process_group=None,
                            half_batches: Optional[bool] = None) -> None:
@@ -389,47 +533,61 @@ class DLRMTrain(nn.Module):
         This replaces DistributedDataParallel altogether (its forward wrapper alone cost 0.43 ms of host
         time per step, plus 16 per-parameter bucket copies — the per-rank step of an N > 1 run is
         host-bound); DistributedModelParallel.init_data_parallel() broadcasts rank 0's values instead."""
-        from ..distributed.hip_graph import GraphedSegment
-
+        # the graphs share one memory pool: the order of the captures, and of what is allocated before, inside and between
+        # them, decides addresses (distributed/hip_graph.py write_sinks records what a misplaced allocation did)
         m = self.model
-        p = next(m.dense_arch.parameters())
-        dev, B = p.device, batch_size
-        F, D = m.sparse_arch.F, m.sparse_arch.D
-        dense_in = m.dense_arch.model._mlp[0]._in_size
+        dev, B = next(m.dense_arch.parameters()).device, batch_size
         head = _Head(m.inter_arch, m.over_arch, self.loss_fn)
-        flat_param = None
-        if flat_grads:
-            # the parameters move into ONE flat buffer too (same order as the flat gradient: head, bottom MLP, the
-            # rest), before anything captures their addresses: the dense optimizer becomes one kernel (optim/flat.py)
-            seg_head = [q for q in head.parameters() if q.requires_grad]
-            seg_dense = [q for q in m.dense_arch.parameters() if q.requires_grad]
-            seen = {id(q) for q in seg_head + seg_dense}
-            seg_rest = [q for q in self.parameters() if q.requires_grad and id(q) not in seen]
-            if all(q.dtype == torch.float32 and q.device == dev for q in seg_head + seg_dense + seg_rest):
-                # every segment starts on a 256-B boundary (the head ends with a 1-element bias: without the padding the
-                # bottom MLP's weights and the replicated tables would sit at addresses that are 4 mod 16)
-                starts, total = [], 0
-                for seg in (seg_head, seg_dense, seg_rest):
-                    starts.append(total)
-                    total = _pad64(total + sum(q.numel() for q in seg))
-                flat_param = torch.zeros(total, dtype=torch.float32, device=dev)
-                with torch.no_grad():
-                    for seg, off in zip((seg_head, seg_dense, seg_rest), starts):
-                        for q in seg:
-                            view = flat_param[off:off + q.numel()].view_as(q)
-                            view.copy_(q)
-                            q.data = view
-                            off += q.numel()
         ebc = m.sparse_arch.embedding_bag_collection
         ebc = getattr(ebc, "sharded", ebc)
+        segments, offsets, total, flat_param = self._flatten_parameters(head, dev) if flat_grads else (None,) * 4
         if half_batches is None:
             half_batches = _HALF_BATCHES == "1" or (_HALF_BATCHES == "auto" and B >= _HALF_BATCH_MIN)
         halves = bool(half_batches and flat_grads and B % 2 == 0 and getattr(ebc, "_exchange", False)
                       and hasattr(ebc, "set_half_batch_exchange"))
-        g_dense = GraphedSegment(m.dense_arch, [torch.randn(B, dense_in, device=dev)])
-        if halves and hasattr(ebc, "set_graph_exchange"):
-            ebc.set_graph_exchange(None)
+        cap, hooks = self._capture_forward(head, ebc, B, dev, flat_grads, halves)
+        st = None
+        if flat_grads:  # the flat gradient buffer, and who is told when a segment's backward has written its slice
+            st = _FlatDenseGrads(segments, offsets, total, flat_param, dev, process_group,
+                                 _WGRAD_SPLIT_MODE if cap.half is None else "late")
+            if hasattr(ebc, "set_replicated_grad_sink"):
+                dp = getattr(ebc, "_dp_module", None)
+                ebc.set_replicated_grad_sink(next((v for q, v in st.extras if dp is not None and q is dp.weights), None))
+            if cap.half is None:  # (the half-batch step tells it itself, once for both head segments)
+                cap.heads[-1].after_backward = st.head_done
+            cap.dense.after_backward = st.dense_done
+            self._flat_dense = st
+        self._capture_backward(cap, st, ebc, hooks, dev)
+        self._graphs = cap
+
+    def _flatten_parameters(self, head: nn.Module, dev):
+        """The trainable dense parameters as (head, bottom MLP, the rest), their _flat_layout, and ONE flat buffer of that layout
+        they move into before anything captures their addresses (or None): optim/flat.py updates them with one kernel."""
+        seg_head = [q for q in head.parameters() if q.requires_grad]
+        seg_dense = [q for q in self.model.dense_arch.parameters() if q.requires_grad]
+        seen = {id(q) for q in seg_head + seg_dense}
+        segments = (seg_head, seg_dense, [q for q in self.parameters() if q.requires_grad and id(q) not in seen])
+        offsets, total = _flat_layout(*segments)
+        flat_param = None
+        if all(q.dtype == torch.float32 and q.device == dev for seg in segments for q in seg):
+            flat_param = torch.zeros(total, dtype=torch.float32, device=dev)
+            with torch.no_grad():
+                for seg, off in zip(segments, offsets):
+                    for q, view in zip(seg, _views(flat_param, seg, off)):
+                        view.copy_(q)
+                        q.data = view
+        return segments, offsets, total, flat_param
+
+    def _capture_forward(self, head: nn.Module, ebc, B: int, dev, flat_grads: bool, halves: bool):
+        """The forward graphs: bottom MLP, then head (whole, or per half batch).  Returns (_Captured, exchange hooks or None)."""
+        from ..distributed.hip_graph import GraphedSegment
+
+        m = self.model
+        F, D = m.sparse_arch.F, m.sparse_arch.D
+        g_dense = GraphedSegment(m.dense_arch, [torch.randn(B, m.dense_arch.model._mlp[0]._in_size, device=dev)])
         if halves:
+            if hasattr(ebc, "set_graph_exchange"):
+                ebc.set_graph_exchange(None)
             # whole-batch buffers the two head segments share by halves: pooled embeddings (the collection's output
             # buffer), labels, and the gradients w.r.t. the bottom-MLP output / the pooled embeddings
             Bh = B // 2
@@ -448,143 +606,72 @@ class DLRMTrain(nn.Module):
                         pool=g_dense._pool))
                 finally:
                     m.inter_arch.grad_sinks = None
-            g_head = heads[1]
-        else:
-            # static-exchange mode (flat gradients + explicit step + a collection that exchanges): the unpack of the pooled
-            # all-to-all's receive buffer is the FIRST kernel of the head's forward graph and the pack of the gradient
-            # into the send buffer the LAST of its backward graph, instead of two eager launches per step
-            hooks = None
-            if (flat_grads and _GRAPH_EXCHANGE and getattr(ebc, "_exchange", False)
-                    and hasattr(ebc, "set_graph_exchange")):
-                pooled = torch.zeros(B, F, D, device=dev)
-                ebc.set_output_buffer(pooled)
-                hooks = ebc.set_graph_exchange(B)
-            elif hasattr(ebc, "set_graph_exchange"):
-                ebc.set_graph_exchange(None)
-            g_head = GraphedSegment(
-                head, [g_dense.static_outputs[0].detach().requires_grad_(True),
-                       torch.randn(B, F, D, device=dev).requires_grad_(True),
-                       torch.randint(0, 2, (B,), device=dev)],  # int64, as the data loader delivers them
-                input_buffers=[g_dense.static_outputs[0], pooled if hooks is not None else None, None], pool=g_dense._pool,
-                pre_forward=hooks[0] if hooks is not None else None)
-        head_sinks = dense_sinks = None
-        scale = 1.0
-        if flat_grads:
-            import torch.distributed as dist
+            return _Captured(B, g_dense, heads, half, False), None
+        # static-exchange mode (flat gradients + explicit step + a collection that exchanges): the unpack of the pooled
+        # all-to-all's receive buffer is the FIRST kernel of the head's forward graph and the pack of the gradient
+        # into the send buffer the LAST of its backward graph, instead of two eager launches per step
+        hooks = None
+        if (flat_grads and _GRAPH_EXCHANGE and getattr(ebc, "_exchange", False)
+                and hasattr(ebc, "set_graph_exchange")):
+            pooled = torch.zeros(B, F, D, device=dev)
+            ebc.set_output_buffer(pooled)
+            hooks = ebc.set_graph_exchange(B)
+        elif hasattr(ebc, "set_graph_exchange"):
+            ebc.set_graph_exchange(None)
+        g_head = GraphedSegment(
+            head, [g_dense.static_outputs[0].detach().requires_grad_(True),
+                   torch.randn(B, F, D, device=dev).requires_grad_(True),
+                   torch.randint(0, 2, (B,), device=dev)],  # int64, as the data loader delivers them
+            input_buffers=[g_dense.static_outputs[0], pooled if hooks is not None else None, None], pool=g_dense._pool,
+            pre_forward=hooks[0] if hooks is not None else None)
+        return _Captured(B, g_dense, [g_head], None, hooks is not None), hooks
 
-            world = dist.get_world_size(process_group) if process_group is not None else 1
-            scale = 1.0 / world
-            dense_pg = process_group
-            # TORCHREC_AMD_FORCE_DENSE_REDUCE=1 (rehearsal of the N > 1 path on one rank): issue the dense all-reduces — and
-            # create their communicator — although a one-rank group needs none
-            reduce = world > 1 or (process_group is not None and os.environ.get("TORCHREC_AMD_FORCE_DENSE_REDUCE") == "1")
-            if reduce and dist.get_backend(process_group) == "nccl" and os.environ.get("TORCHREC_AMD_DENSE_PG", "1") == "1":
-                # the dense all-reduces get a communicator (and stream) of their own: on the collection's they would queue
-                # behind a pooled all-to-all that is waiting for its links (the prefetched one, above all)
-                from ..distributed.comm import new_rccl_group
-
-                dense_pg = new_rccl_group(process_group)
-            graphed = {id(q) for q in list(g_head._params) + list(g_dense._params)}
-            # every other trainable dense parameter of the model (the replicated tiny tables of a sharded
-            # collection): its gradient arrives through autograd and joins the flat buffer after backward
-            extras = [q for q in self.parameters() if q.requires_grad and id(q) not in graphed]
-            # same layout as the flat parameter buffer: [head | pad | bottom MLP | pad | rest | pad], segments 256-B aligned
-            n_head = _pad64(sum(q.numel() for q in g_head._params))
-            n_dense = _pad64(sum(q.numel() for q in g_dense._params))
-            n_extra = _pad64(sum(q.numel() for q in extras))
-            flat = torch.zeros(n_head + n_dense + n_extra, dtype=torch.float32, device=dev)
-
-            def views(params, off):
-                out = []
-                for q in params:
-                    out.append(flat[off:off + q.numel()].view_as(q))
-                    off += q.numel()
-                return out
-
-            head_sinks, dense_sinks = views(g_head._params, 0), views(g_dense._params, n_head)
-            extra_views = views(extras, n_head + n_dense)
-            state = {"flat": flat, "flat_param": flat_param, "params": list(g_head._params) + list(g_dense._params) + extras,
-                     "views": head_sinks + dense_sinks + extra_views, "extras": list(zip(extras, extra_views)),
-                     "n_head": n_head, "n_dense": n_dense, "works": [], "pg": dense_pg, "world": world, "scale": scale,
-                     "reduce": reduce}
-
-            def reduce_head():  # the head's backward runs first: its slice overlaps the rest of backward
-                state["fired"] += 1
-                # with a late part (its gradients do not exist yet) what is left of the head's slice is two small layers:
-                # they ride with the rest of the buffer (_start_rest_reduce) instead of paying for a collective of their own
-                if state["reduce"] and not state.get("n_late", 0):
-                    state["works"].append(dist.all_reduce(flat[:n_head], group=state["pg"], async_op=True))
-
-            def reduce_late():
-                if state["reduce"] and state.get("n_late", 0):
-                    state["works"].append(dist.all_reduce(flat[:state["n_late"]], group=state["pg"], async_op=True))
-
-            state["reduce_late"] = reduce_late
-
-            def dense_done():
-                state["fired"] += 1
-
-            state["fired"] = 0
-            if hasattr(ebc, "set_replicated_grad_sink"):
-                dp = getattr(ebc, "_dp_module", None)
-                sink = next((v for q, v in zip(extras, extra_views) if dp is not None and q is dp.weights), None)
-                ebc.set_replicated_grad_sink(sink)
-            g_head.after_backward = reduce_head
-            g_dense.after_backward = dense_done
-            object.__setattr__(self, "_flat_dense", state)
+    def _capture_backward(self, cap: _Captured, st: Optional[_FlatDenseGrads], ebc, hooks, dev) -> None:
+        """The backward graphs: the head's (of both halves), then the bottom MLP's."""
+        g_dense, g_head, half, flat = cap.dense, cap.heads[-1], cap.half, st is not None
+        n = len(g_head._params)
+        head_sinks = st.views[:n] if flat else None
+        dense_sinks = st.views[n:n + len(g_dense._params)] if flat else None
+        scale = st.scale if flat else 1.0
         late = 0
-        if flat_grads and _DEFER_WGRAD and getattr(ebc, "_exchange", False):
+        if flat and _DEFER_WGRAD and getattr(ebc, "_exchange", False):
             # (weight, bias) of the over arch's first layers: the leading parameters of the head segment
             n_lin = sum(1 for q in g_head._params if q.dim() == 2)
-            late = 2 * min(_late_layers(B, halves), max(n_lin - 1, 0))
+            late = 2 * min(_late_layers(cap.batch, half is not None), max(n_lin - 1, 0))
             if late and not all(g_head._params[j].dim() == (2 if j % 2 == 0 else 1) for j in range(late)):
                 late = 0  # not a plain (weight, bias) sequence: keep everything in the second graph
         # the embedding collection writes its pooled output straight into the head segment's static input
         if hasattr(ebc, "set_half_batch_exchange"):
-            ebc.set_half_batch_exchange(halves)
-        if halves:
+            ebc.set_half_batch_exchange(half is not None)
+        if half is not None:
             ebc.set_output_buffer(half["pooled"])
             # half 0's parameter gradients go to a buffer of their own and are added to half 1's (which sit in the flat
             # buffer) by one launch after both weight-gradient graphs
-            tmp = torch.zeros(n_head, dtype=torch.float32, device=dev)
-            tmp_sinks, off = [], 0
-            for q in g_head._params:
-                tmp_sinks.append(tmp[off:off + q.numel()].view_as(q))
-                off += q.numel()
-            half["tmp"], half["n_head_used"] = tmp, off
-            for h, gh in enumerate(heads):
+            half["tmp"] = torch.zeros(st.n_head, dtype=torch.float32, device=dev)
+            tmp_sinks = _views(half["tmp"], g_head._params, 0)
+            half["n_used"] = sum(q.numel() for q in g_head._params)
+            for h, gh in enumerate(cap.heads):
                 gh.capture_backward(param_grad_sinks=tmp_sinks if h == 0 else head_sinks, sink_scale=scale,
                                     defer_wgrad=_DEFER_WGRAD, late_params=late)
-                rows = slice(h * Bh, (h + 1) * Bh)
+                rows = slice(h * half["Bh"], (h + 1) * half["Bh"])
                 if (gh.static_grad_inputs[0].data_ptr() != half["gd"][rows].data_ptr()
                         or gh.static_grad_inputs[1].data_ptr() != half["gs"][rows].data_ptr()):
                     raise RuntimeError("capture_hip_graphs(half_batches=True): the head segment's input gradients did not land "
                                        "in the shared whole-batch buffers (is the fused dot interaction in use?)")
-            heads[1].after_backward = heads[0].after_backward = None
-            half["heads"], half["reduce_head"] = heads, reduce_head
-            state["n_late"] = sum(q.numel() for q in g_head._params[:late]) if heads[1].bwd_graph3 is not None else 0
-            g_dense.capture_backward([half["gd"]], param_grad_sinks=dense_sinks, sink_scale=scale, defer_wgrad=_DEFER_WGRAD)
-            object.__setattr__(self, "_half", half)
-            object.__setattr__(self, "_graph_exchange", False)
+            grad_out = half["gd"]
         else:
             if hasattr(ebc, "set_output_buffer") and hooks is None:
                 ebc.set_output_buffer(g_head.static_input(1).detach())
             # flat mode: the head's weight gradients go into a second graph that the explicit step replays after it has
             # started the embedding-gradient all-to-all (modules/mlp.py _DeferredWgrad)
-            g_head.capture_backward(param_grad_sinks=head_sinks, sink_scale=scale, defer_wgrad=flat_grads and _DEFER_WGRAD,
+            g_head.capture_backward(param_grad_sinks=head_sinks, sink_scale=scale, defer_wgrad=flat and _DEFER_WGRAD,
                                     late_params=late,
                                     post_backward=(lambda gin: hooks[1](gin[1])) if hooks is not None else None)
-            object.__setattr__(self, "_graph_exchange", hooks is not None)
-            if flat_grads:
-                state["n_late"] = sum(q.numel() for q in g_head._params[:late]) if g_head.bwd_graph3 is not None else 0
-                state["split_mode"] = _WGRAD_SPLIT_MODE
-            # the head's gradient w.r.t. the bottom-MLP output doubles as the bottom segment's grad_output buffer
-            g_dense.capture_backward([g_head.static_grad_inputs[0]], param_grad_sinks=dense_sinks, sink_scale=scale,
-                                     defer_wgrad=flat_grads and _DEFER_WGRAD)
-            object.__setattr__(self, "_half", None)
-        object.__setattr__(self, "_graphs", (B, g_dense, g_head))  # not sub-modules: state_dict keys unchanged
-        # the explicit step fills d(loss) = 1 into the NEW head segment's grad-output buffer (zeros after capture)
-        object.__setattr__(self, "_loss_grad_ready", False)
+            grad_out = g_head.static_grad_inputs[0]
+        # the head's gradient w.r.t. the bottom-MLP output doubles as the bottom segment's grad_output buffer
+        g_dense.capture_backward([grad_out], param_grad_sinks=dense_sinks, sink_scale=scale, defer_wgrad=flat and _DEFER_WGRAD)
+        if flat and g_head.bwd_graph3 is not None:
+            st.n_late = sum(q.numel() for q in g_head._params[:late])
 
     def dense_optimizer(self, params, lr: float, momentum: float = 0.0, weight_decay: float = 0.0) -> torch.optim.Optimizer:
         """SGD for the dense parameters (what examples/dlrm/dlrm_main.py:536-540 builds with torch.optim.SGD): one
@@ -592,88 +679,34 @@ class DLRMTrain(nn.Module):
         (optim/flat.py), torch.optim.SGD otherwise — same hyper-parameters, same arithmetic.  Call it AFTER
         capture_hip_graphs (a later capture moves the parameters into NEW flat buffers)."""
         params = list(params)
-        st = getattr(self, "_flat_dense", None)
-        if (st is not None and st.get("flat_param") is not None and {id(q) for q in st["params"]} <= {id(q) for q in params}
+        st = self._flat()
+        if (st is not None and st.flat_param is not None and {id(q) for q in st.params} <= {id(q) for q in params}
                 and os.environ.get("TORCHREC_AMD_FLAT_SGD", "1") != "0"):
             from ..optim.flat import FlatSGD
 
-            return FlatSGD(params, lr, flat_param=st["flat_param"], flat_grad=st["flat"], covered=st["params"],
-                           grad_views=st["views"], momentum=momentum, weight_decay=weight_decay)
+            return FlatSGD(params, lr, flat_param=st.flat_param, flat_grad=st.flat, covered=st.params,
+                           grad_views=st.views, momentum=momentum, weight_decay=weight_decay)
         return torch.optim.SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
 
     def flat_grad_parameters(self) -> List[nn.Parameter]:
         """Parameters whose gradients travel through the flat buffer (kept out of DDP)."""
-        st = getattr(self, "_flat_dense", None)
-        return list(st["params"]) if st is not None else []
-
-    def _start_rest_reduce(self, st) -> None:
-        """Graph-replayed step: folds the autograd / explicit gradients of the non-graphed dense parameters (the replicated
-        tiny tables) into the flat buffer and starts the all-reduce of everything behind the head's slice (bottom MLP +
-        those).  The explicit step calls this as soon as the bottom MLP's backward graph is enqueued — before the fused
-        embedding backward and before the next step's prefetched lookup + pooled all-to-all, so that on the collective
-        stream the (small) dense reduction is queued AHEAD of that all-to-all and overlaps the embedding update."""
-        if st.get("rest_started"):
-            return
-        import torch.distributed as dist
-
-        self._fold_extras(st)
-        if st["reduce"]:
-            if st.get("pieces_done"):  # "early" split mode: head and replicated tables are on their way, the bottom MLP is left
-                lo, hi = st["n_head"], st["n_head"] + st["n_dense"]
-            else:
-                lo, hi = (st["n_late"] if st.get("n_late", 0) else st["n_head"]), st["flat"].numel()  # (see reduce_head)
-            st["works"].append(dist.all_reduce(st["flat"][lo:hi], group=st["pg"], async_op=True))
-        st["rest_started"] = True
-        st["pieces_done"] = False
-
-    @staticmethod
-    def _fold_extras(st) -> None:
-        if st.get("extras_folded"):
-            return
-        for q, v in st["extras"]:
-            if q.grad is None:
-                v.zero_()
-            elif q.grad.data_ptr() != v.data_ptr():
-                torch.mul(q.grad, st["scale"], out=v)
-            elif st["scale"] != 1.0:
-                v.mul_(st["scale"])  # autograd accumulated in place (zero_grad(set_to_none=False))
-        st["extras_folded"] = True
+        st = self._flat()
+        return list(st.params) if st is not None else []
 
     def finish_dense_grads(self) -> None:
         """After backward: folds the autograd gradients of the non-graphed dense parameters into the flat
         buffer, all-reduces the rest of it (bottom segment + those), waits, and attaches the slices as
         `.grad` (every rank then holds the rank-averaged gradient, as under DistributedDataParallel)."""
-        st = getattr(self, "_flat_dense", None)
+        st = self._flat()
         if st is None:
             return
-        replayed = st["fired"] == 2
-        st["fired"] = 0
-        import torch.distributed as dist
-
-        if not replayed:
-            # this step ran eagerly (another batch size, ...): every gradient came through autograd; fold all of
-            # them into the flat buffer and reduce it as a whole
-            for w in st["works"]:
-                w.wait()
-            st["works"].clear()
-            for q, v in zip(st["params"], st["views"]):
-                if q.grad is None:
-                    v.zero_()
-                elif q.grad.data_ptr() != v.data_ptr():
-                    torch.mul(q.grad, st["scale"], out=v)
-                elif st["scale"] != 1.0:
-                    v.mul_(st["scale"])
-            if st["reduce"]:
-                st["works"].append(dist.all_reduce(st["flat"], group=st["pg"], async_op=True))
+        replayed = st.head_replayed and st.dense_replayed
+        st.head_replayed = st.dense_replayed = False
+        if replayed:
+            st.start_rest()
         else:
-            self._start_rest_reduce(st)
-        st["rest_started"] = False
-        st["extras_folded"] = False
-        for w in st["works"]:
-            w.wait()
-        st["works"].clear()
-        for q, v in zip(st["params"], st["views"]):
-            q.grad = v
+            st.fold_all_and_reduce()
+        st.wait_and_attach()
 
     # ---- explicit train step (HIP-graph + flat-gradient mode): forward AND backward without the autograd engine --------
     def set_between_forward_and_backward(self, fn, prefetch=None) -> None:
@@ -686,30 +719,23 @@ class DLRMTrain(nn.Module):
         — not on the dense optimizer, the dense gradient all-reduce or the host's step-boundary work — so they are
         enqueued here and the GPU has work while the host does that (the step boundary was the largest idle gap of the
         per-rank step: 98 us of 1.99 ms, profiles/r02_rehearsal_b8192_explicit_gaps.txt)."""
-        object.__setattr__(self, "_between", fn)
-        object.__setattr__(self, "_prefetch", prefetch)
+        self._between, self._prefetch = fn, prefetch
 
     @property
     def wants_lookup_prefetch(self) -> bool:
         """True when the captured head segment keeps part of its weight gradients for the window behind the next step's
         prefetched lookup (capture_hip_graphs, TORCHREC_AMD_WGRAD_LATE_LAYERS): the pipeline then prefetches by default."""
-        g = getattr(self, "_graphs", None)
-        st = getattr(self, "_flat_dense", None)
-        return bool(g is not None and getattr(g[2], "bwd_graph3", None) is not None
-                    and (st is None or st.get("split_mode", "late") == "late"))
+        g, st = self._graphs, self._flat()
+        return bool(g is not None and g.heads[-1].bwd_graph3 is not None and (st is None or st.split_mode == "late"))
 
     def take_backward_done(self) -> bool:
         """True (once) when the latest forward() already ran the backward: the caller must not call loss.backward()."""
-        done = getattr(self, "_backward_done", False)
-        object.__setattr__(self, "_backward_done", False)
+        done, self._backward_done = self._backward_done, False
         return done
 
-    def _explicit_step(self, batch, g_dense, g_head):
-        """One train step of the graphed configuration driven by hand: lookup -> all-to-all || bottom-MLP graph ->
-        head graph (forward + backward replays) -> gradient all-to-all || bottom-MLP backward graph -> embedding
-        backward.  Same kernels, same order of the dependent work as the autograd path; what disappears is the engine
-        (its worker thread, ~12 Python Function nodes and their hand-offs: ~0.25 ms of host time per step, which is the
-        bottleneck of the N > 1 per-rank step on a slow host).  Returns None if the collection cannot run it."""
+    def _explicit_lookup(self, batch):
+        """The collection's ExplicitLookupStep for this batch: the one prefetched at the end of the previous step, or a
+        new one on the pipeline's queued input dist (or on its own).  None if the collection cannot run it."""
         ebc = self.model.sparse_arch.embedding_bag_collection
         if not hasattr(ebc, "compute_explicit"):
             return None
@@ -717,178 +743,150 @@ class DLRMTrain(nn.Module):
         if list(inner._feature_names) != list(self.model.sparse_arch.sparse_feature_names):
             return None
         kjt = batch.sparse_features
-        pre = getattr(self, "_prefetched", None)
-        object.__setattr__(self, "_prefetched", None)
+        pre, self._prefetched = self._prefetched, None
         if pre is not None and pre[0] is kjt and getattr(pre[1], "epoch", 0) != getattr(inner, "_weights_epoch", 0):
             # the tables were rewritten (load_state_dict) after the prefetch: look up again, on the same distributed ids
             pre[1].discard()
             pre = (kjt, inner.compute_explicit(pre[1].d))
-            object.__setattr__(self, "prefetched_lookups", getattr(self, "prefetched_lookups", 0) - 1)
+            self.prefetched_lookups -= 1
         if pre is not None and pre[0] is kjt:
-            step = pre[1]  # looked up (and its all-to-all started) at the end of the previous step
-            object.__setattr__(self, "prefetched_lookups", getattr(self, "prefetched_lookups", 0) + 1)
-        else:
-            if pre is not None:
-                raise RuntimeError("DLRMTrain: a lookup was prefetched for another batch than the one this step received; the "
-                                   "owner of the pipeline must feed the batches in the order it announced them")
-            piped = getattr(ebc, "_pipelined", None)  # a train pipeline's forward on this collection (queued input dist)
-            step = (piped.compute_explicit(kjt) if piped is not None
-                    else (ebc.compute_explicit(ebc.input_dist(kjt).wait()) if ebc.explicit_step_supported(kjt.stride()) else None))
+            self.prefetched_lookups += 1
+            return pre[1]  # looked up (and its all-to-all started) at the end of the previous step
+        if pre is not None:
+            raise RuntimeError("DLRMTrain: a lookup was prefetched for another batch than the one this step received; the "
+                               "owner of the pipeline must feed the batches in the order it announced them")
+        piped = getattr(ebc, "_pipelined", None)  # a train pipeline's forward on this collection (queued input dist)
+        if piped is not None:
+            return piped.compute_explicit(kjt)
+        return ebc.compute_explicit(ebc.input_dist(kjt).wait()) if ebc.explicit_step_supported(kjt.stride()) else None
+
+    def _explicit_step(self, batch, g: _Captured):
+        """One train step of the graphed configuration driven by hand: lookup -> all-to-all || bottom-MLP graph ->
+        head graph (forward + backward replays) -> gradient all-to-all || bottom-MLP backward graph -> embedding
+        backward.  Same kernels, same order of the dependent work as the autograd path; what disappears is the engine
+        (its worker thread, ~12 Python Function nodes and their hand-offs: ~0.25 ms of host time per step, which is the
+        bottleneck of the N > 1 per-rank step on a slow host).  Returns None if the collection cannot run it."""
+        step = self._explicit_lookup(batch)
         if step is None:
             return None
-        B = g_dense.static_inputs[0].shape[0]
-        half = getattr(self, "_half", None)
-        if half is not None:
-            if not getattr(step, "halves", False):
-                raise RuntimeError("DLRMTrain: the head segments were captured for half-batch exchanges, the collection did "
-                                   "not start one")
-            return self._explicit_step_halves(batch, step, g_dense, half, B)
+        if g.half is not None:
+            return self._explicit_step_halves(batch, step, g)
+        st, g_dense, g_head = self._flat(), g.dense, g.heads[0]
+        early = g_head.bwd_graph3 is not None and st.split_mode == "early"
         with torch.no_grad():
-            # bottom MLP (graph) while the pooled all-to-all is in flight
-            if batch.dense_features.data_ptr() != g_dense.static_inputs[0].data_ptr():
-                g_dense.static_inputs[0].copy_(batch.dense_features)
-            g_dense.fwd_graph.replay()
+            self._bottom_forward(batch, g_dense)
             pooled = step.finish()  # written into the head segment's static input by the collection
             if pooled.data_ptr() != g_head.static_inputs[1].data_ptr():
                 g_head.static_inputs[1].copy_(pooled.view_as(g_head.static_inputs[1]))
             g_head.static_inputs[2].copy_(batch.labels)
             g_head.fwd_graph.replay()
-            loss, logits = g_head.static_outputs[0], g_head.static_outputs[1]
-            between = getattr(self, "_between", None)
-            if between is not None:
-                between()
-            # backward: d(loss) = 1
+            self._between()
             with label("## backward ##"):  # train_pipeline.py:546
-                ones = getattr(self, "_loss_grad_ready", False)
-                if not ones:
-                    g_head.static_grad_outputs[0].fill_(1.0)
-                    object.__setattr__(self, "_loss_grad_ready", True)
+                if not g.loss_grad_ready:
+                    g_head.static_grad_outputs[0].fill_(1.0)  # d(loss) = 1
+                    g.loss_grad_ready = True
                 g_head.bwd_graph.replay()  # ends with the gradient of the pooled embeddings
-                step.start_backward(g_head.static_grad_inputs[1].view(B, -1))  # pack + gradient all-to-all (+ replicated tables)
-                st = getattr(self, "_flat_dense", None)
-                early = (getattr(g_head, "bwd_graph3", None) is not None and st is not None
-                         and st.get("split_mode") == "early")
+                step.start_backward(g_head.static_grad_inputs[1].view(g.batch, -1))  # pack + gradient all-to-all (+ replicated tables)
                 if early:
-                    # every piece of the flat gradient is all-reduced as soon as it exists, the largest first: the replicated
-                    # tables' (written by start_backward above), the head's largest layers', the head's other layers' — and
-                    # the bottom MLP's small slice last (_start_rest_reduce), behind its backward graphs
-                    import torch.distributed as dist
-
-                    self._fold_extras(st)
-                    if st["reduce"]:
-                        st["works"].append(dist.all_reduce(st["flat"][st["n_head"] + st["n_dense"]:], group=st["pg"], async_op=True))
+                    st.early_extras()  # (_WGRAD_SPLIT_MODE; start_backward above has written the replicated tables' gradients)
                     g_head.bwd_graph3.replay()
-                    st["reduce_late"]()
-                if getattr(g_head, "bwd_graph2", None) is not None:
+                    st.reduce_late()
+                if g_head.bwd_graph2 is not None:
                     g_head.bwd_graph2.replay()  # the head's weight gradients, while the all-to-all is in flight
-                if early:
-                    st["fired"] += 1
-                    if st["reduce"]:
-                        st["works"].append(dist.all_reduce(st["flat"][st["n_late"]:st["n_head"]], group=st["pg"], async_op=True))
-                    st["pieces_done"] = True
-                elif g_head.after_backward is not None:
-                    g_head.after_backward()  # all-reduce of the head's slice of the flat gradient
-                g_dense.bwd_graph.replay()  # its grad_output buffer IS the head's gradient w.r.t. the bottom-MLP output
-                if getattr(g_dense, "bwd_graph2", None) is not None:
-                    g_dense.bwd_graph2.replay()  # its weight / bias gradients, finished into the flat buffer
-                if g_dense.after_backward is not None:
-                    g_dense.after_backward()
-                st = getattr(self, "_flat_dense", None)
-                if st is not None and st["fired"] == 2:
-                    self._start_rest_reduce(st)  # ahead of the embedding update and of the next step's all-to-all
-                step.finish_backward()
-            prefetch = getattr(self, "_prefetch", None)
-            if prefetch is not None:
-                object.__setattr__(self, "_prefetched", prefetch())  # (kjt, ExplicitLookupStep) of the NEXT batch, or None
-            if getattr(g_head, "bwd_graph3", None) is not None and not early:
-                # the late part of the head's weight gradients: behind the NEXT step's lookup + pooled all-to-all when the
-                # owner prefetches (its cover on the links), right here otherwise
-                g_head.bwd_graph3.replay()
-                if st is not None:
-                    st["reduce_late"]()
-        object.__setattr__(self, "_backward_done", True)
-        object.__setattr__(self, "explicit_steps", getattr(self, "explicit_steps", 0) + 1)  # for tests / bench.py's line
+                st.head_done(early)  # all-reduce of the head's slice of the flat gradient
+                self._bottom_backward(step, g_dense, st)
+            self._end_step(g, st, late=not early)
+        loss, logits = g_head.static_outputs
         return loss.detach(), (loss.detach(), logits.detach(), batch.labels.detach())
 
-    def _explicit_step_halves(self, batch, step, g_dense, half, B: int):
-        """The explicit step with the exchange in two half-batches (capture_hip_graphs(half_batches=True)):
-
-            lookup (whole batch) -> all-to-all half 0, half 1 -> bottom MLP
+    def _explicit_step_halves(self, batch, step, g: _Captured):
+        """The explicit step with the exchange in two half-batches (capture_hip_graphs(half_batches=True)); the head's part:
             half 0: wait, unpack, head forward, head backward (input gradients), pack, gradient all-to-all 0
             half 1: the same — its embeddings crossed the links during half 0's work, half 0's gradients cross during this
-            weight gradients of both halves, bottom-MLP backward (gradient all-to-all 1 in flight), embedding backward."""
-        heads, Bh = half["heads"], half["Bh"]
+            weight gradients of both halves (gradient all-to-all 1 in flight)."""
+        if not getattr(step, "halves", False):
+            raise RuntimeError("DLRMTrain: the head segments were captured for half-batch exchanges, the collection did "
+                               "not start one")
+        st, g_dense, half, heads = self._flat(), g.dense, g.half, g.heads
+        Bh, gs_all = half["Bh"], half["gs"].view(g.batch, -1)
         with torch.no_grad():
-            if batch.dense_features.data_ptr() != g_dense.static_inputs[0].data_ptr():
-                g_dense.static_inputs[0].copy_(batch.dense_features)
-            g_dense.fwd_graph.replay()
+            self._bottom_forward(batch, g_dense)
             half["labels"].copy_(batch.labels)
-            if not getattr(self, "_loss_grad_ready", False):
+            if not g.loss_grad_ready:
                 for gh in heads:
                     gh.static_grad_outputs[0].fill_(0.5)  # loss = (mean of half 0 + mean of half 1) / 2
-                object.__setattr__(self, "_loss_grad_ready", True)
-            gs_all = half["gs"].view(B, -1)
-            between = getattr(self, "_between", None)
+                g.loss_grad_ready = True
             with label("## backward ##"):  # train_pipeline.py:546 (the halves' forwards are inside: they alternate)
                 for h, gh in enumerate(heads):
                     step.finish_half(h)  # into the rows of the pooled buffer this segment reads
                     gh.fwd_graph.replay()
-                    if h == 0 and between is not None:
-                        between()
+                    if h == 0:
+                        self._between()
                     gh.bwd_graph.replay()  # ends with the gradients of this half's pooled embeddings / bottom-MLP output
                     step.start_backward_half(h, gs_all[h * Bh:(h + 1) * Bh], grad_out=gs_all if h == 1 else None)
                 for gh in heads:
-                    if getattr(gh, "bwd_graph2", None) is not None:
+                    if gh.bwd_graph2 is not None:
                         gh.bwd_graph2.replay()  # weight gradients, while the gradient all-to-alls are in flight
-                n, nl = half["n_head_used"], self._flat_dense.get("n_late", 0)
-                st = self._flat_dense
-                st["flat"][nl:n].add_(half["tmp"][nl:n])
-                half["reduce_head"]()  # all-reduce of the head's slice of the flat gradient (without the late part)
-                g_dense.bwd_graph.replay()
-                if getattr(g_dense, "bwd_graph2", None) is not None:
-                    g_dense.bwd_graph2.replay()
-                if g_dense.after_backward is not None:
-                    g_dense.after_backward()
-                if st["fired"] == 2:
-                    self._start_rest_reduce(st)
-                step.finish_backward()
-            prefetch = getattr(self, "_prefetch", None)
-            if prefetch is not None:
-                object.__setattr__(self, "_prefetched", prefetch())  # (kjt, ExplicitLookupStep) of the NEXT batch, or None
-            if nl:
-                for gh in heads:
-                    gh.bwd_graph3.replay()  # late weight gradients: behind the next step's first half-batch all-to-all
-                st["flat"][:nl].add_(half["tmp"][:nl])
-                st["reduce_late"]()
+                st.flat[st.n_late:half["n_used"]].add_(half["tmp"][st.n_late:half["n_used"]])
+                st.head_done()  # all-reduce of the head's slice of the flat gradient (without the late part)
+                self._bottom_backward(step, g_dense, st)
+            self._end_step(g, st, late=True)
             loss = (heads[0].static_outputs[0] + heads[1].static_outputs[0]) * 0.5
             logits = torch.cat([heads[0].static_outputs[1], heads[1].static_outputs[1]])
-        object.__setattr__(self, "_backward_done", True)
-        object.__setattr__(self, "explicit_steps", getattr(self, "explicit_steps", 0) + 1)
-        object.__setattr__(self, "half_batch_steps", getattr(self, "half_batch_steps", 0) + 1)  # for tests / bench.py's line
+        self.half_batch_steps += 1
         return loss.detach(), (loss.detach(), logits.detach(), batch.labels.detach())
+
+    def _bottom_forward(self, batch, g_dense) -> None:
+        """Both steps' prologue: the bottom MLP (graph), while the pooled all-to-all is in flight."""
+        if batch.dense_features.data_ptr() != g_dense.static_inputs[0].data_ptr():
+            g_dense.static_inputs[0].copy_(batch.dense_features)
+        g_dense.fwd_graph.replay()
+
+    def _bottom_backward(self, step, g_dense, st: _FlatDenseGrads) -> None:
+        """Both steps' epilogue inside the backward label: the bottom MLP's backward, then the embedding backward."""
+        g_dense.bwd_graph.replay()  # its grad_output buffer IS the head's gradient w.r.t. the bottom-MLP output
+        if g_dense.bwd_graph2 is not None:
+            g_dense.bwd_graph2.replay()  # its weight / bias gradients, finished into the flat buffer
+        st.dense_done()
+        st.start_rest()  # ahead of the embedding update and of the next step's all-to-all
+        step.finish_backward()
+
+    def _end_step(self, g: _Captured, st: _FlatDenseGrads, late: bool) -> None:
+        """Both steps' epilogue behind the embedding backward."""
+        if self._prefetch is not None:
+            self._prefetched = self._prefetch()  # (kjt, ExplicitLookupStep) of the NEXT batch, or None
+        if late and g.heads[-1].bwd_graph3 is not None:
+            # the late part of the head's weight gradients: behind the NEXT step's lookup + (first half-batch) pooled
+            # all-to-all when the owner prefetches (its cover on the links), right here otherwise
+            for gh in g.heads:
+                gh.bwd_graph3.replay()
+            if g.half is not None:
+                st.flat[:st.n_late].add_(g.half["tmp"][:st.n_late])
+            st.reduce_late()
+        self._backward_done = True
+        self.explicit_steps += 1
 
     def forward(self, batch) -> Tuple[torch.Tensor, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         g = self._graphs
         if (g is not None and self.training and torch.is_grad_enabled()
-                and batch.dense_features.shape[0] == g[0] and batch.dense_features.is_cuda):
-            _, g_dense, g_head = g
-            if getattr(self, "_flat_dense", None) is not None and getattr(self, "_between", None) is not None:
+                and batch.dense_features.shape[0] == g.batch and batch.dense_features.is_cuda):
+            if self._flat() is not None and self._between is not None:
                 # only under an owner that asked for it (set_between_forward_and_backward) and will skip loss.backward()
-                out = self._explicit_step(batch, g_dense, g_head)
-                object.__setattr__(self, "_between", None)
-                object.__setattr__(self, "_prefetch", None)
+                out = self._explicit_step(batch, g)
+                self._between = self._prefetch = None
                 if out is not None:
                     return out
-            if getattr(self, "_half", None) is not None:
+            if g.half is not None:
                 raise RuntimeError("DLRMTrain: graphs captured with half_batches=True serve the explicit step only (run the "
                                    "model under TrainPipelineSparseDist, or capture with half_batches=False)")
-            if getattr(self, "_graph_exchange", False):
+            if g.graph_exchange:
                 raise RuntimeError("DLRMTrain: these graphs unpack / pack the pooled exchange themselves and serve the explicit "
                                    "step only (run the model under TrainPipelineSparseDist, or set TORCHREC_AMD_GRAPH_EXCHANGE=0)")
+            g_head = g.heads[0]
             pending = self.model.sparse_arch.start(batch.sparse_features)
-            embedded_dense = g_dense(batch.dense_features)
+            embedded_dense = g.dense(batch.dense_features)
             embedded_sparse = self.model.sparse_arch.finish(pending)
-            object.__setattr__(self, "_loss_grad_ready", False)  # autograd writes whatever d(loss) the caller backpropagates
+            g.loss_grad_ready = False  # autograd writes whatever d(loss) the caller backpropagates
             loss, logits = g_head(embedded_dense, embedded_sparse, batch.labels.to(g_head.static_inputs[2].dtype))
             return loss, (loss.detach(), logits.detach(), batch.labels.detach())
         logits = self.model(batch.dense_features, batch.sparse_features).squeeze(-1)
