@@ -244,6 +244,30 @@ int tbe_backward_apply_f32(const uint64_t* feat_weights, const int32_t* feat_D,
                            int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* Once-touched rows (pooling factor 1, EXACT_SGD, FP32 tables): a contribution whose row no other contribution of the
+ * call touches needs no coalescing, so whoever computes its gradient row can apply the update on the spot
+ * (tbe_dlrm_interaction_gather_backward_sgd_f32 below) and the update kernel can leave it out.
+ *   tbe_backward_single_flags: on the workspace a tbe_backward_prepare call filled for (N = F*B ids, one per bag, no
+ *     TBE_FLAG_WEIGHTED, pooled), on the same stream or after it.  Writes all of single[N]: single[f*B + b] = 1 exactly
+ *     when the id of bag (f, b) gave a valid row key that no other id of the call gave, else 0.
+ *   tbe_backward_apply_skip_single_f32: tbe_backward_apply_f32 for a caller that has ALREADY written
+ *     w <- fmaf(-learning_rate, g + 0, w) into every row flagged by tbe_backward_single_flags (g = the row's gradient):
+ *     those contributions are neither loaded nor applied (the decision is the flags' rule, taken on the same sorted keys,
+ *     so every valid contribution is applied exactly once); their grad_out rows are never read.  Everything else, the
+ *     profiling row counter included, is tbe_backward_apply_f32.  EXACT_SGD, SUM pooling, no per-sample weights,
+ *     N == F*B, max_D <= 128. */
+int tbe_backward_single_flags(int32_t F, int32_t B, int32_t max_D, int32_t key_bits, int64_t N, void* workspace,
+                              size_t workspace_bytes, uint8_t* single, void* stream);
+int tbe_backward_apply_skip_single_f32(const uint64_t* feat_weights, const int32_t* feat_D,
+                                       const int64_t* feat_out_offset, const int64_t* feat_rows,
+                                       const int64_t* feat_row_base, const uint64_t* feat_state0,
+                                       const uint64_t* feat_state1, int32_t F, int32_t B,
+                                       int32_t max_D, int32_t key_bits, const int64_t* indices, int64_t N,
+                                       const int64_t* offsets, const float* per_sample_weights,
+                                       int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+                                       int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Gradient of the pooled lookup with respect to per_sample_weights (fbgemm's grad_indice_weights): what
  * trains the position weights of torchrec/modules/feature_processor.py:29-74 (PositionWeightedModule) in
@@ -676,6 +700,16 @@ int tbe_dlrm_interaction_gather_backward_f32(const float* dense, const uint64_t*
                                              const int64_t* feat_window, const int64_t* indices, const float* grad_out,
                                              int64_t grad_row_stride, int32_t B, int32_t F, int32_t D, float* grad_dense,
                                              float* grad_sparse, int32_t* bounds_errors, void* stream);
+/* The gather backward that also applies exact SGD to the once-touched rows: where single[f*B + b] != 0
+ * (tbe_backward_single_flags) and the id selects a table row, that row becomes fmaf(-learning_rate, g + 0, w) in place
+ * (g = the contribution's gradient row, w = the row as the kernel loaded it) and grad_sparse[b, f*D .. (f+1)*D) is NOT
+ * written.  Everything else is tbe_dlrm_interaction_gather_backward_f32, bit for bit; follow it with
+ * tbe_backward_apply_skip_single_f32 on the same sort and the tables end exactly as after the plain pair of calls. */
+int tbe_dlrm_interaction_gather_backward_sgd_f32(const float* dense, const uint64_t* feat_weights, const int64_t* feat_rows,
+                                                 const int64_t* feat_window, const int64_t* indices, const float* grad_out,
+                                                 int64_t grad_row_stride, int32_t B, int32_t F, int32_t D, float* grad_dense,
+                                                 float* grad_sparse, int32_t* bounds_errors, const uint8_t* single,
+                                                 float learning_rate, void* stream);
 
 /* ReLU backward + bias gradient of one MLP layer in one pass (torchrec/modules/mlp.py:14-170 Perceptron
  * trained through autograd: threshold_backward + sum(0)):

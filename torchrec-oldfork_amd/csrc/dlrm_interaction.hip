@@ -701,7 +701,18 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_fwd_kernel(const fl
 
 // Backward.  The rows are staged through registers as in interaction_bwd_kernel; the feature lanes load the ids one
 // sample further ahead than the rows (one 8-B load per lane and sample), so a row load never waits for its id.
-template <int NT>  // NT = D / 16 column tiles
+//
+// SGD: the variant that also applies the exact-SGD update of the rows a batch touches ONCE.  `single[f * B + b]` (one
+// byte per contribution, tbe_backward_single_flags) says that contribution (f, b) is the only one of the call that
+// touches its row: the row's gradient is then this sample's dX row alone, the old row w sits in the LDS image until dX
+// overwrites it, and the row's address is the one the kernel loaded it from.  Such a row is written to the table as
+// fmaf(-lr, dX + 0, w) — what bwd_update_kernel computes for it — instead of to grad_sparse, whose rows of flagged
+// contributions stay unwritten; the update kernel of the same call skips them (tbe_backward_apply_skip_single_f32).
+// The feature lanes load the flag where they load the id, one sample ahead of the rows.  No extra LDS, no second read of
+// a row, no address the plain kernel does not dereference.  No other wave reads a flagged row (no other contribution has
+// its key), and a zero row (address 0) is never flagged.  The row loads and the row stores go through plain pointers:
+// nothing tells the compiler that the tables are read-only or disjoint from what is stored.
+template <int NT, bool SGD = false>  // NT = D / 16 column tiles
 __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const float* __restrict__ dense,
                                                                        const uint64_t* __restrict__ feat_weights,
                                                                        const int64_t* __restrict__ feat_rows,
@@ -711,7 +722,8 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
                                                                        float* __restrict__ grad_dense,
                                                                        float* __restrict__ grad_sparse,
                                                                        int32_t* __restrict__ bounds_errors, int B, int F,
-                                                                       int64_t grad_stride) {
+                                                                       int64_t grad_stride,
+                                                                       const uint8_t* __restrict__ single, float lr) {
   extern __shared__ float smem[];
   constexpr int D = NT * 16;
   constexpr int XS = D + 16;
@@ -748,6 +760,20 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
 
   const GatherLane gl = load_gather_lane(feat_weights, feat_rows, feat_window, lane, F);
   const int64_t* my_ids = indices + static_cast<int64_t>(min(lane, F - 1)) * B;
+  // SGD only.  Contribution (f, sample) is "once" when it is flagged and its row address is a table row's.  A ballot
+  // makes that a wave-uniform mask (bit f), and the feature lane leaves the address (0 when not once) in the pad columns
+  // of row f + 1 of the LDS image — columns D .. D+15 exist for the bank layout and nothing else touches them — for the
+  // lanes that store the row.  Two slots per row, used in turn: the sample in flight is published while the sample
+  // being computed still needs its own.
+  auto my_single = [&](int s) { return single[(my_ids + s) - indices]; };  // (no second per-lane pointer: registers)
+  uint32_t once_in_flight = 0;  // wave-uniform mask of the sample whose rows are in flight
+  uint32_t next_single = 0;     // feature lane: flag of the sample after it (loaded with next_id)
+  int slot = 0;                 // of the sample being computed
+  auto publish_once = [&](uint64_t row_addr, uint32_t flag, int into_slot) {
+    const bool once = lane < F && row_addr != 0 && flag != 0;
+    if (lane < F) reinterpret_cast<uint64_t*>(xs + (lane + 1) * XS + D)[into_slot] = once ? row_addr : 0;
+    return static_cast<uint32_t>(__ballot(once));
+  };
   int nbad = 0;
   float4 pre[MAXV];
   float gpre[MAXP];
@@ -770,8 +796,13 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
   int b = blockIdx.x * 4 + wave;
   int64_t next_id = 0;  // this lane's id of the sample AFTER the one whose rows are in flight
   if (b < B) {
-    load_x(b, gather_row_address<D>(gl, my_ids[b], 0, nbad));
-    if (b + stride_b < B) next_id = my_ids[b + stride_b];
+    const uint64_t row_addr = gather_row_address<D>(gl, my_ids[b], 0, nbad);
+    if constexpr (SGD) once_in_flight = publish_once(row_addr, my_single(b), 0);
+    load_x(b, row_addr);
+    if (b + stride_b < B) {
+      next_id = my_ids[b + stride_b];
+      if constexpr (SGD) next_single = my_single(b + stride_b);
+    }
 #pragma unroll
     for (int t = 0; t < MAXP; ++t) {
       const int p = lane + t * kWave;
@@ -779,6 +810,8 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
     }
   }
   for (; b < B; b += stride_b) {
+    // SGD: sample b's mask, kept across the prefetch of the next sample; bit r = row r is once (row 0, the dense row, never)
+    const uint32_t once_b = once_in_flight << 1;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
       const int v = lane + i * kWave;
@@ -806,8 +839,13 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
     }
     const int nb = b + stride_b;
     if (nb < B) {
-      load_x(nb, gather_row_address<D>(gl, next_id, 0, nbad));
-      if (nb + stride_b < B) next_id = my_ids[nb + stride_b];
+      const uint64_t row_addr = gather_row_address<D>(gl, next_id, 0, nbad);
+      if constexpr (SGD) once_in_flight = publish_once(row_addr, next_single, slot ^ 1);
+      load_x(nb, row_addr);
+      if (nb + stride_b < B) {
+        next_id = my_ids[nb + stride_b];
+        if constexpr (SGD) next_single = my_single(nb + stride_b);
+      }
 #pragma unroll
       for (int t = 0; t < MAXP; ++t) {
         const int p = lane + t * kWave;
@@ -833,35 +871,91 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
       }
     }
     wave_lds_fence();  // every lane is done reading X before it is overwritten with dX
+    if constexpr (SGD) {
+      // A flagged row becomes the NEW table row: w - lr * dX with the operands and roundings of bwd_update_kernel +
+      // apply_row (the gradient is first added to the +0 accumulator, then one fmaf), w read from the very LDS word
+      // that is overwritten.  One instruction stream for both kinds of row (a select, no divergent copies of the
+      // stores): the old words of a row are read whether it is once or not.
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < NT; ++n)
+      for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int row = 16 * m + 4 * kq + q;
-          if (row < R) xs[row * XS + 16 * n + r16] = acc[m][n][q];
-        }
-    wave_lds_fence();
+          if (row < R) {
+            float* xw = xs + row * XS + r16;
+            const bool once = ((once_b >> row) & 1u) != 0;
+            float w[NT];
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int v = lane + i * kWave;
-      if (v < nvec) {
-        const int r = v >> LOG_V;
-        const int c = (v & ((1 << LOG_V) - 1)) * 4;
-        float4 x = ld4(xs + r * XS + c);
-        if (r == 0) {  // v == lane < D/4 here
-          x.x += gdense.x;
-          x.y += gdense.y;
-          x.z += gdense.z;
-          x.w += gdense.w;
-          st4(grad_dense + static_cast<int64_t>(b) * D + c, x);
-        } else {
-          st4(grad_sparse + (static_cast<int64_t>(b) * F + (r - 1)) * D + c, x);
+            for (int n = 0; n < NT; ++n) w[n] = xw[16 * n];
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+              const float g = acc[m][n][q];
+              xw[16 * n] = once ? fmaf(-lr, fmaf(1.f, g, 0.f), w[n]) : g;
+            }
+          }
+        }
+    } else {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int row = 16 * m + 4 * kq + q;
+            if (row < R) xs[row * XS + 16 * n + r16] = acc[m][n][q];
+          }
+    }
+    wave_lds_fence();
+    if constexpr (SGD) {
+      // The plain store loop below with its addresses spelled as ONE per-lane base plus a compile-time offset per
+      // instruction (v = lane + 64 i gives row r0 + i * RPV, column c0 and grad_sparse element 4 v - D): the kernel has
+      // no registers left for fourteen hoisted copies of each.
+      constexpr int RPV = kWave >> LOG_V;  // rows per store instruction
+      const int r0 = lane >> LOG_V;
+      const int c0 = (lane & ((1 << LOG_V) - 1)) * 4;
+      const float* xl = xs + r0 * XS + c0;
+      const uint64_t* sl = reinterpret_cast<const uint64_t*>(xs + r0 * XS + D) + slot;
+      float* gsl = grad_sparse + (static_cast<int64_t>(b) * F - 1) * D + 4 * lane;
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i) {
+        const int r = r0 + i * RPV;
+        if (r < R) {
+          float4 x = ld4(xl + i * RPV * XS);
+          if (i == 0 && r == 0) {  // lanes < D/4 of the first instruction: c0 = 4 * lane
+            x.x += gdense.x;
+            x.y += gdense.y;
+            x.z += gdense.z;
+            x.w += gdense.w;
+            st4(grad_dense + static_cast<int64_t>(b) * D + c0, x);
+          } else {
+            // where a once row came from, else 0 (a lane of row 0 never gets here)
+            const uint64_t table_row = sl[i * RPV * (XS / 2)];
+            st4(table_row != 0 ? reinterpret_cast<float*>(table_row) + c0 : gsl + i * (4 * kWave), x);
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i) {
+        const int v = lane + i * kWave;
+        if (v < nvec) {
+          const int r = v >> LOG_V;
+          const int c = (v & ((1 << LOG_V) - 1)) * 4;
+          float4 x = ld4(xs + r * XS + c);
+          if (r == 0) {  // v == lane < D/4 here
+            x.x += gdense.x;
+            x.y += gdense.y;
+            x.z += gdense.z;
+            x.w += gdense.w;
+            st4(grad_dense + static_cast<int64_t>(b) * D + c, x);
+          } else {
+            st4(grad_sparse + (static_cast<int64_t>(b) * F + (r - 1)) * D + c, x);
+          }
         }
       }
     }
     wave_lds_fence();
+    slot ^= 1;
   }
   report_bad_ids(nbad, bounds_errors);
 }
@@ -1038,12 +1132,55 @@ extern "C" int tbe_dlrm_interaction_gather_backward_f32(const float* dense, cons
     attr_set = true;
   }
   const dim3 grid(interaction_grid(B));
+  const uint8_t* const no_flags = nullptr;
   if (D == 128)
     hipLaunchKernelGGL(interaction_gather_bwd_kernel<8>, grid, dim3(256), lds, st, dense, feat_weights, feat_rows,
-                       feat_window, indices, grad_out, grad_dense, grad_sparse, bounds_errors, B, F, grad_row_stride);
+                       feat_window, indices, grad_out, grad_dense, grad_sparse, bounds_errors, B, F, grad_row_stride,
+                       no_flags, 0.f);
   else
     hipLaunchKernelGGL(interaction_gather_bwd_kernel<4>, grid, dim3(256), lds, st, dense, feat_weights, feat_rows,
-                       feat_window, indices, grad_out, grad_dense, grad_sparse, bounds_errors, B, F, grad_row_stride);
+                       feat_window, indices, grad_out, grad_dense, grad_sparse, bounds_errors, B, F, grad_row_stride,
+                       no_flags, 0.f);
+  TBE_CHECK_LAUNCH(what);
+  return TBE_OK;
+}
+
+extern "C" int tbe_dlrm_interaction_gather_backward_sgd_f32(const float* dense, const uint64_t* feat_weights,
+                                                            const int64_t* feat_rows, const int64_t* feat_window,
+                                                            const int64_t* indices, const float* grad_out,
+                                                            int64_t grad_row_stride, int32_t B, int32_t F, int32_t D,
+                                                            float* grad_dense, float* grad_sparse,
+                                                            int32_t* bounds_errors, const uint8_t* single,
+                                                            float learning_rate, void* stream) {
+  const char* what = "tbe_dlrm_interaction_gather_backward_sgd_f32";
+  if (int rc = check_gather_args(what, B, F, D, grad_row_stride)) return rc;
+  TBE_REQUIRE(dense && feat_weights && feat_rows && indices && grad_out && grad_dense && grad_sparse && single,
+              "%s: null pointer", what);
+  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(dense) | reinterpret_cast<uintptr_t>(grad_dense) |
+                reinterpret_cast<uintptr_t>(grad_sparse)) & 15) == 0 && (reinterpret_cast<uintptr_t>(indices) & 7) == 0,
+              "%s: tensors must be 16-B aligned, indices 8-B aligned", what);
+  if (B == 0) return TBE_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // the LDS of the plain kernel, to the byte: two workgroups fill a CU at D = 128
+  const size_t lds = 4 * (static_cast<size_t>(28) * (D + 16) + 32 * 34) * sizeof(float);
+  static bool attr_set = false;
+  if (!attr_set) {
+    const size_t big = 4 * (28 * (128 + 16) + 32 * 34) * sizeof(float);
+    if (!reserve_lds(interaction_gather_bwd_kernel<8, true>, big) || !reserve_lds(interaction_gather_bwd_kernel<4, true>, big)) {
+      set_error("%s: cannot reserve LDS", what);
+      return TBE_ERR_LAUNCH;
+    }
+    attr_set = true;
+  }
+  const dim3 grid(interaction_grid(B));
+  if (D == 128)
+    hipLaunchKernelGGL((interaction_gather_bwd_kernel<8, true>), grid, dim3(256), lds, st, dense, feat_weights, feat_rows,
+                       feat_window, indices, grad_out, grad_dense, grad_sparse, bounds_errors, B, F, grad_row_stride,
+                       single, learning_rate);
+  else
+    hipLaunchKernelGGL((interaction_gather_bwd_kernel<4, true>), grid, dim3(256), lds, st, dense, feat_weights, feat_rows,
+                       feat_window, indices, grad_out, grad_dense, grad_sparse, bounds_errors, B, F, grad_row_stride,
+                       single, learning_rate);
   TBE_CHECK_LAUNCH(what);
   return TBE_OK;
 }

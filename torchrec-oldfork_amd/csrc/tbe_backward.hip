@@ -23,6 +23,9 @@
 //                 order and applies the update.
 // Fixed chunks keep the work balanced no matter how skewed the ids are (a 3-row table
 // receives B contributions per row).
+// Between 2 and 3 a caller at one id per bag may ask which contributions touch their row alone
+// (tbe_backward_single_flags), apply exact SGD to those rows where it computes their gradient, and have the
+// update leave them out (tbe_backward_apply_skip_single_f32; key_is_single in tbe_backward_impl.hpp is the rule of both).
 #include "tbe_backward_impl.hpp"
 
 namespace tbe {
@@ -131,6 +134,22 @@ static int prepare(const BwdArgs& a, const BwdWorkspace& w, hipStream_t st) {
   return where < 0 ? where : TBE_OK;
 }
 
+// single[payload of sorted position k] = key_is_single.  With one id per bag (offsets[i] == i, what the entry is for) the
+// payloads are the bag numbers 0 .. N-1, each once, so every byte of the array is written, zeros included.  A position
+// that malformed offsets left uncovered carries no payload: whatever it holds is bounded by N before it is used.
+template <typename KeyT>
+__global__ __launch_bounds__(256) void bwd_single_flags_kernel(const KeyT* __restrict__ skey, const uint32_t* __restrict__ spay,
+                                                                int64_t N, int key_bits, uint8_t* __restrict__ single) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (k >= N) return;
+  const KeyT sentinel = static_cast<KeyT>((key_bits >= 64) ? ~0ull : ((1ull << key_bits) - 1ull));
+  const KeyT key = skey[k];
+  const KeyT prev = k > 0 ? skey[k - 1] : sentinel;
+  const KeyT next = k + 1 < N ? skey[k + 1] : sentinel;
+  const uint32_t i = spay[k];
+  if (i < N) single[i] = key_is_single<KeyT>(key, prev, k > 0, next, k + 1 < N, sentinel) ? 1 : 0;
+}
+
 int run_prepare(const BwdArgs& a, const BwdWorkspace& w, bool wide_payload, hipStream_t st) {
   if (a.key_bits > 32) return wide_payload ? prepare<uint64_t, uint64_t>(a, w, st) : prepare<uint64_t, uint32_t>(a, w, st);
   return wide_payload ? prepare<uint32_t, uint64_t>(a, w, st) : prepare<uint32_t, uint32_t>(a, w, st);
@@ -211,6 +230,55 @@ extern "C" int tbe_backward_apply_f32(
   c.stream = stream;
   c.who = "tbe_backward_apply_f32";
   c.phase = kPhaseApply;
+  return backward_entry<float>(c);
+}
+
+extern "C" int tbe_backward_single_flags(int32_t F, int32_t B, int32_t max_D, int32_t key_bits, int64_t N, void* workspace,
+                                         size_t workspace_bytes, uint8_t* single, void* stream) {
+  const char* who = "tbe_backward_single_flags";
+  TBE_REQUIRE(F > 0 && B >= 0 && N == static_cast<int64_t>(F) * B, "%s: needs exactly one id per bag (N == F * B)", who);
+  TBE_REQUIRE(max_D > 0 && max_D <= 2048 && key_bits >= 1 && key_bits <= 64, "%s: max_D=%d key_bits=%d", who, max_D, key_bits);
+  TBE_REQUIRE(N < kSortMaxPairs, "%s: N = %lld ids in one call; the limit is 2^29 - 1", who, static_cast<long long>(N));
+  if (N == 0) return TBE_OK;
+  TBE_REQUIRE(workspace && single, "%s: null pointer", who);
+  TBE_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-B aligned", who);
+  BwdWorkspace w;
+  if (int rc = carve(workspace, N, max_D, key_bits, &w)) return rc;
+  if (w.total > workspace_bytes) {
+    set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, w.total);
+    return TBE_ERR_WORKSPACE;
+  }
+  // where bwd_setup finds the sorted pairs
+  const bool in_second = (radix_passes(key_bits) & 1) != 0;
+  const void* keys = in_second ? w.keys_out : w.keys_in;
+  const uint32_t* pay = static_cast<const uint32_t*>(in_second ? w.pay_out : w.pay_in);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(static_cast<unsigned>((N + 255) / 256));
+  if (key_bits > 32)
+    hipLaunchKernelGGL(bwd_single_flags_kernel<uint64_t>, grid, dim3(256), 0, st, static_cast<const uint64_t*>(keys), pay, N,
+                       key_bits, single);
+  else
+    hipLaunchKernelGGL(bwd_single_flags_kernel<uint32_t>, grid, dim3(256), 0, st, static_cast<const uint32_t*>(keys), pay, N,
+                       key_bits, single);
+  TBE_CHECK_LAUNCH(who);
+  return TBE_OK;
+}
+
+extern "C" int tbe_backward_apply_skip_single_f32(
+    const uint64_t* feat_weights, const int32_t* feat_D, const int64_t* feat_out_offset,
+    const int64_t* feat_rows, const int64_t* feat_row_base, const uint64_t* feat_state0,
+    const uint64_t* feat_state1, int32_t F, int32_t B, int32_t max_D,
+    int32_t key_bits, const int64_t* indices, int64_t N, const int64_t* offsets,
+    const float* per_sample_weights, int32_t pooling_mode, const int32_t* feat_pooling, const float* grad_out,
+    int64_t grad_row_stride, tbe_optimizer_args opt, int32_t flags, void* workspace,
+    size_t workspace_bytes, void* stream) {
+  BwdCall c{feat_weights, feat_D, feat_out_offset, feat_rows, feat_row_base, feat_state0, feat_state1, F, B, max_D,
+            key_bits, indices, N, offsets, per_sample_weights, pooling_mode, feat_pooling, grad_out, grad_row_stride,
+            opt, flags, workspace, workspace_bytes};
+  c.stream = stream;
+  c.who = "tbe_backward_apply_skip_single_f32";
+  c.phase = kPhaseApply;
+  c.skip_single = true;
   return backward_entry<float>(c);
 }
 

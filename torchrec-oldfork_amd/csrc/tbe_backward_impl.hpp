@@ -56,7 +56,20 @@ struct BwdArgs {
   // _Float16 tables only: how the FP32 result of a row update becomes a half (TBE_ROUND_*)
   int32_t rounding;
   uint32_t round_hash;  // call_hash(seed, opt.iteration)
+  // host side only (launch_update picks the kernel by it): leave the single contributions to the caller, who has
+  // applied them already (tbe_backward_apply_skip_single_f32)
+  int32_t skip_single;
 };
+
+// The ONE rule for "contribution k (sorted position) is the only contribution of the call to its row": a valid key
+// (below the sentinel) that neither sorted neighbour shares.  `has_prev` / `has_next`: the position is not the first /
+// last of the sorted array.  tbe_backward_single_flags publishes it per contribution and the gather backward applies
+// SGD to exactly those rows; bwd_update_kernel<..., SKIP> leaves exactly those out.  A single's run has length one, so
+// it never crosses a chunk boundary: partials, origin list and fix-up never see it.
+template <typename KeyT>
+__device__ __forceinline__ bool key_is_single(KeyT key, KeyT prev, bool has_prev, KeyT next, bool has_next, KeyT sentinel) {
+  return key < sentinel && !(has_prev && prev == key) && !(has_next && next == key);
+}
 
 template <typename PayT>
 __device__ __forceinline__ PayT make_payload(uint32_t bag, uint32_t pos) {
@@ -461,7 +474,9 @@ struct BwdUnroll {
 
 // FAST: every feature has dim a.fast_D (multiple of 4), SUM pooling, no per-sample weights, every
 // row base 16-B aligned (TBE_FLAG_UNIFORM_ALIGNED from the host) — the Criteo configuration.
-template <typename WT, typename KeyT, typename PayT, int G, int NV, int OPTC, bool FAST, int U, int MINW>
+// SKIP: single contributions (key_is_single) were applied by the caller: no gradient-row load, no weight-row load, no
+// apply_row for them; they still count as updated rows.
+template <typename WT, typename KeyT, typename PayT, int G, int NV, int OPTC, bool FAST, int U, int MINW, bool SKIP = false>
 __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
   constexpr int NG = kWave / G;
   const int lane = threadIdx.x & 63;
@@ -510,7 +525,12 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
       pay_k = spay[kk];
       if (kk + 1 < a.N) keyn_k = skey[kk + 1];
     }
-    const bool valid_k = in && key_k < sentinel;  // sentinel = invalid id; anything above = never written
+    bool single_k = false;
+    if constexpr (SKIP) {
+      if (in) single_k = key_is_single<KeyT>(key_k, kk > 0 ? skey[kk - 1] : sentinel, kk > 0, keyn_k, kk + 1 < a.N, sentinel);
+    }
+    // sentinel = invalid id; anything above = never written; a skipped single is no work for this kernel
+    const bool valid_k = in && key_k < sentinel && !single_k;
     const bool last_k = valid_k && (key_k != keyn_k || kk + 1 >= a.N);
     const uint32_t bag_k = payload_bag<PayT>(pay_k);
     const uint32_t pos_k = payload_pos<PayT>(pay_k);
@@ -554,6 +574,9 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
       for (int u = 0; u < U; ++u) {
         const int src = gbase + ((j + u) & (G - 1));
         const bool inb = (j + u) < n;
+        // (a skipped single still takes its trip of this loop: walking only the lanes with work — tried, the set bits
+        // of a ballot — made the kernel 5 % slower, not faster)
+        if constexpr (SKIP) nrows += (inb && __shfl(static_cast<int>(single_k), src, kWave) != 0) ? 1 : 0;
         val[u] = inb && (__shfl(static_cast<int>(valid_k), src, kWave) != 0);
         lst[u] = inb && (__shfl(static_cast<int>(last_k), src, kWave) != 0);
         wt[u] = FAST ? 1.f : __shfl(w_k, src, kWave);
@@ -872,7 +895,21 @@ static int launch_update(const BwdArgs& a, hipStream_t st) {
     const int oc = a.opt.optimizer;
 #define TBE_UPD(OPTC, FAST_, UU, MW) \
   hipLaunchKernelGGL((bwd_update_kernel<WT, KeyT, PayT, G, NV, OPTC, FAST_, UU, MW>), dim3(grid), dim3(256), 0, st, a)
-    if (is_norm_family(oc)) {
+#define TBE_UPD_SKIP(OPTC, FAST_, UU, MW) \
+  hipLaunchKernelGGL((bwd_update_kernel<WT, KeyT, PayT, G, NV, OPTC, FAST_, UU, MW, true>), dim3(grid), dim3(256), 0, st, a)
+    if (a.skip_single) {
+      // EXACT_SGD on float tables of dim <= 128 with bag payloads (backward_entry checks): the two kernels such a call takes
+      if constexpr (std::is_same_v<WT, float> && sizeof(PayT) == 4 && NV == 1 && G <= 32) {
+        if (G == 32 && fast) {
+          if constexpr (G == 32) TBE_UPD_SKIP(TBE_OPT_EXACT_SGD, true, 4, 4);
+        } else {
+          TBE_UPD_SKIP(-1, false, BwdUnroll<NV>::U, 1);
+        }
+      } else {
+        set_error("tbe_backward update: no kernel that skips single contributions for this configuration");
+        return TBE_ERR_UNSUPPORTED;
+      }
+    } else if (is_norm_family(oc)) {
       TBE_UPD(kOptNormFamily, false, BwdUnroll<NV>::U, 1);
     } else if constexpr (G == 32 && NV == 1) {  // the fast kernels exist for the one (G, NV) pair that can reach them
       if (fast && oc == TBE_OPT_EXACT_SGD) {
@@ -889,6 +926,7 @@ static int launch_update(const BwdArgs& a, hipStream_t st) {
       TBE_UPD(-1, false, BwdUnroll<NV>::U, 1);
     }
 #undef TBE_UPD
+#undef TBE_UPD_SKIP
   }
   TBE_CHECK_LAUNCH("tbe_backward update");
   const unsigned fgrid = static_cast<unsigned>(std::min<int64_t>((nchunks + 3) / 4, 1024));
@@ -944,6 +982,7 @@ struct BwdCall {
   int32_t rounding = TBE_ROUND_NEAREST_EVEN;  // _f16w
   uint64_t seed = 0;                          // _f16w
   const tbe_optimizer_ext* ext = nullptr;     // _ex
+  bool skip_single = false;                   // _skip_single
   void* stream = nullptr;
   // not arguments: which entry this is
   const char* who = nullptr;  // its name, for error messages
@@ -1003,6 +1042,14 @@ static int bwd_setup(BwdCall c, BwdArgs* args, BwdWorkspace* ws, bool* wide_payl
     default:
       set_error("%s: unknown optimizer %d", who, opt.optimizer);
       return TBE_ERR_UNSUPPORTED;
+  }
+  if (c.skip_single) {
+    // what makes sorted position <-> contribution (f, b) the mapping the caller's flags use, and the update the caller's
+    TBE_REQUIRE(opt.optimizer == TBE_OPT_EXACT_SGD && c.ext == nullptr, "%s: EXACT_SGD without extensions only", who);
+    TBE_REQUIRE(c.pooling_mode == TBE_POOL_SUM && c.per_sample_weights == nullptr && (c.flags & TBE_FLAG_WEIGHTED) == 0 &&
+                    c.N == static_cast<int64_t>(c.F) * c.B,
+                "%s: SUM pooling, no per-sample weights, exactly one id per bag (N == F * B)", who);
+    TBE_REQUIRE(c.max_D <= 128, "%s: max_D=%d above 128", who, c.max_D);
   }
   const tbe_optimizer_ext* const ext = c.ext;
   const bool clip = ext != nullptr && ext->gradient_clipping != 0;
@@ -1066,6 +1113,7 @@ static int bwd_setup(BwdCall c, BwdArgs* args, BwdWorkspace* ws, bool* wide_payl
   a.unique_rows = (c.phase & kPhaseApply) ? profile_unique_rows_counter() : nullptr;
   a.rounding = TBE_ROUND_NEAREST_EVEN;
   a.round_hash = 0;
+  a.skip_single = c.skip_single ? 1 : 0;
   // the sort ping-pongs between the two buffer pairs: an odd number of passes ends in the second
   const bool in_second = (radix_passes(c.key_bits) & 1) != 0;
   a.keys_sorted = in_second ? w.keys_out : w.keys_in;

@@ -96,6 +96,9 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_i32, c_i32, c_void_p,
          c_size, c_void_p, c_void_p, c_void_p],
     ),
+    "tbe_backward_single_flags": (
+        ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i64, c_void_p, c_size, c_void_p, c_void_p]),
+    "tbe_backward_apply_skip_single_f32": (ctypes.c_int, _BWD_COMMON + [c_void_p]),
     "tbe_sort_pairs_workspace_bytes": (c_size, [c_i64, c_i32]),
     "tbe_sort_pairs": (
         ctypes.c_int,
@@ -165,6 +168,10 @@ SIGNATURES = {
         ctypes.c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p,
          c_void_p, c_void_p]),
+    "tbe_dlrm_interaction_gather_backward_sgd_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_float, c_void_p]),
     "tbe_relu_backward_bias_grad_workspace_bytes": (c_size, [c_i64, c_i32]),
     "tbe_relu_backward_bias_grad_f32": (
         ctypes.c_int, [c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),

@@ -696,10 +696,12 @@ class _TBEBase(nn.Module):
                                "split the batch")
         return workspace(nbytes, self.current_device)
 
-    def _prepare_backward(self, indices, offsets, B: int, weighted: bool = False):
+    def _prepare_backward(self, indices, offsets, B: int, weighted: bool = False, single: Optional[torch.Tensor] = None):
         """Enqueues the gradient-independent half of backward (linearize + stable sort of the row
         keys) on a side stream, right after the forward kernel, so that it overlaps whatever the
-        caller does between forward and backward (the dense MLPs).  Returns (workspace, event)."""
+        caller does between forward and backward (the dense MLPs).  Returns (workspace, event).
+        `single` (uint8 [N], one id per bag): also filled, behind the sort and ahead of the event, with the flags of the
+        once-touched rows (include/tbe_hip.h tbe_backward_single_flags)."""
         N = indices.numel()
         if N == 0 or B == 0:
             return None
@@ -722,6 +724,13 @@ class _TBEBase(nn.Module):
                                          self._errors_ptr(), ptr(lay.feat_window), side.cuda_stream),
                 "tbe_backward_prepare",
             )
+            if single is not None:
+                single.record_stream(side)
+                check(
+                    lib.tbe_backward_single_flags(self.F, B, self.max_D, self.key_bits, N, ptr(ws), ws.numel(),
+                                                  ptr(single), side.cuda_stream),
+                    "tbe_backward_single_flags",
+                )
             ev = torch.cuda.Event()
             ev.record(side)
         return ws, ev
@@ -729,10 +738,12 @@ class _TBEBase(nn.Module):
     def _backward_impl(self, grad_out, indices, offsets, per_sample_weights, B: int,
                        opt: OptimizerArgs, state0_override: Optional[torch.Tensor] = None,
                        prepared=None, layout=None, state0_aligned: bool = False,
-                       ext: Optional[OptimizerExt] = None) -> None:
+                       ext: Optional[OptimizerExt] = None, singles_applied: bool = False) -> None:
         """`ext` (momentum / eta / gradient clipping: include/tbe_hip.h tbe_optimizer_ext) selects the _ex entries, which
         alone take the row-norm optimizers and clipping.  `prepared` (the sort already ran on the side stream: see
-        _prepare_backward) selects the apply entries, the tables' element type the _f32 / _f16w ones."""
+        _prepare_backward) selects the apply entries, the tables' element type the _f32 / _f16w ones.
+        `singles_applied` (begin_single_row_sgd): the caller has waited for the sort and updated the once-touched rows
+        itself; the update leaves them out (tbe_backward_apply_skip_single_f32)."""
         lay = self._get_layout()
         dev = self.current_device
         lib = _lib.load()
@@ -763,7 +774,8 @@ class _TBEBase(nn.Module):
             # the entry, and what it takes beyond the common list
             if prepared is not None:
                 ws, ev = prepared
-                torch.cuda.current_stream(dev).wait_event(ev)
+                if not singles_applied:  # (else begin_single_row_sgd has waited, in front of the caller's kernel)
+                    torch.cuda.current_stream(dev).wait_event(ev)
                 kind, tail = "apply", []
             else:  # no sort yet
                 ws = self._backward_workspace(N, B)
@@ -773,6 +785,10 @@ class _TBEBase(nn.Module):
             if ext is not None:
                 tail.append(ctypes_byref(ext))
             name = f"tbe_backward_{kind}{'_ex' if ext is not None else ''}{'_f16w' if f16 else '_f32'}"
+            if singles_applied:
+                if name != "tbe_backward_apply_f32" or not flags & 1:
+                    raise RuntimeError("singles_applied: only after begin_single_row_sgd() handed out the flags")
+                name = "tbe_backward_apply_skip_single_f32"
             check(
                 getattr(lib, name)(
                     ptr(lay.feat_weights), ptr(lay.feat_D), ptr(out_off), ptr(lay.feat_rows), ptr(lay.feat_row_base),
@@ -841,11 +857,12 @@ class LookupRecord:
     autograd context: a train step that knows its own schedule — models/dlrm.py, HIP-graph mode — drives forward and
     backward itself and skips the autograd engine, its per-node Python hand-offs and its worker thread)."""
 
-    __slots__ = ("indices", "offsets", "per_sample_weights", "B", "layout", "prepared", "sort_pending")
+    __slots__ = ("indices", "offsets", "per_sample_weights", "B", "layout", "prepared", "sort_pending", "single")
 
     def __init__(self, indices, offsets, per_sample_weights, B, layout) -> None:
         self.indices, self.offsets, self.per_sample_weights, self.B, self.layout = indices, offsets, per_sample_weights, B, layout
         self.prepared = None  # (workspace, event) of the backward's sort once it runs on the side stream
+        self.single = None  # uint8 [N] flags of the once-touched rows, filled behind that sort (lookup_deferred)
         self.sort_pending = False  # the lookup wants that sort but left starting it to start_backward_sort()
 
 
@@ -982,6 +999,7 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
             momentum=momentum,
         )
         self.iter = 0
+        self.single_row_sgd_steps = 0  # backwards whose once-touched rows the consumer updated (begin_single_row_sgd; tests)
         self.register_buffer("weights_dev", self._alloc("dev", self._flat_sizes["dev"], wdtype), persistent=False)
         self.register_buffer("weights_uvm", self._alloc("uvm", self._flat_sizes["uvm"], wdtype), persistent=False)
         code = _OPT_CODE[optimizer]
@@ -1138,16 +1156,45 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         indices, offsets, _, B, overlap = self._begin_lookup(indices, offsets, None, torch.is_grad_enabled())
         rec = LookupRecord(indices, offsets, None, B, None)
         if overlap:
-            rec.prepared = self._prepare_backward(indices, offsets, B)
+            if self._single_row_sgd_ok() and indices.numel() == self.F * B:
+                rec.single = torch.empty(indices.numel(), dtype=torch.uint8, device=self.current_device)
+            rec.prepared = self._prepare_backward(indices, offsets, B, single=rec.single)
+            if rec.prepared is None:
+                rec.single = None
         self._enforce_bounds_check_mode()
         return rec
 
-    def backward_no_autograd(self, rec: "LookupRecord", grad_out: torch.Tensor) -> None:
-        """Coalesced gradient + fused optimizer update for the lookup `rec` describes (what _FusedLookup.backward does)."""
+    def _single_row_sgd_ok(self) -> bool:
+        """Whether the consumer of a deferred lookup may apply the update of the once-touched rows itself
+        (begin_single_row_sgd): what gather_layout() asks plus plain exact SGD — no momentum, no clipping — on a dim the
+        gather kernels serve, so that the backward is the uniform-aligned tbe_backward_apply_f32."""
+        return (_OPT_CODE[self.optimizer] == 0 and self._optimizer_ext() is None and not self._fp16_tables()
+                and self.max_D in (64, 128) and self.gather_layout() is not None)
+
+    def begin_single_row_sgd(self, rec: "LookupRecord"):
+        """Opens the backward of the deferred lookup `rec` for a consumer that applies the SGD update of the once-touched
+        rows while it computes their gradient (tbe_dlrm_interaction_gather_backward_sgd_f32): counts the iteration, makes
+        the current stream wait for the side-stream sort and returns (flags, optimizer struct) — the struct, and with it
+        the learning rate, that backward_no_autograd(rec, grad, opened=...) then hands to the update kernel.  None (nothing
+        done) when the lookup has no flags: the caller takes the plain path."""
+        if rec.single is None or rec.prepared is None or not self._single_row_sgd_ok():
+            return None
         self.iter += 1
-        self._backward_impl(grad_out, rec.indices, rec.offsets, rec.per_sample_weights, rec.B, self._optimizer_struct(),
-                            prepared=rec.prepared, layout=rec.layout, ext=self._optimizer_ext())
+        self.single_row_sgd_steps += 1
+        torch.cuda.current_stream(self.current_device).wait_event(rec.prepared[1])
+        return rec.single, self._optimizer_struct()
+
+    def backward_no_autograd(self, rec: "LookupRecord", grad_out: torch.Tensor, opened=None) -> None:
+        """Coalesced gradient + fused optimizer update for the lookup `rec` describes (what _FusedLookup.backward does).
+        `opened`: what begin_single_row_sgd(rec) returned, after the caller applied the flagged rows."""
+        if opened is None:
+            self.iter += 1
+        opt = opened[1] if opened is not None else self._optimizer_struct()
+        self._backward_impl(grad_out, rec.indices, rec.offsets, rec.per_sample_weights, rec.B, opt,
+                            prepared=rec.prepared, layout=rec.layout, ext=self._optimizer_ext(),
+                            singles_applied=opened is not None)
         rec.prepared = None
+        rec.single = None
         if self._cache is not None:
             self._cache.after_backward()
 

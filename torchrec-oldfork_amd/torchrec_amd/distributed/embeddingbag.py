@@ -1267,10 +1267,23 @@ class DeferredLookup:
         self.module, self.rec, self.F, self.D, self.B = module, rec, F, D, rec.B
         self.feat_weights, self.feat_rows, self.feat_window = module.gather_layout()
 
-    def backward(self, grad_sparse: torch.Tensor) -> None:
-        """grad_sparse [B, F * D]: coalesced gradient + fused optimizer update of the tables."""
+    def begin_single_row_sgd(self):
+        """(flags, optimizer struct) when the module lets the consumer apply the exact-SGD update of the once-touched rows
+        itself (uint8 [F * B] flags, feature-major like the ids; the struct carries this backward's learning rate), with
+        the current stream already waiting for the sort that made the flags; else None.  What it returns goes back into
+        backward(grad_sparse, opened)."""
+        begin = getattr(self.module, "begin_single_row_sgd", None)
+        return begin(self.rec) if begin is not None else None
+
+    def backward(self, grad_sparse: torch.Tensor, opened=None) -> None:
+        """grad_sparse [B, F * D]: coalesced gradient + fused optimizer update of the tables.  With `opened`
+        (begin_single_row_sgd) the rows of the flagged contributions are already updated and their grad_sparse rows are
+        never read."""
         with label("## tbe_backward_fused_optimizer ##"):
-            self.module.backward_no_autograd(self.rec, grad_sparse)
+            if opened is not None:
+                self.module.backward_no_autograd(self.rec, grad_sparse, opened=opened)
+            else:
+                self.module.backward_no_autograd(self.rec, grad_sparse)
 
 
 class ExplicitLookupStep:

@@ -167,10 +167,13 @@ class _FusedGatherInteraction(torch.autograd.Function):
     """_FusedDotInteraction with the pooling-factor-1 lookup folded in (csrc/dlrm_interaction.hip gather kernels): the
     interaction reads the table rows itself, the pooled [B, F, D] buffer is neither written nor read.  `lookup` is the
     collection's DeferredLookup; backward hands the rows' gradient to its fused backward and returns d(dense).
-    `placeholder` (the embedding module's zero-size leaf) keeps this node in the graph when `dense` needs no gradient."""
+    `placeholder` (the embedding module's zero-size leaf) keeps this node in the graph when `dense` needs no gradient.
+    `single_row_sgd`: where the lookup's module allows it (exact SGD on fp32 tables, sort prepared: DeferredLookup
+    .begin_single_row_sgd) the backward kernel writes the updated row of every contribution that alone touches its row
+    straight into the table, and the fused backward leaves those contributions out."""
 
     @staticmethod
-    def forward(ctx, dense, placeholder, lookup, pad_rows=False):
+    def forward(ctx, dense, placeholder, lookup, pad_rows=False, single_row_sgd=False):
         dense = dense.contiguous()
         B, F, D = lookup.B, lookup.F, lookup.D
         if dense.shape != (B, D) or dense.dtype != torch.float32 or dense.device != lookup.module.current_device:
@@ -185,6 +188,7 @@ class _FusedGatherInteraction(torch.autograd.Function):
                 "tbe_dlrm_interaction_gather_forward_f32")
         ctx.save_for_backward(dense)
         ctx.lookup = lookup
+        ctx.single_row_sgd = single_row_sgd
         return buf if stride == width else buf[:, :width]
 
     @staticmethod
@@ -196,14 +200,23 @@ class _FusedGatherInteraction(torch.autograd.Function):
         gd = torch.empty_like(dense)
         gs = torch.empty((B, F * D), dtype=torch.float32, device=dense.device)
         with torch.cuda.device(dense.device):
+            # (flags, optimizer struct), the stream waiting for the sort behind the flags; None = the plain pair of calls
+            opened = lookup.begin_single_row_sgd() if ctx.single_row_sgd else None
             # the ids were counted by the forward: no counter here (include/tbe_hip.h)
-            check(_lib.load().tbe_dlrm_interaction_gather_backward_f32(
-                ptr(dense), ptr(lookup.feat_weights), ptr(lookup.feat_rows), ptr(lookup.feat_window),
-                ptr(lookup.rec.indices), ptr(grad_out), grad_out.stride(0), B, F, D, ptr(gd), ptr(gs), None,
-                stream_ptr(dense.device)),
-                "tbe_dlrm_interaction_gather_backward_f32")
-        lookup.backward(gs)
-        return gd, None, None, None
+            if opened is not None:
+                check(_lib.load().tbe_dlrm_interaction_gather_backward_sgd_f32(
+                    ptr(dense), ptr(lookup.feat_weights), ptr(lookup.feat_rows), ptr(lookup.feat_window),
+                    ptr(lookup.rec.indices), ptr(grad_out), grad_out.stride(0), B, F, D, ptr(gd), ptr(gs), None,
+                    ptr(opened[0]), opened[1].learning_rate, stream_ptr(dense.device)),
+                    "tbe_dlrm_interaction_gather_backward_sgd_f32")
+            else:
+                check(_lib.load().tbe_dlrm_interaction_gather_backward_f32(
+                    ptr(dense), ptr(lookup.feat_weights), ptr(lookup.feat_rows), ptr(lookup.feat_window),
+                    ptr(lookup.rec.indices), ptr(grad_out), grad_out.stride(0), B, F, D, ptr(gd), ptr(gs), None,
+                    stream_ptr(dense.device)),
+                    "tbe_dlrm_interaction_gather_backward_f32")
+        lookup.backward(gs, opened)
+        return gd, None, None, None, None
 
 
 def _fused_interaction_ok(dense: torch.Tensor, sparse: torch.Tensor) -> bool:
@@ -277,6 +290,9 @@ class DLRM(nn.Module):
         # DeferredLookup (one rank, no exchange: embeddingbag.py deferred_lookup_supported).  False = always materialise.
         self.fused_lookup = True
         self.fused_lookup_steps = 0  # forwards that took the gather path (tests)
+        # On the gather path with exact SGD the interaction backward also writes the updated row of every contribution
+        # that alone touches its row (_FusedGatherInteraction single_row_sgd).  False = the plain pair of calls (tests).
+        self.fused_single_row_update = True
 
     def _deferred_lookup(self, dense_features: torch.Tensor, sparse_features: KeyedJaggedTensor):
         """The collection's DeferredLookup for this batch, or None (nothing consumed) when the gather path cannot serve it."""
@@ -299,7 +315,7 @@ class DLRM(nn.Module):
         if lookup is not None:
             embedded_dense = self.dense_arch(dense_features)
             concatenated = _FusedGatherInteraction.apply(embedded_dense, lookup.module.placeholder_autograd_tensor, lookup,
-                                                         self.inter_arch.pad_rows)
+                                                         self.inter_arch.pad_rows, self.fused_single_row_update)
             self.fused_lookup_steps += 1
             return self.over_arch(concatenated)
         # The reference runs dense_arch, then sparse_arch (models/dlrm.py:400-401).  Here the lookup and
