@@ -787,6 +787,40 @@ int tbe_vector_cross_backward_f32(const float* grad_out, const float* x0, const 
                                   const float* bias, int64_t B, int32_t N, int32_t L, float* grad_in, float* grad_params,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* DeepFM interaction: the factorization-machine term and the deep branch's concatenated row in one pass each way.
+ * Replaces torchrec/modules/deepfm.py:28-32 (_get_flatten_input: torch.cat of all inputs, once per branch), :209-215
+ * (FactorizationMachine.forward: x * x, two row sums, a square) and what torchrec/models/deepfm.py:175-184 builds from
+ * them, with autograd's backward.
+ * The logical row x[b, 0:N] is a list of 1 .. TBE_FM_MAX_SEGMENTS column blocks, each with its own base and row stride (in
+ * elements); N = sum of the widths, segment k starts at column off_k = sum of the widths before it.  `segs` and `grads` are
+ * HOST arrays: they travel by value in the kernel arguments (no device table, no copy), so both calls can be captured into a
+ * HIP graph.  fp32 only.
+ *   forward : s = sum_c x[b, c], q = sum_c x[b, c]^2; fm[b * fm_stride] = (s * s - q) * 0.5; row_sum[b] = s;
+ *             cat[b, off_k + c] = x_k[b, c] when cat != NULL.  Every input element is read once.
+ *   backward: grads[k].g[b, c] = (grad_cat ? grad_cat[b, off_k + c] : 0) + grad_fm[b * grad_fm_stride] * (row_sum[b] - x_k[b, c])
+ *             for every segment whose g is not NULL; the others are neither read nor written.
+ * A segment moves as 16-byte vectors when its base, row stride, width and (with cat / grad_cat) column offset and N are
+ * multiples of 16 bytes / 4 elements (and, backward, its gradient's base and stride), else as 4-byte scalars; one launch
+ * may mix both, and the choice changes no result bit.  Sums run in an order that depends on (N, segment geometry) only; no
+ * float atomics; two runs are bit-identical.  No buffers may overlap.
+ * Errors, before anything is launched: TBE_ERR_INVALID_ARGUMENT for nseg outside 1 .. TBE_FM_MAX_SEGMENTS, a width < 1, a row
+ * stride smaller than the width, a null or 4-byte-misaligned pointer, fm_stride / grad_fm_stride < 1, or B beyond 2^31 - 1
+ * row blocks of 4 rows.  B == 0 launches nothing and returns TBE_OK. */
+#define TBE_FM_MAX_SEGMENTS 8
+typedef struct { const float* x; int64_t row_stride; int32_t width; } tbe_fm_segment;   /* elements */
+typedef struct { float* g;       int64_t row_stride; }                tbe_fm_grad_segment; /* g may be NULL: not wanted */
+/* torchrec/modules/deepfm.py:28-32, 209-215; torchrec/models/deepfm.py:175-184 */
+int tbe_fm_forward_f32(const tbe_fm_segment* segs, int32_t nseg, int64_t B,
+                       float* fm, int64_t fm_stride,   /* fm[b*fm_stride] = 0.5 * (s*s - q) */
+                       float* row_sum,                 /* [B]: s = sum_c x[b,c], kept for the backward */
+                       float* cat,                     /* NULL, or [B, N] contiguous: the concatenated row */
+                       void* stream);
+/* the backward autograd builds for torchrec/modules/deepfm.py:28-32, 209-215 */
+int tbe_fm_backward_f32(const tbe_fm_segment* segs, const tbe_fm_grad_segment* grads, int32_t nseg, int64_t B,
+                        const float* grad_fm, int64_t grad_fm_stride, const float* row_sum,
+                        const float* grad_cat,         /* NULL, or [B, N] contiguous: gradient of `cat` */
+                        void* stream);
+
 /* nn.BCEWithLogitsLoss (mean) forward + gradient in one launch — the loss of the reference's train wrapper
  * (examples/dlrm/modules/dlrm_train.py):  loss = mean_i [max(x_i, 0) - x_i y_i + log1p(exp(-|x_i|))],
  * dlogits_i = (sigmoid(x_i) - y_i) / B  (dlogits may be NULL).  labels: float32 (label_elem_size 4) or int64 (8).

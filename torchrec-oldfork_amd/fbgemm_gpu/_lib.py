@@ -47,6 +47,21 @@ class OptimizerExt(ctypes.Structure):
     ]
 
 
+class FmSegment(ctypes.Structure):
+    """Mirror of ``tbe_fm_segment`` (include/tbe_hip.h); strides and widths in elements."""
+
+    _fields_ = [("x", c_void_p), ("row_stride", c_i64), ("width", c_i32)]
+
+
+class FmGradSegment(ctypes.Structure):
+    """Mirror of ``tbe_fm_grad_segment`` (include/tbe_hip.h); g = None: this segment's gradient is not wanted."""
+
+    _fields_ = [("g", c_void_p), ("row_stride", c_i64)]
+
+
+FM_MAX_SEGMENTS = 8  # TBE_FM_MAX_SEGMENTS
+
+
 class CacheDesc(ctypes.Structure):
     """Mirror of ``tbe_cache_desc`` (include/tbe_hip.h)."""
 
@@ -195,6 +210,12 @@ SIGNATURES = {
     "tbe_vector_cross_backward_f32": (
         ctypes.c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_size,
+         c_void_p]),
+    "tbe_fm_forward_f32": (
+        ctypes.c_int, [ctypes.POINTER(FmSegment), c_i32, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
+    "tbe_fm_backward_f32": (
+        ctypes.c_int,
+        [ctypes.POINTER(FmSegment), ctypes.POINTER(FmGradSegment), c_i32, c_i64, c_void_p, c_i64, c_void_p, c_void_p,
          c_void_p]),
     "tbe_bce_with_logits_workspace_bytes": (c_size, []),
     "tbe_bce_with_logits_f32": (

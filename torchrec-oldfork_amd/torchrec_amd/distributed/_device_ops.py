@@ -27,6 +27,8 @@ _def.define("bce_with_logits(Tensor logits, Tensor labels) -> (Tensor, Tensor)")
 _def.define("cross_backward(Tensor grad_out, Tensor x0, Tensor t, Tensor(a!) acc, bool first) -> (Tensor, Tensor)")
 _def.define("vector_cross_forward(Tensor x0, Tensor weights, Tensor bias) -> (Tensor, Tensor)")
 _def.define("vector_cross_backward(Tensor grad_out, Tensor x0, Tensor s, Tensor weights, Tensor bias) -> (Tensor, Tensor)")
+_def.define("fm_forward(Tensor[] xs, bool want_cat) -> (Tensor, Tensor, Tensor)")
+_def.define("fm_backward(Tensor[] xs, Tensor grad_fm, Tensor row_sum, Tensor? grad_cat, bool[] wanted) -> Tensor[]")
 _impl = torch.library.Library("tbe_hip", "IMPL", "CUDA")
 
 
@@ -176,6 +178,105 @@ def _vector_cross_backward(grad_out, x0, s, weights, bias):
     return gin, gp
 
 
+def fm_segments(xs, wanted=None):
+    """The segment list of csrc/deepfm.hip for the column blocks `xs` (each float32 [B, w], inner stride 1): list
+    neighbours that are adjacent column slices of one buffer (same row stride, the next one's address = the previous one's
+    + its width — the per-feature views of a KeyedTensor) and, with `wanted`, share their flag are merged into one segment.
+    Returns [(first index, count, address, row stride, width)]."""
+    groups = []
+    for i, x in enumerate(xs):
+        w = x.shape[1]
+        stride = x.stride(0) if x.shape[0] > 1 else max(x.stride(0), w)
+        if groups:
+            j, n, addr, st, gw = groups[-1]
+            if st == stride and addr + 4 * gw == x.data_ptr() and gw + w <= st and (wanted is None or wanted[j] == wanted[i]):
+                groups[-1] = (j, n + 1, addr, st, gw + w)
+                continue
+        groups.append((i, 1, x.data_ptr(), stride, w))
+    return groups
+
+
+def _fm_check(name, xs):
+    if len(xs) == 0:
+        raise RuntimeError(f"{name}: empty input list")
+    dev = require_gpu(*xs)
+    B = xs[0].shape[0]
+    for i, x in enumerate(xs):
+        if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] != B or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1):
+            raise RuntimeError(f"{name}: xs[{i}] must be float32 [B={B}, w >= 1] with a contiguous inner dimension, got "
+                               f"{x.dtype} {tuple(x.shape)} strides {tuple(x.stride())}")
+        if B > 1 and x.stride(0) < x.shape[1]:
+            raise RuntimeError(f"{name}: xs[{i}] has overlapping rows (strides {tuple(x.stride())})")
+    return dev, B
+
+
+def _fm_seg_array(name, groups):
+    if len(groups) > _lib.FM_MAX_SEGMENTS:
+        raise RuntimeError(f"{name}: {len(groups)} segments are left after merging neighbours, more than "
+                           f"{_lib.FM_MAX_SEGMENTS}; concatenate the inputs first (FactorizationMachine does)")
+    segs = (_lib.FmSegment * len(groups))()
+    for k, (_, _, addr, stride, w) in enumerate(groups):
+        segs[k].x, segs[k].row_stride, segs[k].width = addr, stride, w
+    return segs
+
+
+def _fm_forward(xs, want_cat):
+    """(fm [B, 1], row_sum [B], cat [B, N] or an empty tensor) of the column blocks `xs` in one pass (csrc/deepfm.hip)."""
+    dev, B = _fm_check("fm_forward", xs)
+    groups = fm_segments(xs)
+    segs = _fm_seg_array("fm_forward", groups)
+    N = sum(g[4] for g in groups)
+    fm = torch.empty((B, 1), dtype=torch.float32, device=dev)
+    row_sum = torch.empty(B, dtype=torch.float32, device=dev)
+    cat = torch.empty((B, N) if want_cat else (0,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_fm_forward_f32(segs, len(groups), B, ptr(fm), 1, ptr(row_sum), ptr(cat) if want_cat else None,
+                                             stream_ptr(dev)), "tbe_fm_forward_f32")
+    return fm, row_sum, cat
+
+
+def _fm_backward(xs, grad_fm, row_sum, grad_cat, wanted):
+    """One gradient per entry of `xs` (an empty tensor where `wanted` is False) in one pass (csrc/deepfm.hip):
+    grad_cat[:, its columns] + grad_fm * (row_sum - x).  grad_fm may be a strided [B, 1] view."""
+    dev, B = _fm_check("fm_backward", xs)
+    require_gpu(grad_fm, row_sum, grad_cat)
+    wanted = [bool(w) for w in wanted]
+    if len(wanted) != len(xs):
+        raise RuntimeError(f"fm_backward: {len(wanted)} flags for {len(xs)} inputs")
+    groups = fm_segments(xs, wanted)
+    segs = _fm_seg_array("fm_backward", groups)
+    N = sum(g[4] for g in groups)
+    if grad_fm.dtype != torch.float32 or grad_fm.numel() != B or grad_fm.dim() not in (1, 2):
+        raise RuntimeError(f"fm_backward: grad_fm must be float32 [B] or [B, 1] with B = {B}, got {grad_fm.dtype} "
+                           f"{tuple(grad_fm.shape)}")
+    if B > 1 and grad_fm.stride(0) < 1:  # an expanded scalar (out.sum().backward())
+        grad_fm = grad_fm.contiguous()
+    if row_sum.dtype != torch.float32 or row_sum.shape != (B,) or not row_sum.is_contiguous():
+        raise RuntimeError(f"fm_backward: row_sum must be a contiguous float32 [{B}], got {row_sum.dtype} {tuple(row_sum.shape)}")
+    if grad_cat is not None:
+        if grad_cat.dtype != torch.float32 or grad_cat.shape != (B, N):
+            raise RuntimeError(f"fm_backward: grad_cat must be float32 [{B}, {N}], got {grad_cat.dtype} {tuple(grad_cat.shape)}")
+        grad_cat = grad_cat.contiguous()
+    gsegs = (_lib.FmGradSegment * len(groups))()
+    out = [None] * len(xs)
+    for k, (first, count, _, _, w) in enumerate(groups):
+        if wanted[first]:
+            g = torch.empty((B, w), dtype=torch.float32, device=dev)
+            gsegs[k].g, gsegs[k].row_stride = g.data_ptr(), w
+            col = 0
+            for i in range(first, first + count):
+                out[i] = g if count == 1 else g[:, col:col + xs[i].shape[1]]
+                col += xs[i].shape[1]
+        else:
+            gsegs[k].g, gsegs[k].row_stride = None, 0
+            for i in range(first, first + count):
+                out[i] = torch.empty(0, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_fm_backward_f32(segs, gsegs, len(groups), B, ptr(grad_fm), grad_fm.stride(0) if B > 1 else 1,
+                                              ptr(row_sum), ptr(grad_cat), stream_ptr(dev)), "tbe_fm_backward_f32")
+    return out
+
+
 def _multi_chunk_sum(seg_table, nseg, max_numel, dst, scale):
     """dst[off_s + i] = scale * sum_c src_s[c, i] for every segment of `seg_table` (device int64 [nseg, 4]: src address,
     chunks, numel, dst element offset) in one launch; the caller keeps the sources alive."""
@@ -298,6 +399,8 @@ _impl.impl("weighted_colsum_partials", _weighted_colsum_partials)
 _impl.impl("cross_backward", _cross_backward)
 _impl.impl("vector_cross_forward", _vector_cross_forward)
 _impl.impl("vector_cross_backward", _vector_cross_backward)
+_impl.impl("fm_forward", _fm_forward)
+_impl.impl("fm_backward", _fm_backward)
 _impl.impl("multi_chunk_sum", _multi_chunk_sum)
 _impl.impl("bce_with_logits", _bce_with_logits)
 _impl.impl("pooled_exchange_unpack", _unpack)
