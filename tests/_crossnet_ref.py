@@ -16,6 +16,8 @@ import os
 
 import numpy as np
 
+from _colsum_order import rows_per_block  # rows per workgroup of cross_bwd_kernel (csrc/colsum.hpp)
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crossnet.npz")
 KINDS = ("CrossNet", "LowRankCrossNet", "VectorCrossNet")
 CASES = {"3x10": (3, 10, 2, 3), "37x20": (37, 20, 3, 5), "70x64": (70, 64, 2, 1)}  # (B, N, L, r)
@@ -24,11 +26,6 @@ VECTOR_ROWS_PER_BLOCK = 128  # csrc/crossnet.hip kVecRowsPerBlock
 # the GPU tests' shapes (the issue's): vector kernels (B, N, L); modules (B, N, L, r)
 VECTOR_GPU_SHAPES = [(1, 4, 1), (5, 12, 3), (67, 64, 2), (130, 260, 3), (64, 1028, 4), (3, 4096, 8)]
 TRAIN_SHAPE = (130, 260, 3, 16)
-
-
-def cross_rows_per_block(N):
-    """csrc/crossnet.hip cross_rows_per_block (= mlp_epilogue.hip's rule)."""
-    return 256 if N >= 512 else 64
 
 
 def param_names(kind, L):
@@ -114,7 +111,7 @@ def run(kind, params, x, g, dtype="float64", fault=None):
             x_l = x0 * t + x_l
         xs.append(x_l)
     res["out"] = xs[L]
-    rpb = VECTOR_ROWS_PER_BLOCK if kind == "VectorCrossNet" else cross_rows_per_block(N)
+    rpb = VECTOR_ROWS_PER_BLOCK if kind == "VectorCrossNet" else rows_per_block(N)
     G = g
     acc = np.zeros_like(x0)
     for l in reversed(range(L)):

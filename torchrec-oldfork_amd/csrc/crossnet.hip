@@ -10,7 +10,7 @@
 // Their BACKWARD through autograd is, per layer, a chain of HBM-bound kernels over [B, N]: mul (G * x_0), mul (G * t),
 // AccumulateGrad add into x_0's gradient, a column sum for the bias.  cross_bwd_kernel does all of it in one pass: it
 // reads G, x_0, t (and acc, unless `first`), writes g_y = G * x_0 and acc (+)= G * t and leaves the column sums of g_y per
-// row block, which a fixed-order second stage adds (deterministic, no float atomics) — the scheme of mlp_epilogue.hip.
+// row block, which a fixed-order second stage adds (deterministic, no float atomics) — the scheme of colsum.hpp.
 //
 // VectorCrossNet is element-wise work plus row dots only:  s_l[b] = x_l[b, :] . w_l,  x_{l+1} = x_0 * s_l + b_l + x_l.
 // One forward kernel runs all L layers with the row in registers; one backward kernel recomputes every x_l from x_0, s and
@@ -21,84 +21,33 @@
 // restatement in numpy reproduces the element-wise results bit for bit.
 #include <algorithm>
 
-#include "common.hpp"
+#include "colsum.hpp"
 
 namespace tbe {
 
-// rows of [B, N] per workgroup of cross_bwd_kernel: the rule of mlp_epilogue.hip (tbe_colsum_row_blocks)
-__host__ __device__ inline int cross_rows_per_block(int N) { return N >= 512 ? 256 : 64; }
-
-// block = 256 threads = TY rows x TX float4-columns; grid = (column tiles, row blocks)
+// block = 256 threads = TY rows x TX float4-columns; grid = (column tiles, row blocks): colsum.hpp
 template <int TX>
 __global__ __launch_bounds__(256) void cross_bwd_kernel(const float* __restrict__ G, const float* __restrict__ x0,
                                                         const float* __restrict__ t, float* __restrict__ gy,
                                                         float* __restrict__ acc, float* __restrict__ partial, int64_t B,
                                                         int N, int first) {
-  constexpr int TY = 256 / TX;
-  __shared__ float4 red[TY][TX];
-  const int tx = threadIdx.x % TX;
-  const int ty = threadIdx.x / TX;
-  const int col = (blockIdx.x * TX + tx) * 4;
-  const int rpb = cross_rows_per_block(N);
-  const int64_t row0 = static_cast<int64_t>(blockIdx.y) * rpb;
-  const int64_t row1 = min(B, row0 + rpb);
-  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (col < N) {
-#pragma unroll 4
-    for (int64_t r = row0 + ty; r < row1; r += TY) {
-      const int64_t o = r * N + col;
-      const float4 g = ld4(G + o);
-      const float4 x = ld4(x0 + o);
-      const float4 tt = ld4(t + o);
-      const float4 y = make_float4(g.x * x.x, g.y * x.y, g.z * x.z, g.w * x.w);
-      float4 a = make_float4(g.x * tt.x, g.y * tt.y, g.z * tt.z, g.w * tt.w);
-      if (!first) {
-        const float4 p = ld4(acc + o);
-        a.x = p.x + a.x;
-        a.y = p.y + a.y;
-        a.z = p.z + a.z;
-        a.w = p.w + a.w;
-      }
-      st4(gy + o, y);
-      st4(acc + o, a);
-      sum.x += y.x;
-      sum.y += y.y;
-      sum.z += y.z;
-      sum.w += y.w;
+  colsum_row_block<TX>(partial, B, N, [=](int64_t, int64_t o, float4& sum) {
+    const float4 g = ld4(G + o);
+    const float4 x = ld4(x0 + o);
+    const float4 tt = ld4(t + o);
+    const float4 y = make_float4(g.x * x.x, g.y * x.y, g.z * x.z, g.w * x.w);
+    float4 a = make_float4(g.x * tt.x, g.y * tt.y, g.z * tt.z, g.w * tt.w);
+    if (!first) {
+      const float4 p = ld4(acc + o);
+      a.x = p.x + a.x;
+      a.y = p.y + a.y;
+      a.z = p.z + a.z;
+      a.w = p.w + a.w;
     }
-  }
-  red[ty][tx] = sum;
-  __syncthreads();
-  if (ty == 0 && col < N) {
-    float4 s = red[0][tx];
-#pragma unroll
-    for (int y = 1; y < TY; ++y) {
-      const float4 o = red[y][tx];
-      s.x += o.x;
-      s.y += o.y;
-      s.z += o.z;
-      s.w += o.w;
-    }
-    st4(partial + static_cast<int64_t>(blockIdx.y) * N + col, s);
-  }
-}
-
-// out[c] = sum over row blocks of partial[rb][c], fixed order: wave w takes blocks w, w+4, ... — the twin of
-// mlp_epilogue.hip's colsum_partials_kernel (a kernel of another translation unit cannot be launched from here)
-__global__ __launch_bounds__(256) void cross_colsum_partials_kernel(const float* __restrict__ partial, int64_t nblocks, int N,
-                                                                    float* __restrict__ out) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  float acc = 0.f;
-  if (c < N) {
-#pragma unroll 8
-    for (int64_t rb = wave; rb < nblocks; rb += 4) acc += partial[rb * N + c];
-  }
-  red[wave][lane] = acc;
-  __syncthreads();
-  if (wave == 0 && c < N) out[c] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    st4(gy + o, y);
+    st4(acc + o, a);
+    add4(sum, y);
+  });
 }
 
 // ---- VectorCrossNet ---------------------------------------------------------------------------------------------------
@@ -180,13 +129,6 @@ __global__ __launch_bounds__(256) void vector_cross_fwd_kernel(const float* __re
       if (col < N) st4(out + r * N + col, x[k]);
     }
   }
-}
-
-__device__ __forceinline__ void add4(float4& a, const float4 b) {
-  a.x += b.x;
-  a.y += b.y;
-  a.z += b.z;
-  a.w += b.w;
 }
 
 // L is a template parameter, so that the 2 * L * kVecK float4 column sums of a thread stay in registers.
@@ -303,48 +245,23 @@ static int64_t vec_row_blocks(int64_t B) { return (B + kVecRowsPerBlock - 1) / k
 
 using namespace tbe;
 
-extern "C" size_t tbe_cross_backward_workspace_bytes(int64_t B, int32_t N) {
-  if (B <= 0 || N <= 0) return 256;
-  const int rpb = cross_rows_per_block(N);
-  return align_up(static_cast<size_t>((B + rpb - 1) / rpb) * N * sizeof(float), 256);
-}
+extern "C" size_t tbe_cross_backward_workspace_bytes(int64_t B, int32_t N) { return colsum_workspace_bytes(B, N); }
 
 extern "C" int tbe_cross_backward_f32(const float* grad_out, const float* x0, const float* t, int64_t B, int32_t N,
                                       int32_t first, float* grad_y, float* acc, float* bias_grad, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-  TBE_REQUIRE(B >= 0 && N > 0 && (N & 3) == 0, "tbe_cross_backward_f32: N=%d must be a positive multiple of 4", N);
-  TBE_REQUIRE(bias_grad != nullptr, "tbe_cross_backward_f32: null bias_grad");
+  const char* name = "tbe_cross_backward_f32";
+  TBE_REQUIRE(bias_grad != nullptr, "%s: null bias_grad", name);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (B == 0) {
-    if (hipMemsetAsync(bias_grad, 0, sizeof(float) * N, st) != hipSuccess) return TBE_ERR_LAUNCH;
-    return TBE_OK;
-  }
-  TBE_REQUIRE(grad_out && x0 && t && grad_y && acc && workspace, "tbe_cross_backward_f32: null pointer");
-  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(t) |
-                reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(acc) |
-                reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
-              "tbe_cross_backward_f32: tensors must be 16-B aligned");
-  TBE_REQUIRE(workspace_bytes >= tbe_cross_backward_workspace_bytes(B, N), "tbe_cross_backward_f32: workspace too small");
-  const int rpb = cross_rows_per_block(N);
-  const int64_t nrb = (B + rpb - 1) / rpb;
-  TBE_REQUIRE(nrb <= 65535, "tbe_cross_backward_f32: B=%lld too large (more than 65535 row blocks)", (long long)B);
   float* partial = static_cast<float*>(workspace);
-  const int vecs = N / 4;
   const int f = first != 0;
-  if (vecs >= 64) {
-    hipLaunchKernelGGL(cross_bwd_kernel<64>, dim3((vecs + 63) / 64, static_cast<unsigned>(nrb)), dim3(256), 0, st, grad_out, x0,
-                       t, grad_y, acc, partial, B, N, f);
-  } else if (vecs >= 32) {
-    hipLaunchKernelGGL(cross_bwd_kernel<32>, dim3((vecs + 31) / 32, static_cast<unsigned>(nrb)), dim3(256), 0, st, grad_out, x0,
-                       t, grad_y, acc, partial, B, N, f);
-  } else {
-    hipLaunchKernelGGL(cross_bwd_kernel<16>, dim3((vecs + 15) / 16, static_cast<unsigned>(nrb)), dim3(256), 0, st, grad_out, x0,
-                       t, grad_y, acc, partial, B, N, f);
-  }
-  TBE_CHECK_LAUNCH("tbe_cross_backward_f32");
-  hipLaunchKernelGGL(cross_colsum_partials_kernel, dim3((N + 63) / 64), dim3(256), 0, st, partial, nrb, N, bias_grad);
-  TBE_CHECK_LAUNCH("tbe_cross_backward_f32 colsum");
-  return TBE_OK;
+  int64_t nrb;
+  const int rc = colsum_first_stage(name, true, B, N, {grad_out, x0, t, grad_y, acc}, partial, workspace_bytes, &nrb,
+                                    [&](auto tx, dim3 grid) {
+                                      hipLaunchKernelGGL(cross_bwd_kernel<decltype(tx)::value>, grid, dim3(256), 0, st, grad_out,
+                                                         x0, t, grad_y, acc, partial, B, N, f);
+                                    });
+  return rc != TBE_OK ? rc : launch_colsum_partials(name, partial, nrb, N, bias_grad, st);
 }
 
 #define TBE_VEC_CROSS_LIMITS(what)                                                                                      \
@@ -421,8 +338,5 @@ extern "C" int tbe_vector_cross_backward_f32(const float* grad_out, const float*
   }
 #undef TBE_VEC_BWD
   TBE_CHECK_LAUNCH("tbe_vector_cross_backward_f32");
-  const int cols = 2 * L * N;
-  hipLaunchKernelGGL(cross_colsum_partials_kernel, dim3((cols + 63) / 64), dim3(256), 0, st, partial, nrb, cols, grad_params);
-  TBE_CHECK_LAUNCH("tbe_vector_cross_backward_f32 colsum");
-  return TBE_OK;
+  return launch_colsum_partials("tbe_vector_cross_backward_f32", partial, nrb, 2 * L * N, grad_params, st);
 }

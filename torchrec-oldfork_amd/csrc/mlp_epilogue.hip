@@ -10,58 +10,25 @@
 #include <algorithm>
 #include <cstring>
 
-#include "common.hpp"
+#include "colsum.hpp"
 
 namespace tbe {
 
-// rows of [B, N] handled by one workgroup of the first stage; the second stage sums B / rows partial rows.
-// Wide layers have enough column tiles to fill the chip with 256-row blocks (4x fewer partials to sum).
-__host__ __device__ inline int rows_per_block(int N) { return N >= 512 ? 256 : 64; }
-
-// block = 256 threads = TY rows x TX float4-columns; grid = (column tiles, row blocks)
+// block = 256 threads = TY rows x TX float4-columns; grid = (column tiles, row blocks): colsum.hpp
 template <int TX>
 __global__ __launch_bounds__(256) void drelu_bgrad_kernel(const float* __restrict__ gy, const float* __restrict__ act,
                                                           float* __restrict__ gx, float* __restrict__ partial,
                                                           int64_t B, int N) {
-  constexpr int TY = 256 / TX;
-  __shared__ float4 red[TY][TX];
-  const int tx = threadIdx.x % TX;
-  const int ty = threadIdx.x / TX;
-  const int col = (blockIdx.x * TX + tx) * 4;
-  const int rpb = rows_per_block(N);
-  const int64_t row0 = static_cast<int64_t>(blockIdx.y) * rpb;
-  const int64_t row1 = min(B, row0 + rpb);
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (col < N) {
-#pragma unroll 4
-    for (int64_t r = row0 + ty; r < row1; r += TY) {
-      float4 g = ld4(gy + r * N + col);
-      const float4 a = ld4(act + r * N + col);
-      g.x = a.x > 0.f ? g.x : 0.f;
-      g.y = a.y > 0.f ? g.y : 0.f;
-      g.z = a.z > 0.f ? g.z : 0.f;
-      g.w = a.w > 0.f ? g.w : 0.f;
-      st4(gx + r * N + col, g);
-      acc.x += g.x;
-      acc.y += g.y;
-      acc.z += g.z;
-      acc.w += g.w;
-    }
-  }
-  red[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0 && col < N) {
-    float4 s = red[0][tx];
-#pragma unroll
-    for (int y = 1; y < TY; ++y) {
-      const float4 o = red[y][tx];
-      s.x += o.x;
-      s.y += o.y;
-      s.z += o.z;
-      s.w += o.w;
-    }
-    st4(partial + static_cast<int64_t>(blockIdx.y) * N + col, s);
-  }
+  colsum_row_block<TX>(partial, B, N, [=](int64_t, int64_t o, float4& sum) {
+    float4 g = ld4(gy + o);
+    const float4 a = ld4(act + o);
+    g.x = a.x > 0.f ? g.x : 0.f;
+    g.y = a.y > 0.f ? g.y : 0.f;
+    g.z = a.z > 0.f ? g.z : 0.f;
+    g.w = a.w > 0.f ? g.w : 0.f;
+    st4(gx + o, g);
+    add4(sum, g);
+  });
 }
 
 // partial[rb][c] = sum over the block's rows of w[b] * x[b, c]  (weight gradient of a Linear with ONE output:
@@ -69,40 +36,14 @@ __global__ __launch_bounds__(256) void drelu_bgrad_kernel(const float* __restric
 template <int TX>
 __global__ __launch_bounds__(256) void wcolsum_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                       float* __restrict__ partial, int64_t B, int N) {
-  constexpr int TY = 256 / TX;
-  __shared__ float4 red[TY][TX];
-  const int tx = threadIdx.x % TX;
-  const int ty = threadIdx.x / TX;
-  const int col = (blockIdx.x * TX + tx) * 4;
-  const int rpb = rows_per_block(N);
-  const int64_t row0 = static_cast<int64_t>(blockIdx.y) * rpb;
-  const int64_t row1 = min(B, row0 + rpb);
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (col < N) {
-#pragma unroll 4
-    for (int64_t r = row0 + ty; r < row1; r += TY) {
-      const float4 v = ld4(x + r * N + col);
-      const float s = w[r];
-      acc.x = fmaf(s, v.x, acc.x);
-      acc.y = fmaf(s, v.y, acc.y);
-      acc.z = fmaf(s, v.z, acc.z);
-      acc.w = fmaf(s, v.w, acc.w);
-    }
-  }
-  red[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0 && col < N) {
-    float4 s = red[0][tx];
-#pragma unroll
-    for (int y = 1; y < TY; ++y) {
-      const float4 o = red[y][tx];
-      s.x += o.x;
-      s.y += o.y;
-      s.z += o.z;
-      s.w += o.w;
-    }
-    st4(partial + static_cast<int64_t>(blockIdx.y) * N + col, s);
-  }
+  colsum_row_block<TX>(partial, B, N, [=](int64_t r, int64_t o, float4& sum) {
+    const float4 v = ld4(x + o);
+    const float s = w[r];
+    sum.x = fmaf(s, v.x, sum.x);
+    sum.y = fmaf(s, v.y, sum.y);
+    sum.z = fmaf(s, v.z, sum.z);
+    sum.w = fmaf(s, v.w, sum.w);
+  });
 }
 
 // bias_grad[c] = sum over row blocks of partial[rb][c], fixed order: wave w takes blocks w, w+4, ...
@@ -304,136 +245,68 @@ __global__ __launch_bounds__(256) void bce_with_logits_kernel(const float* __res
 
 using namespace tbe;
 
-extern "C" size_t tbe_relu_backward_bias_grad_workspace_bytes(int64_t B, int32_t N) {
-  if (B <= 0 || N <= 0) return 256;
-  const int rpb = rows_per_block(N);
-  return align_up(static_cast<size_t>((B + rpb - 1) / rpb) * N * sizeof(float), 256);
+int tbe::launch_colsum_partials(const char* name, const float* partial, int64_t row_blocks, int N, float* out, hipStream_t st) {
+  if (row_blocks == 0) return hipMemsetAsync(out, 0, sizeof(float) * N, st) == hipSuccess ? TBE_OK : TBE_ERR_LAUNCH;
+  hipLaunchKernelGGL(colsum_partials_kernel, dim3((N + 63) / 64), dim3(256), 0, st, partial, row_blocks, N, out);
+  TBE_CHECK_LAUNCH((std::string(name) + " colsum").c_str());
+  return TBE_OK;
 }
+
+// ---- first stages: alone (`_partials`: the column sums of the row blocks are left in `partial` [row blocks][N] for a later
+//      tbe_multi_chunk_sum_f32, one launch for every layer of a captured backward) or followed by the second stage ----------
+static int relu_backward_first_stage(const char* name, bool one_pass, const float* grad_out, const float* act, int64_t B, int32_t N,
+                                     float* grad_in, void* partial, size_t partial_bytes, hipStream_t st, int64_t* nrb) {
+  return colsum_first_stage(name, one_pass, B, N, {grad_out, act, grad_in}, partial, partial_bytes, nrb, [&](auto tx, dim3 grid) {
+    hipLaunchKernelGGL(drelu_bgrad_kernel<decltype(tx)::value>, grid, dim3(256), 0, st, grad_out, act, grad_in,
+                       static_cast<float*>(partial), B, N);
+  });
+}
+
+static int weighted_colsum_first_stage(const char* name, bool one_pass, const float* x, const float* w, int64_t B, int32_t N,
+                                       void* partial, size_t partial_bytes, hipStream_t st, int64_t* nrb) {
+  TBE_REQUIRE(w != nullptr || B == 0, "%s: null pointer", name);
+  return colsum_first_stage(name, one_pass, B, N, {x}, partial, partial_bytes, nrb, [&](auto tx, dim3 grid) {
+    hipLaunchKernelGGL(wcolsum_kernel<decltype(tx)::value>, grid, dim3(256), 0, st, x, w, static_cast<float*>(partial), B, N);
+  });
+}
+
+extern "C" int64_t tbe_colsum_row_blocks(int64_t B, int32_t N) { return B <= 0 || N <= 0 ? 0 : colsum_row_blocks(B, N); }
+extern "C" size_t tbe_relu_backward_bias_grad_workspace_bytes(int64_t B, int32_t N) { return colsum_workspace_bytes(B, N); }
+extern "C" size_t tbe_weighted_colsum_workspace_bytes(int64_t B, int32_t N) { return colsum_workspace_bytes(B, N); }
 
 extern "C" int tbe_relu_backward_bias_grad_f32(const float* grad_out, const float* act, int64_t B, int32_t N,
                                                float* grad_in, float* bias_grad, void* workspace,
                                                size_t workspace_bytes, void* stream) {
-  TBE_REQUIRE(B >= 0 && N > 0 && (N & 3) == 0, "tbe_relu_backward_bias_grad_f32: N=%d must be a positive multiple of 4", N);
-  TBE_REQUIRE(bias_grad != nullptr, "tbe_relu_backward_bias_grad_f32: null bias_grad");
+  const char* name = "tbe_relu_backward_bias_grad_f32";
+  TBE_REQUIRE(bias_grad != nullptr, "%s: null bias_grad", name);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (B == 0) {
-    if (hipMemsetAsync(bias_grad, 0, sizeof(float) * N, st) != hipSuccess) return TBE_ERR_LAUNCH;
-    return TBE_OK;
-  }
-  TBE_REQUIRE(grad_out && act && grad_in && workspace, "tbe_relu_backward_bias_grad_f32: null pointer");
-  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(act) |
-                reinterpret_cast<uintptr_t>(grad_in) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
-              "tbe_relu_backward_bias_grad_f32: tensors must be 16-B aligned");
-  TBE_REQUIRE(workspace_bytes >= tbe_relu_backward_bias_grad_workspace_bytes(B, N),
-              "tbe_relu_backward_bias_grad_f32: workspace too small");
-  const int rpb = rows_per_block(N);
-  const int64_t nrb = (B + rpb - 1) / rpb;
-  TBE_REQUIRE(nrb <= 65535, "tbe_relu_backward_bias_grad_f32: B=%lld too large", (long long)B);
-  float* partial = static_cast<float*>(workspace);
-  const int vecs = N / 4;
-  if (vecs >= 64) {
-    const dim3 grid((vecs + 63) / 64, static_cast<unsigned>(nrb));
-    hipLaunchKernelGGL(drelu_bgrad_kernel<64>, grid, dim3(256), 0, st, grad_out, act, grad_in, partial, B, N);
-  } else if (vecs >= 32) {
-    const dim3 grid((vecs + 31) / 32, static_cast<unsigned>(nrb));
-    hipLaunchKernelGGL(drelu_bgrad_kernel<32>, grid, dim3(256), 0, st, grad_out, act, grad_in, partial, B, N);
-  } else {
-    const dim3 grid((vecs + 15) / 16, static_cast<unsigned>(nrb));
-    hipLaunchKernelGGL(drelu_bgrad_kernel<16>, grid, dim3(256), 0, st, grad_out, act, grad_in, partial, B, N);
-  }
-  TBE_CHECK_LAUNCH("tbe_relu_backward_bias_grad_f32");
-  hipLaunchKernelGGL(colsum_partials_kernel, dim3((N + 63) / 64), dim3(256), 0, st, partial, nrb, N, bias_grad);
-  TBE_CHECK_LAUNCH("tbe_relu_backward_bias_grad_f32 colsum");
-  return TBE_OK;
-}
-
-extern "C" size_t tbe_weighted_colsum_workspace_bytes(int64_t B, int32_t N) {
-  return tbe_relu_backward_bias_grad_workspace_bytes(B, N);
-}
-
-extern "C" int tbe_weighted_colsum_f32(const float* x, const float* w, int64_t B, int32_t N, float* out,
-                                       void* workspace, size_t workspace_bytes, void* stream) {
-  TBE_REQUIRE(B >= 0 && N > 0 && (N & 3) == 0, "tbe_weighted_colsum_f32: N=%d must be a positive multiple of 4", N);
-  TBE_REQUIRE(out != nullptr, "tbe_weighted_colsum_f32: null out");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (B == 0) {
-    if (hipMemsetAsync(out, 0, sizeof(float) * N, st) != hipSuccess) return TBE_ERR_LAUNCH;
-    return TBE_OK;
-  }
-  TBE_REQUIRE(x && w && workspace, "tbe_weighted_colsum_f32: null pointer");
-  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
-              "tbe_weighted_colsum_f32: tensors must be 16-B aligned");
-  TBE_REQUIRE(workspace_bytes >= tbe_weighted_colsum_workspace_bytes(B, N), "tbe_weighted_colsum_f32: workspace too small");
-  const int rpb = rows_per_block(N);
-  const int64_t nrb = (B + rpb - 1) / rpb;
-  TBE_REQUIRE(nrb <= 65535, "tbe_weighted_colsum_f32: B=%lld too large", (long long)B);
-  float* partial = static_cast<float*>(workspace);
-  const int vecs = N / 4;
-  if (vecs >= 64) {
-    hipLaunchKernelGGL(wcolsum_kernel<64>, dim3((vecs + 63) / 64, static_cast<unsigned>(nrb)), dim3(256), 0, st, x, w, partial, B, N);
-  } else if (vecs >= 32) {
-    hipLaunchKernelGGL(wcolsum_kernel<32>, dim3((vecs + 31) / 32, static_cast<unsigned>(nrb)), dim3(256), 0, st, x, w, partial, B, N);
-  } else {
-    hipLaunchKernelGGL(wcolsum_kernel<16>, dim3((vecs + 15) / 16, static_cast<unsigned>(nrb)), dim3(256), 0, st, x, w, partial, B, N);
-  }
-  TBE_CHECK_LAUNCH("tbe_weighted_colsum_f32");
-  hipLaunchKernelGGL(colsum_partials_kernel, dim3((N + 63) / 64), dim3(256), 0, st, partial, nrb, N, out);
-  TBE_CHECK_LAUNCH("tbe_weighted_colsum_f32 colsum");
-  return TBE_OK;
-}
-
-
-// ---- first stages alone: the column sums of the row blocks are left in `partial` [row blocks][N] for a later
-//      tbe_multi_chunk_sum_f32 (one launch for every layer of a captured backward) --------------------------------------
-extern "C" int64_t tbe_colsum_row_blocks(int64_t B, int32_t N) {
-  if (B <= 0 || N <= 0) return 0;
-  const int rpb = rows_per_block(N);
-  return (B + rpb - 1) / rpb;
+  int64_t nrb;
+  const int rc = relu_backward_first_stage(name, true, grad_out, act, B, N, grad_in, workspace, workspace_bytes, st, &nrb);
+  return rc != TBE_OK ? rc : launch_colsum_partials(name, static_cast<const float*>(workspace), nrb, N, bias_grad, st);
 }
 
 extern "C" int tbe_relu_backward_bias_partials_f32(const float* grad_out, const float* act, int64_t B, int32_t N,
                                                    float* grad_in, float* partial, size_t partial_bytes, void* stream) {
-  TBE_REQUIRE(B > 0 && N > 0 && (N & 3) == 0, "tbe_relu_backward_bias_partials_f32: B > 0 and N a positive multiple of 4 required");
-  TBE_REQUIRE(grad_out && act && grad_in && partial, "tbe_relu_backward_bias_partials_f32: null pointer");
-  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(act) |
-                reinterpret_cast<uintptr_t>(grad_in) | reinterpret_cast<uintptr_t>(partial)) & 15) == 0,
-              "tbe_relu_backward_bias_partials_f32: tensors must be 16-B aligned");
-  const int64_t nrb = tbe_colsum_row_blocks(B, N);
-  TBE_REQUIRE(nrb <= 65535, "tbe_relu_backward_bias_partials_f32: B=%lld too large", (long long)B);
-  TBE_REQUIRE(partial_bytes >= static_cast<size_t>(nrb) * N * sizeof(float), "tbe_relu_backward_bias_partials_f32: partial too small");
+  int64_t nrb;
+  return relu_backward_first_stage("tbe_relu_backward_bias_partials_f32", false, grad_out, act, B, N, grad_in, partial,
+                                   partial_bytes, static_cast<hipStream_t>(stream), &nrb);
+}
+
+extern "C" int tbe_weighted_colsum_f32(const float* x, const float* w, int64_t B, int32_t N, float* out,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  const char* name = "tbe_weighted_colsum_f32";
+  TBE_REQUIRE(out != nullptr, "%s: null out", name);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int vecs = N / 4;
-  if (vecs >= 64) {
-    hipLaunchKernelGGL(drelu_bgrad_kernel<64>, dim3((vecs + 63) / 64, static_cast<unsigned>(nrb)), dim3(256), 0, st, grad_out, act, grad_in, partial, B, N);
-  } else if (vecs >= 32) {
-    hipLaunchKernelGGL(drelu_bgrad_kernel<32>, dim3((vecs + 31) / 32, static_cast<unsigned>(nrb)), dim3(256), 0, st, grad_out, act, grad_in, partial, B, N);
-  } else {
-    hipLaunchKernelGGL(drelu_bgrad_kernel<16>, dim3((vecs + 15) / 16, static_cast<unsigned>(nrb)), dim3(256), 0, st, grad_out, act, grad_in, partial, B, N);
-  }
-  TBE_CHECK_LAUNCH("tbe_relu_backward_bias_partials_f32");
-  return TBE_OK;
+  int64_t nrb;
+  const int rc = weighted_colsum_first_stage(name, true, x, w, B, N, workspace, workspace_bytes, st, &nrb);
+  return rc != TBE_OK ? rc : launch_colsum_partials(name, static_cast<const float*>(workspace), nrb, N, out, st);
 }
 
 extern "C" int tbe_weighted_colsum_partials_f32(const float* x, const float* w, int64_t B, int32_t N, float* partial,
                                                 size_t partial_bytes, void* stream) {
-  TBE_REQUIRE(B > 0 && N > 0 && (N & 3) == 0, "tbe_weighted_colsum_partials_f32: B > 0 and N a positive multiple of 4 required");
-  TBE_REQUIRE(x && w && partial, "tbe_weighted_colsum_partials_f32: null pointer");
-  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(partial)) & 15) == 0,
-              "tbe_weighted_colsum_partials_f32: tensors must be 16-B aligned");
-  const int64_t nrb = tbe_colsum_row_blocks(B, N);
-  TBE_REQUIRE(nrb <= 65535, "tbe_weighted_colsum_partials_f32: B=%lld too large", (long long)B);
-  TBE_REQUIRE(partial_bytes >= static_cast<size_t>(nrb) * N * sizeof(float), "tbe_weighted_colsum_partials_f32: partial too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int vecs = N / 4;
-  if (vecs >= 64) {
-    hipLaunchKernelGGL(wcolsum_kernel<64>, dim3((vecs + 63) / 64, static_cast<unsigned>(nrb)), dim3(256), 0, st, x, w, partial, B, N);
-  } else if (vecs >= 32) {
-    hipLaunchKernelGGL(wcolsum_kernel<32>, dim3((vecs + 31) / 32, static_cast<unsigned>(nrb)), dim3(256), 0, st, x, w, partial, B, N);
-  } else {
-    hipLaunchKernelGGL(wcolsum_kernel<16>, dim3((vecs + 15) / 16, static_cast<unsigned>(nrb)), dim3(256), 0, st, x, w, partial, B, N);
-  }
-  TBE_CHECK_LAUNCH("tbe_weighted_colsum_partials_f32");
-  return TBE_OK;
+  int64_t nrb;
+  return weighted_colsum_first_stage("tbe_weighted_colsum_partials_f32", false, x, w, B, N, partial, partial_bytes,
+                                     static_cast<hipStream_t>(stream), &nrb);
 }
 
 extern "C" int tbe_multi_chunk_sum_f32(const int64_t* seg_table, int32_t nseg, int64_t max_numel, float* dst, float scale,

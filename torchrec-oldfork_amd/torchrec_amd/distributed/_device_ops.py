@@ -4,7 +4,7 @@ tbe_pooled_exchange_*).  Only the HIP key is registered here; CPU tensors raise.
 import torch
 
 from fbgemm_gpu import _lib
-from fbgemm_gpu._lib import check, ptr, require_gpu, stream_ptr
+from fbgemm_gpu._lib import check, ptr, require_gpu, stream_ptr, workspace
 
 _def = torch.library.Library("tbe_hip", "DEF")
 _def.define("pooled_exchange_unpack(Tensor recv, Tensor feat_out_col, Tensor feat_src, Tensor feat_slab_col, "
@@ -46,14 +46,26 @@ def _copy_rows(src, rows):
     return out
 
 
-def _weighted_colsum(x, w):
-    """out[c] = sum_b w[b] * x[b, c] (csrc/mlp_epilogue.hip)."""
-    from fbgemm_gpu._lib import workspace
-
+def _weighted_colsum_args(name, x, w):
+    """(device, contiguous float32 x [B, N], w [B]) of weighted_colsum / weighted_colsum_partials."""
     dev = require_gpu(x, w)
     if x.dim() != 2 or w.numel() != x.shape[0] or x.dtype != torch.float32 or w.dtype != torch.float32:
-        raise RuntimeError(f"weighted_colsum: need float32 x [B, N] and w [B], got {tuple(x.shape)} and {tuple(w.shape)}")
-    x, w = x.contiguous(), w.contiguous().view(-1)
+        raise RuntimeError(f"{name}: need float32 x [B, N] and w [B], got {tuple(x.shape)} and {tuple(w.shape)}")
+    return dev, x.contiguous(), w.contiguous().view(-1)
+
+
+def _relu_backward_args(name, grad_out, act):
+    """(device, contiguous float32 grad_out, act [B, N]) of relu_backward_bias_grad / relu_backward_bias_partials."""
+    dev = require_gpu(grad_out, act)
+    if grad_out.dim() != 2 or grad_out.shape != act.shape or grad_out.dtype != torch.float32 or act.dtype != torch.float32:
+        raise RuntimeError(f"{name}: need two float32 [B, N] tensors of one shape, got "
+                           f"{tuple(grad_out.shape)} and {tuple(act.shape)}")
+    return dev, grad_out.contiguous(), act.contiguous()
+
+
+def _weighted_colsum(x, w):
+    """out[c] = sum_b w[b] * x[b, c] (csrc/mlp_epilogue.hip)."""
+    dev, x, w = _weighted_colsum_args("weighted_colsum", x, w)
     B, N = x.shape
     out = torch.empty(N, dtype=torch.float32, device=dev)
     lib = _lib.load()
@@ -66,13 +78,7 @@ def _weighted_colsum(x, w):
 
 def _relu_backward_bias_grad(grad_out, act):
     """(grad_out * (act > 0), its column sums) in one pass (csrc/mlp_epilogue.hip)."""
-    from fbgemm_gpu._lib import workspace
-
-    dev = require_gpu(grad_out, act)
-    if grad_out.dim() != 2 or grad_out.shape != act.shape or grad_out.dtype != torch.float32 or act.dtype != torch.float32:
-        raise RuntimeError(f"relu_backward_bias_grad: need two float32 [B, N] tensors of one shape, got "
-                           f"{tuple(grad_out.shape)} and {tuple(act.shape)}")
-    grad_out, act = grad_out.contiguous(), act.contiguous()
+    dev, grad_out, act = _relu_backward_args("relu_backward_bias_grad", grad_out, act)
     B, N = grad_out.shape
     gx = torch.empty_like(grad_out)
     gb = torch.empty(N, dtype=torch.float32, device=dev)
@@ -87,11 +93,7 @@ def _relu_backward_bias_grad(grad_out, act):
 def _relu_backward_bias_partials(grad_out, act):
     """(grad_out * (act > 0), column sums of its row blocks [row blocks, N]) — the first stage of relu_backward_bias_grad
     alone; `multi_chunk_sum` finishes every layer's bias gradient in one launch (csrc/mlp_epilogue.hip)."""
-    dev = require_gpu(grad_out, act)
-    if grad_out.dim() != 2 or grad_out.shape != act.shape or grad_out.dtype != torch.float32 or act.dtype != torch.float32:
-        raise RuntimeError(f"relu_backward_bias_partials: need two float32 [B, N] tensors of one shape, got "
-                           f"{tuple(grad_out.shape)} and {tuple(act.shape)}")
-    grad_out, act = grad_out.contiguous(), act.contiguous()
+    dev, grad_out, act = _relu_backward_args("relu_backward_bias_partials", grad_out, act)
     B, N = grad_out.shape
     lib = _lib.load()
     gx = torch.empty_like(grad_out)
@@ -104,10 +106,7 @@ def _relu_backward_bias_partials(grad_out, act):
 
 def _weighted_colsum_partials(x, w):
     """Row-block partials [row blocks, N] of out[c] = sum_b w[b] * x[b, c] (first stage of weighted_colsum)."""
-    dev = require_gpu(x, w)
-    if x.dim() != 2 or w.numel() != x.shape[0] or x.dtype != torch.float32 or w.dtype != torch.float32:
-        raise RuntimeError(f"weighted_colsum_partials: need float32 x [B, N] and w [B], got {tuple(x.shape)} and {tuple(w.shape)}")
-    x, w = x.contiguous(), w.contiguous().view(-1)
+    dev, x, w = _weighted_colsum_args("weighted_colsum_partials", x, w)
     B, N = x.shape
     lib = _lib.load()
     partial = torch.empty((lib.tbe_colsum_row_blocks(B, N), N), dtype=torch.float32, device=dev)
@@ -120,8 +119,6 @@ def _weighted_colsum_partials(x, w):
 def _cross_backward(grad_out, x0, t, acc, first):
     """One layer's backward epilogue of CrossNet / LowRankCrossNet (csrc/crossnet.hip): returns (grad_out * x0, its column
     sums) and writes acc = grad_out * t (`first`) or acc += grad_out * t in place."""
-    from fbgemm_gpu._lib import workspace
-
     dev = require_gpu(grad_out, x0, t, acc)
     if (grad_out.dim() != 2 or any(a.shape != grad_out.shape or a.dtype != torch.float32 or not a.is_contiguous()
                                    for a in (grad_out, x0, t, acc))):
@@ -161,8 +158,6 @@ def _vector_cross_forward(x0, weights, bias):
 
 def _vector_cross_backward(grad_out, x0, s, weights, bias):
     """(input gradient [B, N], parameter gradients [2 L, N]: bias rows first, then weight rows) (csrc/crossnet.hip)."""
-    from fbgemm_gpu._lib import workspace
-
     dev = _vector_cross_check("vector_cross_backward", x0, weights, bias, grad_out, s)
     (B, N), L = x0.shape, weights.shape[0]
     if grad_out.shape != x0.shape or s.shape != (L, B):
