@@ -736,18 +736,39 @@ int tbe_relu_backward_bias_partials_f32(const float* grad_out, const float* act,
 int tbe_weighted_colsum_partials_f32(const float* x, const float* w, int64_t B, int32_t N, float* partial,
                                      size_t partial_bytes, void* stream);
 
+/* Backward of the last two layers of DLRM's over arch, h = relu(x W1^T + b1) and y = h w^T + b2 with ONE output
+ * (torchrec/models/dlrm.py OverArch), in one pass over act = h [B, N], given dy [B] and w [N]:
+ *   grad_in[b, c] = act[b, c] > 0 ? dy[b] * w[c] : 0     (the gradient of the hidden layer's pre-activation)
+ *   sums[0 .. N)  = sum_b grad_in[b, c]                   (b1's gradient: tbe_relu_backward_bias_grad_f32 of dy w, bit for bit)
+ *   sums[N .. 2N) = sum_b dy[b] * act[b, c]               (w's gradient: tbe_weighted_colsum_f32(act, dy), bit for bit)
+ * N a multiple of 4, tensors 16-B aligned.  `_partials` is the first stage alone (B > 0): the row blocks' sums stay in
+ * `partial` [tbe_colsum_row_blocks(B, N)][2 N] for a later tbe_multi_chunk_sum_*; the other entry finishes them itself
+ * (workspace: tbe_relu_linear1_backward_workspace_bytes, B = 0 gives zeros). */
+size_t tbe_relu_linear1_backward_workspace_bytes(int64_t B, int32_t N);
+int tbe_relu_linear1_backward_f32(const float* act, const float* dy, const float* w, int64_t B, int32_t N, float* grad_in,
+                                  float* sums, void* workspace, size_t workspace_bytes, void* stream);
+int tbe_relu_linear1_backward_partials_f32(const float* act, const float* dy, const float* w, int64_t B, int32_t N,
+                                           float* grad_in, float* partial, size_t partial_bytes, void* stream);
+
 /* dst[off_s + i] = scale * sum_{c < chunks_s} src_s[c * numel_s + i] for every segment s of `seg_table` — device int64
  * [nseg][4] = {src address, chunks, numel, dst element offset}; chunk order fixed (deterministic); chunks = 0 writes
- * zeros.  max_numel = the largest numel.  Finishes, in one launch, the split-K weight gradients (chunks = batch slices of
+ * zeros.  A segment of at most 16 chunks is added in plain sequence, a longer one in the order of the column sums'
+ * second stage (wave w of 4 adds the chunks w, w + 4, ... from 0; the result is ((a0 + a1) + a2) + a3);
+ * chunks | TBE_CHUNKS_WAVE_ORDER asks for that order at every count, so that a row-block segment ends as
+ * tbe_relu_backward_bias_grad_f32 / tbe_weighted_colsum_f32 end it, bit for bit, 1 row block included.
+ * max_numel = the largest numel.  Finishes, in one launch, the split-K weight gradients (chunks = batch slices of
  * the batched GEMM), the bias gradients (chunks = row blocks of the kernels above) and the already complete gradients
  * (chunks = 1) of the dense MLPs' backward, scaled by 1 / world size, into the flat gradient buffer that is all-reduced —
  * what the reference leaves to per-parameter autograd kernels + DistributedDataParallel's bucket copies
  * (torchrec/distributed/model_parallel.py:101-111). */
+#define TBE_CHUNKS_WAVE_ORDER (1ll << 62)
 int tbe_multi_chunk_sum_f32(const int64_t* seg_table, int32_t nseg, int64_t max_numel, float* dst, float scale,
                             void* stream);
 /* The same with the table in HOST memory, at most 32 segments: it travels by value in the kernel arguments (no copy the
  * GPU performs later, so the caller may reuse the host buffer at once) — for eager steps, whose sources and destinations
- * change every step.  With dst = NULL the destination offsets are absolute addresses / 4. */
+ * change every step.  With dst = NULL the destination offsets are absolute addresses / 4.  A table in which every segment
+ * carries TBE_CHUNKS_WAVE_ORDER (the row-block sums of an eager backward) runs in the second stage's own geometry, 64
+ * columns per workgroup, with more loads in flight: same order, same bits. */
 int tbe_multi_chunk_sum_host_table_f32(const int64_t* host_seg_table, int32_t nseg, int64_t max_numel, float* dst,
                                        float scale, void* stream);
 

@@ -2,9 +2,11 @@
 // atomics; the order depends on B and N only and is pinned by tests/test_colsum_order_gpu.py):
 //   first stage   a workgroup of 256 threads = TY rows x TX float4 columns owns rows_per_block(N) rows.  Thread row ty starts
 //                 from 0.0f and adds the rows ty, ty + TY, ... of its block; the block's sum of a column is red[0] + red[1]
-//                 + ... + red[TY - 1], left to right, and goes to partial[row block][N].
+//                 + ... + red[TY - 1], left to right, and goes to partial[row block][N].  A kernel with two sums per
+//                 column (the head backward, mlp_epilogue.hip) keeps both in this order: partial[row block][2][N].
 //   second stage  colsum_partials_kernel (mlp_epilogue.hip): wave w of 4 adds the blocks w, w + 4, ...; the result is
-//                 ((a0 + a1) + a2) + a3.  A captured backward finishes all its layers with one multi_chunk_sum instead.
+//                 ((a0 + a1) + a2) + a3.  A captured backward, and an eager one that defers (modules/mlp.py _EagerFinish),
+//                 finish all their layers with one multi_chunk_sum instead, which keeps this order (TBE_CHUNKS_WAVE_ORDER).
 #pragma once
 #include <initializer_list>
 #include <type_traits>
@@ -28,30 +30,44 @@ __device__ __forceinline__ void add4(float4& a, const float4 b) {
   a.w += b.w;
 }
 
-// First stage of a kernel with grid = (column tiles, row blocks): body(row, row * N + column, sum) does one float4 of one row and
-// adds its addend to `sum`.  It captures the kernel's own __restrict__ parameters, which let the four unrolled rows' loads go first.
-template <int TX, typename RowBody>
-__device__ __forceinline__ void colsum_row_block(float* __restrict__ partial, int64_t B, int N, RowBody body) {
+// First stage of a kernel with grid = (column tiles, row blocks) that keeps NS sums per column, each in the order above:
+// body(row, row * N + column, sum) does one float4 of one row and adds its addends to sum[0 .. NS).  It captures the kernel's
+// own __restrict__ parameters, which let the four unrolled rows' loads go first.  The row block's sums go to
+// partial[row block][NS][N]: one second stage over NS * N columns finishes all of them.  LDS: NS * 4 KB.
+template <int TX, int NS, typename RowBody>
+__device__ __forceinline__ void colsum_row_block_n(float* __restrict__ partial, int64_t B, int N, RowBody body) {
   constexpr int TY = 256 / TX;
-  __shared__ float4 red[TY][TX];
+  __shared__ float4 red[NS][TY][TX];
   const int tx = threadIdx.x % TX;
   const int ty = threadIdx.x / TX;
   const int col = (blockIdx.x * TX + tx) * 4;
   const int64_t row0 = static_cast<int64_t>(blockIdx.y) * rows_per_block(N);
   const int64_t row1 = min(B, row0 + rows_per_block(N));
-  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 sum[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) sum[s] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (col < N) {
 #pragma unroll 4
     for (int64_t r = row0 + ty; r < row1; r += TY) body(r, r * N + col, sum);
   }
-  red[ty][tx] = sum;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) red[s][ty][tx] = sum[s];
   __syncthreads();
   if (ty == 0 && col < N) {
-    float4 s = red[0][tx];
 #pragma unroll
-    for (int y = 1; y < TY; ++y) add4(s, red[y][tx]);
-    st4(partial + static_cast<int64_t>(blockIdx.y) * N + col, s);
+    for (int s = 0; s < NS; ++s) {
+      float4 a = red[s][0][tx];
+#pragma unroll
+      for (int y = 1; y < TY; ++y) add4(a, red[s][y][tx]);
+      st4(partial + (static_cast<int64_t>(blockIdx.y) * NS + s) * N + col, a);
+    }
   }
+}
+
+// The one-sum form: body(row, row * N + column, float4& sum).
+template <int TX, typename RowBody>
+__device__ __forceinline__ void colsum_row_block(float* __restrict__ partial, int64_t B, int N, RowBody body) {
+  colsum_row_block_n<TX, 1>(partial, B, N, [&](int64_t r, int64_t o, float4(&sum)[1]) { body(r, o, sum[0]); });
 }
 
 // launch(std::integral_constant<int, TX>, grid) for the TX of N: 64, 32 or 16 float4 columns per workgroup

@@ -46,6 +46,45 @@ __global__ __launch_bounds__(256) void wcolsum_kernel(const float* __restrict__ 
   });
 }
 
+// Backward of y = relu(.) W2^T behind a hidden layer with ReLU, W2 = w [1, N] (the last two layers of DLRM's over arch), in
+// ONE pass over act [B, N]: the gradient of the hidden layer's pre-activation and both column sums that hang on it —
+//   g = dy[b] * w[c]                       (one multiply: what the K = 1 GEMM dy w writes)
+//   gx[b, c] = act[b, c] > 0 ? g : 0       partial[rb][0][c] += gx[b, c]                  (drelu_bgrad_kernel's addend)
+//                                          partial[rb][1][c]  = fmaf(dy[b], act[b, c], .)  (wcolsum_kernel's)
+// instead of that GEMM (writes [B, N]), wcolsum_kernel (reads act) and drelu_bgrad_kernel (reads both, writes gx).
+// Addresses: the row block's (uniform) base + a 32-bit offset inside the block (N <= kHeadMaxN keeps 256 rows below 4 GB),
+// one VGPR per row for the load and the store instead of two 64-bit addresses — with those the kernel took 66 VGPRs, two
+// more than 8 waves per SIMD (drelu_bgrad_kernel's figure) allow.
+constexpr int kHeadMaxN = 1 << 20;
+template <int TX>
+__global__ __launch_bounds__(256) void relu_linear1_bwd_kernel(const float* __restrict__ act, const float* __restrict__ dy,
+                                                               const float* __restrict__ w, float* __restrict__ gx,
+                                                               float* __restrict__ partial, int64_t B, int N) {
+  const int col = (blockIdx.x * TX + threadIdx.x % TX) * 4;
+  const float4 wc = col < N ? ld4(w + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+  const int64_t row0 = static_cast<int64_t>(blockIdx.y) * rows_per_block(N);
+  const char* __restrict__ act_b = reinterpret_cast<const char*>(act + row0 * N);
+  char* __restrict__ gx_b = reinterpret_cast<char*>(gx + row0 * N);
+  const float* __restrict__ dy_b = dy + row0;
+  colsum_row_block_n<TX, 2>(partial, B, N, [=](int64_t r, int64_t, float4(&sum)[2]) {
+    const unsigned lr = static_cast<unsigned>(r - row0);  // < rows_per_block(N)
+    const unsigned off = (lr * static_cast<unsigned>(N) + static_cast<unsigned>(col)) * 4u;
+    const float4 a = *reinterpret_cast<const float4*>(act_b + off);
+    const float d = dy_b[lr];
+    float4 g;
+    g.x = a.x > 0.f ? d * wc.x : 0.f;
+    g.y = a.y > 0.f ? d * wc.y : 0.f;
+    g.z = a.z > 0.f ? d * wc.z : 0.f;
+    g.w = a.w > 0.f ? d * wc.w : 0.f;
+    *reinterpret_cast<float4*>(gx_b + off) = g;
+    add4(sum[0], g);
+    sum[1].x = fmaf(d, a.x, sum[1].x);
+    sum[1].y = fmaf(d, a.y, sum[1].y);
+    sum[1].z = fmaf(d, a.z, sum[1].z);
+    sum[1].w = fmaf(d, a.w, sum[1].w);
+  });
+}
+
 // bias_grad[c] = sum over row blocks of partial[rb][c], fixed order: wave w takes blocks w, w+4, ...
 __global__ __launch_bounds__(256) void colsum_partials_kernel(const float* __restrict__ partial, int64_t nblocks, int N,
                                                               float* __restrict__ out) {
@@ -93,13 +132,47 @@ __global__ __launch_bounds__(256) void multi_chunk_sum_args_kernel(const ChunkSe
   multi_chunk_sum_body(segs.s[blockIdx.y], dst, scale);
 }
 
-__device__ __forceinline__ void multi_chunk_sum_body(const ChunkSeg sg, float* __restrict__ dst, float scale) {
+// A table of TBE_CHUNKS_WAVE_ORDER segments only (the row-block sums of an eager backward: up to 1024 row blocks of a few
+// hundred columns each) in colsum_partials_kernel's own geometry — 64 columns x 4 waves per block, four times the blocks of
+// the float4 form — and 32 loads in flight per lane: a wave's chain of up to 256 row blocks is what the launch waits for.
+// grid = (tiles of 64 elements, segments).  Same order: wave w adds w, w + 4, ... from 0, then ((a0 + a1) + a2) + a3.
+__global__ __launch_bounds__(256) void multi_colsum_partials_kernel(const ChunkSegs32 segs, float* __restrict__ dst, float scale) {
+  __shared__ float red[4][64];
+  const ChunkSeg sg = segs.s[blockIdx.y];
+  const int64_t chunks = sg.chunks & ~TBE_CHUNKS_WAVE_ORDER;
+  if (static_cast<int64_t>(blockIdx.x) * 64 >= sg.numel) return;  // block-uniform
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int64_t c = static_cast<int64_t>(blockIdx.x) * 64 + lane;
+  float acc = 0.f;
+  if (c < sg.numel) {
+    const float* p = sg.src + c;
+    int64_t rb = wave;
+    for (; rb + 4 * 31 < chunks; rb += 4 * 32) {
+      float a[32];
+#pragma unroll
+      for (int u = 0; u < 32; ++u) a[u] = p[(rb + 4 * u) * sg.numel];
+#pragma unroll
+      for (int u = 0; u < 32; ++u) acc += a[u];
+    }
+#pragma unroll 8
+    for (; rb < chunks; rb += 4) acc += p[rb * sg.numel];
+  }
+  red[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && c < sg.numel) dst[sg.dst_off + c] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * scale;
+}
+
+__device__ __forceinline__ void multi_chunk_sum_body(ChunkSeg sg, float* __restrict__ dst, float scale) {
   // many chunks (row-block sums of a bias: 32 ... 1024): block = 64 float4 columns x 4 waves; wave w adds chunks w, w + 4,
   // w + 8, ... (8 loads in flight), the four wave sums are combined through LDS in wave order.  Few chunks (split-K
   // slices of a weight: <= 16): block = 256 float4 columns, every thread adds all chunks of its column (all loads in
-  // flight).  Either way the summation order is a function of (chunks) only.
+  // flight).  Either way the summation order is a function of (chunks) only.  TBE_CHUNKS_WAVE_ORDER in `chunks` takes the
+  // first form at every count: colsum_partials_kernel's order, for row-block sums of few row blocks.
   __shared__ float4 red[4][64];
-  if (sg.chunks <= 16) {  // segment-uniform, hence block-uniform
+  const bool wave_order = (sg.chunks & TBE_CHUNKS_WAVE_ORDER) != 0;
+  sg.chunks &= ~TBE_CHUNKS_WAVE_ORDER;
+  if (!wave_order && sg.chunks <= 16) {  // segment-uniform, hence block-uniform
     const int64_t j0 = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
     if (j0 >= sg.numel) return;
     float* o = dst + sg.dst_off + j0;
@@ -270,6 +343,17 @@ static int weighted_colsum_first_stage(const char* name, bool one_pass, const fl
   });
 }
 
+// two sums per column: `partial` is [row blocks][2 N], so half its bytes must hold a one-sum kernel's [row blocks][N]
+static int relu_linear1_first_stage(const char* name, bool one_pass, const float* act, const float* dy, const float* w, int64_t B,
+                                    int32_t N, float* grad_in, void* partial, size_t partial_bytes, hipStream_t st, int64_t* nrb) {
+  TBE_REQUIRE(dy != nullptr || B == 0, "%s: null pointer", name);
+  TBE_REQUIRE(N <= kHeadMaxN, "%s: N=%d above %d", name, N, kHeadMaxN);
+  return colsum_first_stage(name, one_pass, B, N, {act, w, grad_in}, partial, partial_bytes / 2, nrb, [&](auto tx, dim3 grid) {
+    hipLaunchKernelGGL(relu_linear1_bwd_kernel<decltype(tx)::value>, grid, dim3(256), 0, st, act, dy, w, grad_in,
+                       static_cast<float*>(partial), B, N);
+  });
+}
+
 extern "C" int64_t tbe_colsum_row_blocks(int64_t B, int32_t N) { return B <= 0 || N <= 0 ? 0 : colsum_row_blocks(B, N); }
 extern "C" size_t tbe_relu_backward_bias_grad_workspace_bytes(int64_t B, int32_t N) { return colsum_workspace_bytes(B, N); }
 extern "C" size_t tbe_weighted_colsum_workspace_bytes(int64_t B, int32_t N) { return colsum_workspace_bytes(B, N); }
@@ -309,6 +393,26 @@ extern "C" int tbe_weighted_colsum_partials_f32(const float* x, const float* w, 
                                      static_cast<hipStream_t>(stream), &nrb);
 }
 
+extern "C" size_t tbe_relu_linear1_backward_workspace_bytes(int64_t B, int32_t N) { return 2 * colsum_workspace_bytes(B, N); }
+
+extern "C" int tbe_relu_linear1_backward_f32(const float* act, const float* dy, const float* w, int64_t B, int32_t N,
+                                             float* grad_in, float* sums, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+  const char* name = "tbe_relu_linear1_backward_f32";
+  TBE_REQUIRE(sums != nullptr, "%s: null sums", name);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int64_t nrb;
+  const int rc = relu_linear1_first_stage(name, true, act, dy, w, B, N, grad_in, workspace, workspace_bytes, st, &nrb);
+  return rc != TBE_OK ? rc : launch_colsum_partials(name, static_cast<const float*>(workspace), nrb, 2 * N, sums, st);
+}
+
+extern "C" int tbe_relu_linear1_backward_partials_f32(const float* act, const float* dy, const float* w, int64_t B, int32_t N,
+                                                      float* grad_in, float* partial, size_t partial_bytes, void* stream) {
+  int64_t nrb;
+  return relu_linear1_first_stage("tbe_relu_linear1_backward_partials_f32", false, act, dy, w, B, N, grad_in, partial,
+                                  partial_bytes, static_cast<hipStream_t>(stream), &nrb);
+}
+
 extern "C" int tbe_multi_chunk_sum_f32(const int64_t* seg_table, int32_t nseg, int64_t max_numel, float* dst, float scale,
                                        void* stream) {
   TBE_REQUIRE(nseg >= 0 && max_numel >= 0, "tbe_multi_chunk_sum_f32: bad sizes");
@@ -332,6 +436,16 @@ extern "C" int tbe_multi_chunk_sum_host_table_f32(const int64_t* host_seg_table,
   TBE_REQUIRE(host_seg_table != nullptr, "tbe_multi_chunk_sum_host_table_f32: null table");
   ChunkSegs32 segs{};
   memcpy(segs.s, host_seg_table, static_cast<size_t>(nseg) * sizeof(ChunkSeg));
+  bool all_wave_order = true;
+  for (int s = 0; s < nseg; ++s) all_wave_order = all_wave_order && (segs.s[s].chunks & TBE_CHUNKS_WAVE_ORDER) != 0;
+  if (all_wave_order) {  // row-block sums only: the narrow form (same order, more blocks, more loads in flight)
+    const int64_t tiles64 = (max_numel + 63) / 64;
+    TBE_REQUIRE(tiles64 < (1ll << 31), "tbe_multi_chunk_sum_host_table_f32: segment too long");
+    hipLaunchKernelGGL(multi_colsum_partials_kernel, dim3(static_cast<unsigned>(tiles64), static_cast<unsigned>(nseg)), dim3(256),
+                       0, static_cast<hipStream_t>(stream), segs, dst, scale);
+    TBE_CHECK_LAUNCH("tbe_multi_chunk_sum_host_table_f32");
+    return TBE_OK;
+  }
   const int64_t tiles = (max_numel + 255) / 256;
   TBE_REQUIRE(tiles < (1ll << 31), "tbe_multi_chunk_sum_host_table_f32: segment too long");
   hipLaunchKernelGGL(multi_chunk_sum_args_kernel, dim3(static_cast<unsigned>(tiles), static_cast<unsigned>(nseg)), dim3(256), 0,

@@ -60,6 +60,8 @@ class FmGradSegment(ctypes.Structure):
 
 
 FM_MAX_SEGMENTS = 8  # TBE_FM_MAX_SEGMENTS
+CHUNKS_WAVE_ORDER = 1 << 62  # TBE_CHUNKS_WAVE_ORDER
+CHUNK_SEGS_BY_VALUE = 32  # segments of one tbe_multi_chunk_sum_host_table_f32 call
 
 
 class CacheDesc(ctypes.Structure):
@@ -198,6 +200,11 @@ SIGNATURES = {
         ctypes.c_int, [c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_size, c_void_p]),
     "tbe_weighted_colsum_partials_f32": (
         ctypes.c_int, [c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_size, c_void_p]),
+    "tbe_relu_linear1_backward_workspace_bytes": (c_size, [c_i64, c_i32]),
+    "tbe_relu_linear1_backward_f32": (
+        ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "tbe_relu_linear1_backward_partials_f32": (
+        ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_size, c_void_p]),
     "tbe_multi_chunk_sum_f32": (ctypes.c_int, [c_void_p, c_i32, c_i64, c_void_p, c_float, c_void_p]),
     "tbe_multi_chunk_sum_host_table_f32": (ctypes.c_int, [c_void_p, c_i32, c_i64, c_void_p, c_float, c_void_p]),
     "tbe_cross_backward_workspace_bytes": (c_size, [c_i64, c_i32]),

@@ -22,6 +22,8 @@ _def.define("weighted_colsum(Tensor x, Tensor w) -> Tensor")
 _def.define("copy_rows(Tensor src, Tensor rows) -> Tensor")
 _def.define("relu_backward_bias_partials(Tensor grad_out, Tensor act) -> (Tensor, Tensor)")
 _def.define("weighted_colsum_partials(Tensor x, Tensor w) -> Tensor")
+_def.define("relu_linear1_backward(Tensor act, Tensor dy, Tensor w) -> (Tensor, Tensor)")
+_def.define("relu_linear1_backward_partials(Tensor act, Tensor dy, Tensor w) -> (Tensor, Tensor)")
 _def.define("multi_chunk_sum(Tensor seg_table, int nseg, int max_numel, Tensor(a!) dst, float scale) -> Tensor(a!)")
 _def.define("bce_with_logits(Tensor logits, Tensor labels) -> (Tensor, Tensor)")
 _def.define("cross_backward(Tensor grad_out, Tensor x0, Tensor t, Tensor(a!) acc, bool first) -> (Tensor, Tensor)")
@@ -114,6 +116,68 @@ def _weighted_colsum_partials(x, w):
         check(lib.tbe_weighted_colsum_partials_f32(ptr(x), ptr(w), B, N, ptr(partial), partial.numel() * 4, stream_ptr(dev)),
               "tbe_weighted_colsum_partials_f32")
     return partial
+
+
+def _relu_linear1_args(name, act, dy, w):
+    """(device, contiguous float32 act [B, N], dy [B], w [N]) of relu_linear1_backward / relu_linear1_backward_partials."""
+    dev = require_gpu(act, dy, w)
+    if (act.dim() != 2 or dy.numel() != act.shape[0] or w.numel() != act.shape[1]
+            or any(t.dtype != torch.float32 for t in (act, dy, w))):
+        raise RuntimeError(f"{name}: need float32 act [B, N], dy [B] and w [N], got {tuple(act.shape)}, {tuple(dy.shape)} "
+                           f"and {tuple(w.shape)}")
+    return dev, act.contiguous(), dy.contiguous().view(-1), w.contiguous().view(-1)
+
+
+def _relu_linear1_backward(act, dy, w):
+    """(gx = (act > 0) * dy[:, None] * w[None, :], sums [2 N]: the column sums of gx, then of dy[:, None] * act) in one pass
+    over act (csrc/mlp_epilogue.hip): the backward of a one-output Linear behind a hidden layer with ReLU."""
+    dev, act, dy, w = _relu_linear1_args("relu_linear1_backward", act, dy, w)
+    B, N = act.shape
+    gx = torch.empty_like(act)
+    sums = torch.empty(2 * N, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = workspace(lib.tbe_relu_linear1_backward_workspace_bytes(B, N), dev)
+        check(lib.tbe_relu_linear1_backward_f32(ptr(act), ptr(dy), ptr(w), B, N, ptr(gx), ptr(sums), ptr(ws), ws.numel(),
+                                                stream_ptr(dev)), "tbe_relu_linear1_backward_f32")
+    return gx, sums
+
+
+def _relu_linear1_backward_partials(act, dy, w):
+    """(gx, the row blocks' sums [row blocks, 2 N]) — the first stage of relu_linear1_backward alone; `finish_row_block_sums`
+    finishes it together with every other gradient of the backward."""
+    dev, act, dy, w = _relu_linear1_args("relu_linear1_backward_partials", act, dy, w)
+    B, N = act.shape
+    lib = _lib.load()
+    gx = torch.empty_like(act)
+    partial = torch.empty((lib.tbe_colsum_row_blocks(B, N), 2 * N), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.tbe_relu_linear1_backward_partials_f32(ptr(act), ptr(dy), ptr(w), B, N, ptr(gx), ptr(partial),
+                                                         partial.numel() * 4, stream_ptr(dev)),
+              "tbe_relu_linear1_backward_partials_f32")
+    return gx, partial
+
+
+def finish_row_block_sums(segments, dst):
+    """dst[off : off + n] = the column sums of `partial` [row blocks, n], in the order of the column sums' second stage
+    (csrc/colsum.hpp), for every (partial, off) of `segments`: one launch per 32 segments, the table travelling in the
+    kernel arguments (csrc/mlp_epilogue.hip multi_chunk_sum_args_kernel).  The caller keeps the partials alive until then."""
+    dev = require_gpu(dst, *[p for p, _ in segments])
+    if dst.dtype != torch.float32 or not dst.is_contiguous():
+        raise RuntimeError("finish_row_block_sums: dst must be a contiguous float32 tensor")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        for lo in range(0, len(segments), _lib.CHUNK_SEGS_BY_VALUE):
+            group = segments[lo:lo + _lib.CHUNK_SEGS_BY_VALUE]
+            table = (_lib.c_i64 * (4 * len(group)))()
+            for k, (part, off) in enumerate(group):
+                if part.dim() != 2 or part.dtype != torch.float32 or not part.is_contiguous() or off + part.shape[1] > dst.numel():
+                    raise RuntimeError(f"finish_row_block_sums: segment {lo + k} is not a contiguous float32 [row blocks, n] "
+                                       f"that fits dst ({tuple(part.shape)} at {off} of {dst.numel()})")
+                table[4 * k:4 * k + 4] = [part.data_ptr(), part.shape[0] | _lib.CHUNKS_WAVE_ORDER, part.shape[1], off]
+            check(lib.tbe_multi_chunk_sum_host_table_f32(table, len(group), max(p.shape[1] for p, _ in group), ptr(dst), 1.0,
+                                                         stream_ptr(dev)), "tbe_multi_chunk_sum_host_table_f32")
+    return dst
 
 
 def _cross_backward(grad_out, x0, t, acc, first):
@@ -391,6 +455,8 @@ _impl.impl("weighted_colsum", _weighted_colsum)
 _impl.impl("copy_rows", _copy_rows)
 _impl.impl("relu_backward_bias_partials", _relu_backward_bias_partials)
 _impl.impl("weighted_colsum_partials", _weighted_colsum_partials)
+_impl.impl("relu_linear1_backward", _relu_linear1_backward)
+_impl.impl("relu_linear1_backward_partials", _relu_linear1_backward_partials)
 _impl.impl("cross_backward", _cross_backward)
 _impl.impl("vector_cross_forward", _vector_cross_forward)
 _impl.impl("vector_cross_backward", _vector_cross_backward)

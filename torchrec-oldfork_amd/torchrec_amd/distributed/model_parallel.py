@@ -88,6 +88,9 @@ class DistributedModelParallel(nn.Module):
                             ignore.append(f"{path}.{n}" if path else n)
             ignore += [n for n, p in m.named_parameters() if id(p) in flat_ids]
             DistributedDataParallel._set_params_and_buffers_to_ignore_for_model(m, ignore)
+            for sub in m.modules():  # the reducer's hooks wait for the engine to deliver every gradient (models/dlrm.py)
+                if hasattr(sub, "deferred_dense_finish"):
+                    sub.deferred_dense_finish = False
             self._dmp_wrapped_module = DistributedDataParallel(
                 m, device_ids=[self.device.index] if self.device.type == "cuda" else None,
                 process_group=self._env.process_group, gradient_as_bucket_view=True, broadcast_buffers=False,

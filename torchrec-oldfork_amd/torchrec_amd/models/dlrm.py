@@ -12,7 +12,7 @@ from fbgemm_gpu import _lib
 from fbgemm_gpu._lib import check, ptr, stream_ptr
 from torch import nn
 
-from ..modules.mlp import MLP, LinearOut
+from ..modules.mlp import MLP, LinearOut, _EagerFinish, relu_linear1_head
 from ..profiling import label
 from ..sparse.jagged_tensor import KeyedJaggedTensor, KeyedTensor
 
@@ -260,8 +260,20 @@ class OverArch(nn.Module):
         self.model = nn.Sequential(
             MLP(in_features, layer_sizes[:-1], bias=True, activation="relu", device=device),
             LinearOut(layer_sizes[-2], layer_sizes[-1], bias=True, device=device))
+        # The last hidden layer and a one-output last layer run as one autograd node whose backward is one pass over the
+        # hidden activation (modules/mlp.py relu_linear1_head).  False = the two modules' own nodes (tests).  While it is
+        # on, forward() calls the Perceptrons and the last layer one by one — also when relu_linear1_head declines — so
+        # forward hooks on `self.model`, on its MLP (and its nn.Sequential) do not fire, and where the node applies neither do
+        # those of the last Perceptron and the LinearOut; same results.  Whoever hooks these modules sets it to False.
+        self.fused_head = True
 
     def forward(self, features: torch.Tensor) -> torch.Tensor:
+        if self.fused_head:
+            layers, last = self.model[0]._mlp, self.model[1]
+            for i in range(len(layers) - 1):
+                features = layers[i](features)
+            out = relu_linear1_head(layers[-1], last, features)
+            return out if out is not None else last(layers[-1](features))
         return self.model(features)
 
 
@@ -293,6 +305,14 @@ class DLRM(nn.Module):
         # On the gather path with exact SGD the interaction backward also writes the updated row of every contribution
         # that alone touches its row (_FusedGatherInteraction single_row_sgd).  False = the plain pair of calls (tests).
         self.fused_single_row_update = True
+        # On the gather path (one rank, eager) the dense stacks' bias gradients and the one-output layer's weight gradient
+        # are finished by ONE launch at the end of backward instead of one per layer (modules/mlp.py _EagerFinish): their
+        # `.grad` is set when backward() returns, not by the engine's accumulation.  False = one launch per layer; a
+        # DistributedDataParallel wrapper, whose reducer waits for the engine, turns it off (model_parallel.py).  Set it to
+        # False before torch.autograd.grad(..., these parameters): with it on that call gets None for them and their
+        # `.grad` is set as a side effect.  The pending list is class state (one backward at a time, any thread) keyed by
+        # the engine's graph-task id (torch._C._current_graph_task_id, a private name).
+        self.deferred_dense_finish = True
 
     def _deferred_lookup(self, dense_features: torch.Tensor, sparse_features: KeyedJaggedTensor):
         """The collection's DeferredLookup for this batch, or None (nothing consumed) when the gather path cannot serve it."""
@@ -313,11 +333,12 @@ class DLRM(nn.Module):
     def forward(self, dense_features: torch.Tensor, sparse_features: KeyedJaggedTensor) -> torch.Tensor:
         lookup = self._deferred_lookup(dense_features, sparse_features)
         if lookup is not None:
-            embedded_dense = self.dense_arch(dense_features)
-            concatenated = _FusedGatherInteraction.apply(embedded_dense, lookup.module.placeholder_autograd_tensor, lookup,
-                                                         self.inter_arch.pad_rows, self.fused_single_row_update)
-            self.fused_lookup_steps += 1
-            return self.over_arch(concatenated)
+            with _EagerFinish.enable(self.deferred_dense_finish):
+                embedded_dense = self.dense_arch(dense_features)
+                concatenated = _FusedGatherInteraction.apply(embedded_dense, lookup.module.placeholder_autograd_tensor, lookup,
+                                                             self.inter_arch.pad_rows, self.fused_single_row_update)
+                self.fused_lookup_steps += 1
+                return self.over_arch(concatenated)
         # The reference runs dense_arch, then sparse_arch (models/dlrm.py:400-401).  Here the lookup and
         # the pooled all-to-all are issued first so that the exchange overlaps the bottom MLP on the
         # collective's own HIP stream; the two branches are independent, results are identical.
