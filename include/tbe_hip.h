@@ -808,6 +808,27 @@ int tbe_vector_cross_backward_f32(const float* grad_out, const float* x0, const 
                                   const float* bias, int64_t B, int32_t N, int32_t L, float* grad_in, float* grad_params,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* LowRankMixtureCrossNet (torchrec/modules/crossnet.py:271-446; the layer at :403-444) with the K experts folded into one
+ * low-rank layer of rank K r:  sum_k p_k x_0 (U_k h_k + b) = x_0 ([p_1 h_1 | ... | p_K h_K] Ucat^T + b), since the softmax
+ * weights p sum to 1.  These two entries are the narrow pass between the folded GEMMs: softmax of the gate logits, the
+ * second ReLU, the scale by p_k and the change of layout from the batched expert GEMM's to the Ucat GEMM's.
+ *   a2, grad_a2 [K, B, r];  m, grad_m [B, K r];  logits, p, grad_logits [B, K];  all contiguous fp32.
+ * With relu(a) = a > 0 ? a : +0, per row b:
+ *   forward    mx = max_k logits[b, k];  e_k = expf(logits[b, k] - mx);  s = ((e_0 + e_1) + ...) + e_{K-1}  (k order);
+ *              p[b, k] = e_k / s;   m[b, k r + j] = p[b, k] * relu(a2[k, b, j])           (one product, rounded once)
+ *   backward   d_k = sum_j grad_m[b, k r + j] * relu(a2[k, b, j])            (a fixed order that depends on r only);
+ *              t = ((p_0 d_0 + p_1 d_1) + ...) + p_{K-1} d_{K-1}  (k order);   grad_logits[b, k] = p_k * (d_k - t);
+ *              grad_a2[k, b, j] = a2[k, b, j] > 0 ? p_k * grad_m[b, k r + j] : 0
+ * Each product and each add is rounded on its own; no float atomics; two runs are bit-identical.  With r % 4 == 0 and every
+ * base 16-B aligned the data moves as float4, otherwise as scalars: the choice changes no result bit.
+ * Limits: 2 <= K <= 16, 1 <= r <= 2^26, B >= 0.  Errors, before anything is launched: TBE_ERR_INVALID_ARGUMENT, with a
+ * message that names the entry, for K or r beyond the limits, a null pointer or a base off the 4-byte grid.  B == 0 is
+ * success and touches nothing. */
+int tbe_mixture_gate_forward_f32(const float* a2, const float* logits, int64_t B, int32_t K, int32_t r, float* m, float* p,
+                                 void* stream);
+int tbe_mixture_gate_backward_f32(const float* grad_m, const float* a2, const float* p, int64_t B, int32_t K, int32_t r,
+                                  float* grad_a2, float* grad_logits, void* stream);
+
 /* DeepFM interaction: the factorization-machine term and the deep branch's concatenated row in one pass each way.
  * Replaces torchrec/modules/deepfm.py:28-32 (_get_flatten_input: torch.cat of all inputs, once per branch), :209-215
  * (FactorizationMachine.forward: x * x, two row sums, a square) and what torchrec/models/deepfm.py:175-184 builds from

@@ -17,6 +17,9 @@
 // the biases in the forward's own operation order (so bit for bit the forward's x_l) and produces the input gradient and
 // the row-block partial sums of all 2 L parameter gradients, which ONE second-stage launch over 2 L N columns finishes.
 //
+// LowRankMixtureCrossNet (:271-446) is LowRankCrossNet's layer of rank K r once its K experts are folded (include/tbe_hip.h);
+// what it adds is one narrow pass over [B, K r] between the GEMMs each way: mixture_gate_fwd_kernel / _bwd_kernel below.
+//
 // Every product and every add is rounded on its own (the Makefile builds with -ffp-contract=off; no fmaf here), so a float32
 // restatement in numpy reproduces the element-wise results bit for bit.
 #include <algorithm>
@@ -241,6 +244,122 @@ __global__ __launch_bounds__(256) void vector_cross_bwd_kernel(const float* __re
 
 static int64_t vec_row_blocks(int64_t B) { return (B + kVecRowsPerBlock - 1) / kVecRowsPerBlock; }
 
+// ---- LowRankMixtureCrossNet: the narrow pass between the folded GEMMs -----------------------------------------------------
+// a2, grad_a2 [K, B, r] (what the batched GEMM over experts writes / reads); m, grad_m [B, K r] (what the Ucat GEMMs read /
+// write); logits, p, grad_logits [B, K].  Per row b, with relu(a) = a > 0 ? a : +0:
+//   forward    mx = max_k logits[b, k];  e_k = expf(logits[b, k] - mx);  s = ((e_0 + e_1) + ...) + e_{K-1};
+//              p[b, k] = e_k / s;  m[b, k r + j] = p[b, k] * relu(a2[k, b, j])                      (one product)
+//   backward   d_k = sum_j grad_m[b, k r + j] * relu(a2[k, b, j]);  t = ((p_0 d_0 + p_1 d_1) + ...) + p_{K-1} d_{K-1};
+//              grad_logits[b, k] = p_k * (d_k - t);  grad_a2[k, b, j] = a2[k, b, j] > 0 ? p_k * grad_m[b, k r + j] : 0
+// One wave per row, four rows per workgroup; lane k holds p_k (and d_k).  d_k: lane i adds the columns 4 (i + 64 n) + c,
+// n = 0, 1, ..., c = 0 .. 3, in that order from 0.0f, then the xor butterfly of row_sum — an order that depends on r only
+// and is the same whether the columns move as float4 or as scalars.
+constexpr int kMixMaxK = 16;
+constexpr int kMixRowsPerBlock = 4;
+
+__device__ __forceinline__ float relu1(const float a) { return a > 0.f ? a : 0.f; }
+
+// p[b, lane] for lane < K (0 in the other lanes); all 64 lanes of the row's wave call it
+__device__ __forceinline__ float mix_softmax(const float* __restrict__ logits_row, const int K, const int lane) {
+  const float lg = lane < K ? logits_row[lane] : 0.f;
+  float mx = __shfl(lg, 0, kWave);
+  for (int k = 1; k < K; ++k) mx = fmaxf(mx, __shfl(lg, k, kWave));
+  const float e = lane < K ? expf(lg - mx) : 0.f;
+  float s = __shfl(e, 0, kWave);
+  for (int k = 1; k < K; ++k) s += __shfl(e, k, kWave);
+  return e / s;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void mixture_gate_fwd_kernel(const float* __restrict__ a2, const float* __restrict__ logits,
+                                                               float* __restrict__ m, float* __restrict__ p, int64_t B, int K,
+                                                               int r) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * kMixRowsPerBlock + (threadIdx.x >> 6);
+  if (b >= B) return;  // the whole wave
+  const float p_mine = mix_softmax(logits + b * K, K, lane);
+  if (lane < K) p[b * K + lane] = p_mine;
+  const int W = K * r;
+  float* __restrict__ mrow = m + b * W;
+  constexpr int E = VEC ? 4 : 1;  // elements per lane and round
+  // the trip count is the wave's: every lane takes part in the shuffle
+  for (int base = 0; base < W; base += 64 * E) {
+    const int i = base + lane * E;
+    const bool in = i < W;
+    const int k = in ? i / r : 0;  // VEC: r % 4 == 0, the four columns are one expert's
+    const float pk = __shfl(p_mine, k, kWave);
+    if (in) {
+      const float* src = a2 + (static_cast<int64_t>(k) * B + b) * r + (i - k * r);
+      if constexpr (VEC) {
+        const float4 a = ld4(src);
+        st4(mrow + i, make_float4(pk * relu1(a.x), pk * relu1(a.y), pk * relu1(a.z), pk * relu1(a.w)));
+      } else {
+        mrow[i] = pk * relu1(*src);
+      }
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void mixture_gate_bwd_kernel(const float* __restrict__ gm, const float* __restrict__ a2,
+                                                               const float* __restrict__ p, float* __restrict__ ga2,
+                                                               float* __restrict__ gl, int64_t B, int K, int r) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * kMixRowsPerBlock + (threadIdx.x >> 6);
+  if (b >= B) return;  // the whole wave
+  const float p_mine = lane < K ? p[b * K + lane] : 0.f;
+  float d_mine = 0.f;
+  int phase = 0;
+  for (int k = 0; k < K; ++k) {
+    const float pk = __shfl(p_mine, k, kWave);
+    const float* __restrict__ g = gm + (b * K + k) * r;
+    const int64_t o = (static_cast<int64_t>(k) * B + b) * r;
+    float part = 0.f;
+    for (int j = lane * 4; j < r; j += 256) {
+      if constexpr (VEC) {
+        const float4 gv = ld4(g + j);
+        const float4 av = ld4(a2 + o + j);
+        st4(ga2 + o + j, make_float4(av.x > 0.f ? pk * gv.x : 0.f, av.y > 0.f ? pk * gv.y : 0.f,
+                                     av.z > 0.f ? pk * gv.z : 0.f, av.w > 0.f ? pk * gv.w : 0.f));
+        part = dot4(gv, make_float4(relu1(av.x), relu1(av.y), relu1(av.z), relu1(av.w)), part);
+      } else {
+        const int end = min(j + 4, r);
+        for (int c = j; c < end; ++c) {
+          const float gv = g[c];
+          const float av = a2[o + c];
+          ga2[o + c] = av > 0.f ? pk * gv : 0.f;
+          part += gv * relu1(av);
+        }
+      }
+    }
+    const float d = row_sum<64>(part, nullptr, phase);
+    if (lane == k) d_mine = d;
+  }
+  float t = __shfl(p_mine, 0, kWave) * __shfl(d_mine, 0, kWave);
+  for (int k = 1; k < K; ++k) t += __shfl(p_mine, k, kWave) * __shfl(d_mine, k, kWave);
+  if (lane < K) gl[b * K + lane] = p_mine * (d_mine - t);
+}
+
+// The checks of both gate entries; *launch = false for an empty batch.  *vec: the data moves as float4.
+static int mix_gate_args(const char* name, std::initializer_list<const void*> tensors, int64_t B, int K, int r, bool* launch,
+                         bool* vec) {
+  *launch = false;
+  TBE_REQUIRE(K >= 2 && K <= kMixMaxK, "%s: K=%d beyond the limits 2 <= K <= %d", name, K, kMixMaxK);
+  TBE_REQUIRE(r >= 1 && r <= (1 << 26), "%s: r=%d must be in [1, 2^26]", name, r);
+  TBE_REQUIRE(B >= 0, "%s: B=%lld must be >= 0", name, (long long)B);
+  if (B == 0) return TBE_OK;
+  uintptr_t bits = 0;
+  for (const void* q : tensors) {
+    TBE_REQUIRE(q != nullptr, "%s: null pointer", name);
+    bits |= reinterpret_cast<uintptr_t>(q);
+  }
+  TBE_REQUIRE((bits & 3) == 0, "%s: tensors must be 4-B aligned", name);
+  TBE_REQUIRE((B + kMixRowsPerBlock - 1) / kMixRowsPerBlock < (1ll << 31), "%s: B=%lld too large", name, (long long)B);
+  *vec = (r & 3) == 0 && (bits & 15) == 0;
+  *launch = true;
+  return TBE_OK;
+}
+
 }  // namespace tbe
 
 using namespace tbe;
@@ -339,4 +458,36 @@ extern "C" int tbe_vector_cross_backward_f32(const float* grad_out, const float*
 #undef TBE_VEC_BWD
   TBE_CHECK_LAUNCH("tbe_vector_cross_backward_f32");
   return launch_colsum_partials("tbe_vector_cross_backward_f32", partial, nrb, 2 * L * N, grad_params, st);
+}
+
+extern "C" int tbe_mixture_gate_forward_f32(const float* a2, const float* logits, int64_t B, int32_t K, int32_t r, float* m,
+                                            float* p, void* stream) {
+  const char* name = "tbe_mixture_gate_forward_f32";
+  bool launch, vec;
+  const int rc = mix_gate_args(name, {a2, logits, m, p}, B, K, r, &launch, &vec);
+  if (rc != TBE_OK || !launch) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(static_cast<unsigned>((B + kMixRowsPerBlock - 1) / kMixRowsPerBlock));
+  if (vec)
+    hipLaunchKernelGGL(mixture_gate_fwd_kernel<true>, grid, dim3(256), 0, st, a2, logits, m, p, B, K, r);
+  else
+    hipLaunchKernelGGL(mixture_gate_fwd_kernel<false>, grid, dim3(256), 0, st, a2, logits, m, p, B, K, r);
+  TBE_CHECK_LAUNCH(name);
+  return TBE_OK;
+}
+
+extern "C" int tbe_mixture_gate_backward_f32(const float* grad_m, const float* a2, const float* p, int64_t B, int32_t K,
+                                             int32_t r, float* grad_a2, float* grad_logits, void* stream) {
+  const char* name = "tbe_mixture_gate_backward_f32";
+  bool launch, vec;
+  const int rc = mix_gate_args(name, {grad_m, a2, p, grad_a2, grad_logits}, B, K, r, &launch, &vec);
+  if (rc != TBE_OK || !launch) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(static_cast<unsigned>((B + kMixRowsPerBlock - 1) / kMixRowsPerBlock));
+  if (vec)
+    hipLaunchKernelGGL(mixture_gate_bwd_kernel<true>, grid, dim3(256), 0, st, grad_m, a2, p, grad_a2, grad_logits, B, K, r);
+  else
+    hipLaunchKernelGGL(mixture_gate_bwd_kernel<false>, grid, dim3(256), 0, st, grad_m, a2, p, grad_a2, grad_logits, B, K, r);
+  TBE_CHECK_LAUNCH(name);
+  return TBE_OK;
 }

@@ -29,6 +29,8 @@ _def.define("bce_with_logits(Tensor logits, Tensor labels) -> (Tensor, Tensor)")
 _def.define("cross_backward(Tensor grad_out, Tensor x0, Tensor t, Tensor(a!) acc, bool first) -> (Tensor, Tensor)")
 _def.define("vector_cross_forward(Tensor x0, Tensor weights, Tensor bias) -> (Tensor, Tensor)")
 _def.define("vector_cross_backward(Tensor grad_out, Tensor x0, Tensor s, Tensor weights, Tensor bias) -> (Tensor, Tensor)")
+_def.define("mixture_gate_forward(Tensor a2, Tensor logits) -> (Tensor, Tensor)")
+_def.define("mixture_gate_backward(Tensor grad_m, Tensor a2, Tensor p) -> (Tensor, Tensor)")
 _def.define("fm_forward(Tensor[] xs, bool want_cat) -> (Tensor, Tensor, Tensor)")
 _def.define("fm_backward(Tensor[] xs, Tensor grad_fm, Tensor row_sum, Tensor? grad_cat, bool[] wanted) -> Tensor[]")
 _impl = torch.library.Library("tbe_hip", "IMPL", "CUDA")
@@ -235,6 +237,41 @@ def _vector_cross_backward(grad_out, x0, s, weights, bias):
         check(lib.tbe_vector_cross_backward_f32(ptr(grad_out), ptr(x0), ptr(s), ptr(weights), ptr(bias), B, N, L, ptr(gin),
                                                 ptr(gp), ptr(ws), ws.numel(), stream_ptr(dev)), "tbe_vector_cross_backward_f32")
     return gin, gp
+
+
+def _mixture_gate_check(name, a2, bk, bk_name, *more):
+    """(device, K, B, r) of a gate op: contiguous float32 a2 [K, B, r] and a [B, K] tensor (logits or p)."""
+    dev = require_gpu(a2, bk, *more)
+    if (a2.dim() != 3 or bk.shape != (a2.shape[1], a2.shape[0])
+            or any(a.dtype != torch.float32 or not a.is_contiguous() for a in (a2, bk) + more)):
+        raise RuntimeError(f"{name}: need contiguous float32 a2 [K, B, r] and {bk_name} [B, K], got "
+                           f"{tuple(a2.shape)} and {tuple(bk.shape)}")
+    return (dev,) + tuple(a2.shape)
+
+
+def _mixture_gate_forward(a2, logits):
+    """(m [B, K r], p [B, K]) of LowRankMixtureCrossNet's folded layer: p = softmax(logits), m[b, k r + j] =
+    p[b, k] * relu(a2[k, b, j]) (csrc/crossnet.hip)."""
+    dev, K, B, r = _mixture_gate_check("mixture_gate_forward", a2, logits, "logits")
+    m = torch.empty((B, K * r), dtype=torch.float32, device=dev)
+    p = torch.empty_like(logits)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_mixture_gate_forward_f32(ptr(a2), ptr(logits), B, K, r, ptr(m), ptr(p), stream_ptr(dev)),
+              "tbe_mixture_gate_forward_f32")
+    return m, p
+
+
+def _mixture_gate_backward(grad_m, a2, p):
+    """(grad_a2 [K, B, r], grad_logits [B, K]): the mirror of mixture_gate_forward (csrc/crossnet.hip)."""
+    dev, K, B, r = _mixture_gate_check("mixture_gate_backward", a2, p, "p", grad_m)
+    if grad_m.shape != (B, K * r):
+        raise RuntimeError(f"mixture_gate_backward: grad_m {tuple(grad_m.shape)} does not fit a2 {tuple(a2.shape)}")
+    ga2 = torch.empty_like(a2)
+    gl = torch.empty_like(p)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_mixture_gate_backward_f32(ptr(grad_m), ptr(a2), ptr(p), B, K, r, ptr(ga2), ptr(gl),
+                                                        stream_ptr(dev)), "tbe_mixture_gate_backward_f32")
+    return ga2, gl
 
 
 def fm_segments(xs, wanted=None):
@@ -460,6 +497,8 @@ _impl.impl("relu_linear1_backward_partials", _relu_linear1_backward_partials)
 _impl.impl("cross_backward", _cross_backward)
 _impl.impl("vector_cross_forward", _vector_cross_forward)
 _impl.impl("vector_cross_backward", _vector_cross_backward)
+_impl.impl("mixture_gate_forward", _mixture_gate_forward)
+_impl.impl("mixture_gate_backward", _mixture_gate_backward)
 _impl.impl("fm_forward", _fm_forward)
 _impl.impl("fm_backward", _fm_backward)
 _impl.impl("multi_chunk_sum", _multi_chunk_sum)

@@ -1,3 +1,3 @@
 from .feature_processor import BaseFeatureProcessor, PositionWeightedModule  # noqa: F401
-from .crossnet import CrossNet, LowRankCrossNet, VectorCrossNet  # noqa: F401
+from .crossnet import CrossNet, LowRankCrossNet, LowRankMixtureCrossNet, VectorCrossNet  # noqa: F401
 from .deepfm import DeepFM, FactorizationMachine  # noqa: F401
