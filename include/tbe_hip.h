@@ -829,6 +829,33 @@ int tbe_mixture_gate_forward_f32(const float* a2, const float* logits, int64_t B
 int tbe_mixture_gate_backward_f32(const float* grad_m, const float* a2, const float* p, int64_t B, int32_t K, int32_t r,
                                   float* grad_a2, float* grad_logits, void* stream);
 
+/* SwishLayerNorm (torchrec/modules/activation.py:18-55):  out = y * sigmoid(LayerNorm(y)) over the N elements of every row of
+ * y [B, N], gamma, beta [N], one kernel each way with the row in registers.  Per row b:
+ *   forward   mean = (sum_c y[c]) / N;   var = (sum_c (y[c] - mean)^2) / N   (two-pass, never E[y^2] - mean^2)
+ *             rstd = 1 / sqrtf(var + eps);   n = (y - mean) * rstd;   z = n * gamma + beta;   s = 1 / (1 + expf(-z))
+ *             out = y * s;   stats[0, b] = mean, stats[1, b] = rstd   (stats [2, B]: all the backward needs besides y)
+ *   backward  n, z, s recomputed from y and stats in the forward's operation order;   g = grad_out
+ *             dz = ((g * y) * s) * (1 - s);   dn = dz * gamma;   c1 = (sum_c dn) / N;   c2 = (sum_c dn * n) / N
+ *             grad_y = g * s + rstd * ((dn - c1) - n * c2)
+ *             grad_params[0, :] = grad_gamma = sum_b dz * n;   grad_params[1, :] = grad_beta = sum_b dz
+ * forward: reads y once, writes out and stats.  backward: reads grad_out, y and stats once, writes grad_y and the row blocks'
+ * sums of both parameter gradients into `workspace` (tbe_swish_layernorm_backward_workspace_bytes(B, N) bytes), which one
+ * launch over 2 N columns finishes in fixed order.  Each product and each add is rounded on its own; no float atomics; row
+ * sums and column sums run in an order that depends on (B, N) only: two runs are bit-identical.  A constant row gives
+ * var = 0, n = 0, rstd = 1 / sqrtf(eps); z of large magnitude gives s = exactly 0 or 1; every result stays finite.
+ * Limits: fp32, contiguous, N a positive multiple of 4 and <= 4096, eps finite and >= 0; y, gamma, beta, out, grad_out,
+ * grad_y and workspace 16-B aligned (stats and grad_params 4 B); no two buffers overlapping.  Errors, before anything is
+ * launched: TBE_ERR_INVALID_ARGUMENT, with a message that names the limit, for a bad N or eps, a null or misaligned pointer,
+ * a short workspace, or more than 2^31 - 1 row blocks (of 128 rows for N <= 64, 32 for N <= 1024, 16 beyond).
+ * B == 0: the forward does nothing, the backward zeroes grad_params and touches nothing else. */
+size_t tbe_swish_layernorm_backward_workspace_bytes(int64_t B, int32_t N);
+int tbe_swish_layernorm_forward_f32(const float* y, const float* gamma, const float* beta, float eps, int64_t B, int32_t N,
+                                    float* out, float* stats, void* stream);
+int tbe_swish_layernorm_backward_f32(const float* grad_out, const float* y, const float* stats, const float* gamma,
+                                     const float* beta, int64_t B, int32_t N, float* grad_y,
+                                     float* grad_params /* [2, N]: gamma row, beta row */, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
 /* DeepFM interaction: the factorization-machine term and the deep branch's concatenated row in one pass each way.
  * Replaces torchrec/modules/deepfm.py:28-32 (_get_flatten_input: torch.cat of all inputs, once per branch), :209-215
  * (FactorizationMachine.forward: x * x, two row sums, a square) and what torchrec/models/deepfm.py:175-184 builds from

@@ -109,6 +109,24 @@ int colsum_first_stage(const char* name, bool one_pass, int64_t B, int N, std::i
   return TBE_OK;
 }
 
+// Sum of `v` over the TPR (16, 64 or 256) threads that share a row, the same value in every one of them.  Fixed order: xor
+// butterfly inside the wave (inside the row's 16 lanes for TPR = 16), then (TPR = 256) the four wave sums in wave order
+// through `red`; consecutive calls alternate `phase`, so one barrier per call is enough (a slot is rewritten only after the
+// barrier of the call in between).
+template <int TPR>
+__device__ __forceinline__ float row_sum(float v, float (*red)[4], int& phase) {
+#pragma unroll
+  for (int o = (TPR < kWave ? TPR : kWave) / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  if constexpr (TPR == 256) {
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) red[phase][wave] = v;
+    __syncthreads();
+    v = ((red[phase][0] + red[phase][1]) + red[phase][2]) + red[phase][3];
+    phase ^= 1;
+  }
+  return v;
+}
+
 // The second stage (mlp_epilogue.hip): out[c] = sum over the `row_blocks` rows of partial[row_blocks][N]; zeros for no rows.
 int launch_colsum_partials(const char* name, const float* partial, int64_t row_blocks, int N, float* out, hipStream_t st);
 

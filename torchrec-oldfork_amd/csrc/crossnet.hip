@@ -59,22 +59,7 @@ constexpr int kVecMaxL = 8;
 constexpr int kVecK = 4;            // float4 slots per thread: a row of up to TPR * 16 floats lives in registers
 constexpr int kVecRowsPerBlock = 128;  // rows per workgroup = rows per partial sum
 
-// Sum of `v` over the TPR threads that share a row, the same value in every one of them.  Fixed order: xor butterfly inside
-// the wave, then (TPR = 256) the four wave sums in wave order through `red`; consecutive calls alternate `phase`, so one
-// barrier per call is enough (a slot is rewritten only after the barrier of the call in between).
-template <int TPR>
-__device__ __forceinline__ float row_sum(float v, float (*red)[4], int& phase) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  if constexpr (TPR == 256) {
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[phase][wave] = v;
-    __syncthreads();
-    v = ((red[phase][0] + red[phase][1]) + red[phase][2]) + red[phase][3];
-    phase ^= 1;
-  }
-  return v;
-}
+// row_sum<TPR>: the sum of a value over the TPR threads that share a row, in a fixed order (colsum.hpp)
 
 __device__ __forceinline__ float dot4(const float4 a, const float4 b, float acc) {
   acc += a.x * b.x;

@@ -222,6 +222,12 @@ SIGNATURES = {
         ctypes.c_int, [c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
     "tbe_mixture_gate_backward_f32": (
         ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
+    "tbe_swish_layernorm_backward_workspace_bytes": (c_size, [c_i64, c_i32]),
+    "tbe_swish_layernorm_forward_f32": (
+        ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_float, c_i64, c_i32, c_void_p, c_void_p, c_void_p]),
+    "tbe_swish_layernorm_backward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "tbe_fm_forward_f32": (
         ctypes.c_int, [ctypes.POINTER(FmSegment), c_i32, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
     "tbe_fm_backward_f32": (

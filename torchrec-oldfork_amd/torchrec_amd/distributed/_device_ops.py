@@ -29,6 +29,8 @@ _def.define("bce_with_logits(Tensor logits, Tensor labels) -> (Tensor, Tensor)")
 _def.define("cross_backward(Tensor grad_out, Tensor x0, Tensor t, Tensor(a!) acc, bool first) -> (Tensor, Tensor)")
 _def.define("vector_cross_forward(Tensor x0, Tensor weights, Tensor bias) -> (Tensor, Tensor)")
 _def.define("vector_cross_backward(Tensor grad_out, Tensor x0, Tensor s, Tensor weights, Tensor bias) -> (Tensor, Tensor)")
+_def.define("swish_layernorm_forward(Tensor y, Tensor gamma, Tensor beta, float eps) -> (Tensor, Tensor)")
+_def.define("swish_layernorm_backward(Tensor grad_out, Tensor y, Tensor stats, Tensor gamma, Tensor beta) -> (Tensor, Tensor)")
 _def.define("mixture_gate_forward(Tensor a2, Tensor logits) -> (Tensor, Tensor)")
 _def.define("mixture_gate_backward(Tensor grad_m, Tensor a2, Tensor p) -> (Tensor, Tensor)")
 _def.define("fm_forward(Tensor[] xs, bool want_cat) -> (Tensor, Tensor, Tensor)")
@@ -237,6 +239,45 @@ def _vector_cross_backward(grad_out, x0, s, weights, bias):
         check(lib.tbe_vector_cross_backward_f32(ptr(grad_out), ptr(x0), ptr(s), ptr(weights), ptr(bias), B, N, L, ptr(gin),
                                                 ptr(gp), ptr(ws), ws.numel(), stream_ptr(dev)), "tbe_vector_cross_backward_f32")
     return gin, gp
+
+
+def _swish_layernorm_check(name, y, gamma, beta, *more):
+    dev = require_gpu(y, gamma, beta, *more)
+    if (y.dim() != 2 or gamma.shape != (y.shape[1],) or beta.shape != gamma.shape
+            or any(a.dtype != torch.float32 or not a.is_contiguous() for a in (y, gamma, beta) + more)):
+        raise RuntimeError(f"{name}: need contiguous float32 y [B, N], gamma [N], beta [N], got "
+                           f"{tuple(y.shape)}, {tuple(gamma.shape)}, {tuple(beta.shape)}")
+    return dev
+
+
+def _swish_layernorm_forward(y, gamma, beta, eps):
+    """(y * sigmoid(layer_norm(y)) [B, N], stats [2, B]: mean, rstd) in one kernel (csrc/swish_layernorm.hip)."""
+    dev = _swish_layernorm_check("swish_layernorm_forward", y, gamma, beta)
+    B, N = y.shape
+    out = torch.empty_like(y)
+    stats = torch.empty((2, B), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_swish_layernorm_forward_f32(ptr(y), ptr(gamma), ptr(beta), eps, B, N, ptr(out), ptr(stats),
+                                                          stream_ptr(dev)), "tbe_swish_layernorm_forward_f32")
+    return out, stats
+
+
+def _swish_layernorm_backward(grad_out, y, stats, gamma, beta):
+    """(input gradient [B, N], parameter gradients [2, N]: gamma row, beta row) (csrc/swish_layernorm.hip)."""
+    dev = _swish_layernorm_check("swish_layernorm_backward", y, gamma, beta, grad_out, stats)
+    B, N = y.shape
+    if grad_out.shape != y.shape or stats.shape != (2, B):
+        raise RuntimeError(f"swish_layernorm_backward: grad_out {tuple(grad_out.shape)} / stats {tuple(stats.shape)} do not "
+                           f"fit y {tuple(y.shape)}")
+    gy = torch.empty_like(y)
+    gp = torch.empty((2, N), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = workspace(lib.tbe_swish_layernorm_backward_workspace_bytes(B, N), dev)
+        check(lib.tbe_swish_layernorm_backward_f32(ptr(grad_out), ptr(y), ptr(stats), ptr(gamma), ptr(beta), B, N, ptr(gy),
+                                                   ptr(gp), ptr(ws), ws.numel(), stream_ptr(dev)),
+              "tbe_swish_layernorm_backward_f32")
+    return gy, gp
 
 
 def _mixture_gate_check(name, a2, bk, bk_name, *more):
@@ -497,6 +538,8 @@ _impl.impl("relu_linear1_backward_partials", _relu_linear1_backward_partials)
 _impl.impl("cross_backward", _cross_backward)
 _impl.impl("vector_cross_forward", _vector_cross_forward)
 _impl.impl("vector_cross_backward", _vector_cross_backward)
+_impl.impl("swish_layernorm_forward", _swish_layernorm_forward)
+_impl.impl("swish_layernorm_backward", _swish_layernorm_backward)
 _impl.impl("mixture_gate_forward", _mixture_gate_forward)
 _impl.impl("mixture_gate_backward", _mixture_gate_backward)
 _impl.impl("fm_forward", _fm_forward)

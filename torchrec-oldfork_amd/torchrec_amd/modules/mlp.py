@@ -1,11 +1,16 @@
 """Perceptron / MLP with the reference's module and parameter names
-(torchrec/modules/mlp.py:14-170) so state_dict keys match (`_mlp.{i}._linear.weight`)."""
+(torchrec/modules/mlp.py:14-170) so state_dict keys match (`_mlp.{i}._linear.weight`), and with its activation forms:
+"relu" / "sigmoid" / "swish_layernorm", a tensor function, a module instance (shared), a zero-argument module factory (called
+once per layer)."""
 import contextlib
 from typing import Callable, List, Optional, Tuple, Union
 
 import torch
 from torch import nn
 from torch.autograd import Variable
+
+from .activation import SwishLayerNorm
+from .utils import extract_module_or_tensor_callable
 
 
 class _DeferredWgrad:
@@ -334,8 +339,16 @@ class MLP(nn.Module):
         elif activation == "sigmoid":
             activation = torch.sigmoid
         sizes = [in_size] + list(layer_sizes)
+        if activation == "swish_layernorm":  # one module per layer (torchrec/modules/mlp.py:145-157)
+            def layer_activation(i):
+                return SwishLayerNorm(layer_sizes[i], device=device)
+        elif isinstance(activation, str):
+            raise ValueError(f"MLP supports the activation strings relu, sigmoid and swish_layernorm, got {activation!r}")
+        else:  # a zero-argument factory is called once per layer; torch.relu comes back as torch.relu (:131-143)
+            def layer_activation(i):
+                return extract_module_or_tensor_callable(activation)
         self._mlp = nn.Sequential(*[
-            Perceptron(sizes[i], sizes[i + 1], bias=bias, activation=activation, device=device)
+            Perceptron(sizes[i], sizes[i + 1], bias=bias, activation=layer_activation(i), device=device)
             for i in range(len(layer_sizes))])
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
