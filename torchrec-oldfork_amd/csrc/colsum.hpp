@@ -7,6 +7,7 @@
 //   second stage  colsum_partials_kernel (mlp_epilogue.hip): wave w of 4 adds the blocks w, w + 4, ...; the result is
 //                 ((a0 + a1) + a2) + a3.  A captured backward, and an eager one that defers (modules/mlp.py _EagerFinish),
 //                 finish all their layers with one multi_chunk_sum instead, which keeps this order (TBE_CHUNKS_WAVE_ORDER).
+// The kernels that keep a whole row in registers (rowreg.hpp: row sums, a first stage of their own) use this second stage.
 #pragma once
 #include <initializer_list>
 #include <type_traits>
@@ -91,13 +92,9 @@ int colsum_first_stage(const char* name, bool one_pass, int64_t B, int N, std::i
               (long long)B, one_pass ? ">= 0" : "> 0", N);
   *row_blocks = 0;
   if (B == 0) return TBE_OK;
-  TBE_REQUIRE(partial != nullptr, "%s: null pointer", name);
-  uintptr_t bits = reinterpret_cast<uintptr_t>(partial);
-  for (const void* p : tensors) {
-    TBE_REQUIRE(p != nullptr, "%s: null pointer", name);
-    bits |= reinterpret_cast<uintptr_t>(p);
-  }
-  TBE_REQUIRE((bits & 15) == 0, "%s: tensors must be 16-B aligned", name);
+  int rc = check_pointers(name, {partial});
+  if (rc == TBE_OK) rc = check_pointers(name, tensors);
+  if (rc != TBE_OK) return rc;
   const int64_t nrb = colsum_row_blocks(B, N);
   TBE_REQUIRE(nrb <= 65535, "%s: B=%lld too large (more than 65535 row blocks)", name, (long long)B);
   const size_t need = one_pass ? colsum_workspace_bytes(B, N) : static_cast<size_t>(nrb) * N * sizeof(float);
@@ -107,24 +104,6 @@ int colsum_first_stage(const char* name, bool one_pass, int64_t B, int N, std::i
   TBE_CHECK_LAUNCH(name);
   *row_blocks = nrb;
   return TBE_OK;
-}
-
-// Sum of `v` over the TPR (16, 64 or 256) threads that share a row, the same value in every one of them.  Fixed order: xor
-// butterfly inside the wave (inside the row's 16 lanes for TPR = 16), then (TPR = 256) the four wave sums in wave order
-// through `red`; consecutive calls alternate `phase`, so one barrier per call is enough (a slot is rewritten only after the
-// barrier of the call in between).
-template <int TPR>
-__device__ __forceinline__ float row_sum(float v, float (*red)[4], int& phase) {
-#pragma unroll
-  for (int o = (TPR < kWave ? TPR : kWave) / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  if constexpr (TPR == 256) {
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[phase][wave] = v;
-    __syncthreads();
-    v = ((red[phase][0] + red[phase][1]) + red[phase][2]) + red[phase][3];
-    phase ^= 1;
-  }
-  return v;
 }
 
 // The second stage (mlp_epilogue.hip): out[c] = sum over the `row_blocks` rows of partial[row_blocks][N]; zeros for no rows.

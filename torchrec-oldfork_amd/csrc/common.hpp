@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/tbe_hip.h"
@@ -31,6 +32,23 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// every pointer on the (mask + 1)-byte grid
+inline bool all_aligned(std::initializer_list<const void*> ptrs, uintptr_t mask) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & mask) == 0;
+}
+
+// The pointers of entry `name`: none null, `vec` (arrays that move as float4) 16-B aligned, `scalar` 4-B aligned.
+inline int check_pointers(const char* name, std::initializer_list<const void*> vec, std::initializer_list<const void*> scalar = {}) {
+  for (const auto& ptrs : {vec, scalar}) {
+    for (const void* p : ptrs) TBE_REQUIRE(p != nullptr, "%s: null pointer", name);
+  }
+  TBE_REQUIRE(all_aligned(vec, 15), "%s: tensors must be 16-B aligned", name);
+  TBE_REQUIRE(all_aligned(scalar, 3), "%s: tensors must be 4-B aligned", name);
+  return TBE_OK;
+}
 
 // profile.cpp: optional HIP-event bracketing of a launch (no-op unless tbe_profile_enable(1)).
 bool profile_enabled();

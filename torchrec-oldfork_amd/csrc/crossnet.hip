@@ -16,6 +16,9 @@
 // One forward kernel runs all L layers with the row in registers; one backward kernel recomputes every x_l from x_0, s and
 // the biases in the forward's own operation order (so bit for bit the forward's x_l) and produces the input gradient and
 // the row-block partial sums of all 2 L parameter gradients, which ONE second-stage launch over 2 L N columns finishes.
+// Geometry, slot addressing, the row sums, the finish of the column sums and the host side of the two entries are the
+// row-in-registers scheme of rowreg.hpp (orders pinned by tests/test_rowreg_order_gpu.py); the mixture gate takes its
+// row_sum<64> from there.
 //
 // LowRankMixtureCrossNet (:271-446) is LowRankCrossNet's layer of rank K r once its K experts are folded (include/tbe_hip.h);
 // what it adds is one narrow pass over [B, K r] between the GEMMs each way: mixture_gate_fwd_kernel / _bwd_kernel below.
@@ -24,7 +27,7 @@
 // restatement in numpy reproduces the element-wise results bit for bit.
 #include <algorithm>
 
-#include "colsum.hpp"
+#include "rowreg.hpp"
 
 namespace tbe {
 
@@ -53,13 +56,13 @@ __global__ __launch_bounds__(256) void cross_bwd_kernel(const float* __restrict_
   });
 }
 
-// ---- VectorCrossNet ---------------------------------------------------------------------------------------------------
-constexpr int kVecMaxN = 4096;
+// ---- VectorCrossNet: the row-in-registers scheme of rowreg.hpp; the arithmetic and the rule of N are here -----------------------
 constexpr int kVecMaxL = 8;
-constexpr int kVecK = 4;            // float4 slots per thread: a row of up to TPR * 16 floats lives in registers
 constexpr int kVecRowsPerBlock = 128;  // rows per workgroup = rows per partial sum
-
-// row_sum<TPR>: the sum of a value over the TPR threads that share a row, in a fixed order (colsum.hpp)
+// threads per row: 64 — one wave per row, four rows of the block in flight; 256 — the block per row
+static int vec_tpr(int N) { return N <= 64 * kRowSlots * 4 ? 64 : 256; }
+template <int TPR>
+using VecTile = RowTile<TPR, kVecRowsPerBlock>;
 
 __device__ __forceinline__ float dot4(const float4 a, const float4 b, float acc) {
   acc += a.x * b.x;
@@ -74,160 +77,87 @@ __device__ __forceinline__ float4 cross_step(const float4 x0, const float s, con
   return make_float4((x0.x * s + b.x) + x.x, (x0.y * s + b.y) + x.y, (x0.z * s + b.z) + x.z, (x0.w * s + b.w) + x.w);
 }
 
-// TPR threads per row (64: one wave per row, four rows of the block in flight; 256: the block per row).  Thread `lane` of a
-// row holds the float4 columns lane, lane + TPR, ... (kVecK of them).  grid = row blocks of kVecRowsPerBlock rows.
 template <int TPR>
 __global__ __launch_bounds__(256) void vector_cross_fwd_kernel(const float* __restrict__ x0g, const float* __restrict__ w,
                                                                const float* __restrict__ bias, float* __restrict__ out,
                                                                float* __restrict__ s_out, int64_t B, int N, int L) {
-  __shared__ float red[2][4];
-  int phase = 0;
-  constexpr int RP = 256 / TPR;  // rows in flight per block
-  const int lane = threadIdx.x % TPR;
-  const int sub = threadIdx.x / TPR;
-  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kVecRowsPerBlock;
-  const int64_t row1 = min(B, row0 + kVecRowsPerBlock);
-  // the trip count is the same for every thread of the block (TPR = 256: sub = 0 everywhere; TPR = 64 has no barrier)
-  for (int64_t r = row0 + sub; r < row1; r += RP) {
-    float4 x0[kVecK], x[kVecK];
+  VecTile<TPR> t(B, N);
+  t.for_rows([&](int64_t r) {
+    float4 x0[kRowSlots], x[kRowSlots];
+    t.load(x0g + r * N, x0);
 #pragma unroll
-    for (int k = 0; k < kVecK; ++k) {
-      const int col = (k * TPR + lane) * 4;
-      x0[k] = col < N ? ld4(x0g + r * N + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-      x[k] = x0[k];
-    }
+    for (int k = 0; k < kRowSlots; ++k) x[k] = x0[k];
     for (int l = 0; l < L; ++l) {
       float part = 0.f;
-#pragma unroll
-      for (int k = 0; k < kVecK; ++k) {
-        const int col = (k * TPR + lane) * 4;
-        if (col < N) part = dot4(x[k], ld4(w + l * N + col), part);
-      }
-      const float s = row_sum<TPR>(part, red, phase);
-      if (lane == 0) s_out[static_cast<int64_t>(l) * B + r] = s;
-#pragma unroll
-      for (int k = 0; k < kVecK; ++k) {
-        const int col = (k * TPR + lane) * 4;
-        if (col < N) x[k] = cross_step(x0[k], s, ld4(bias + l * N + col), x[k]);
-      }
+      t.for_slots([=, &part, &x](int k, int col) { part = dot4(x[k], ld4(w + l * N + col), part); });
+      const float s = t.sum(part);
+      if (t.lane == 0) s_out[static_cast<int64_t>(l) * B + r] = s;
+      t.for_slots([=, &x, &x0](int k, int col) { x[k] = cross_step(x0[k], s, ld4(bias + l * N + col), x[k]); });
     }
-#pragma unroll
-    for (int k = 0; k < kVecK; ++k) {
-      const int col = (k * TPR + lane) * 4;
-      if (col < N) st4(out + r * N + col, x[k]);
-    }
-  }
+    t.store(out + r * N, x);
+  });
 }
 
-// L is a template parameter, so that the 2 * L * kVecK float4 column sums of a thread stay in registers.
+// L is a template parameter, so that the 2 * L * kRowSlots float4 column sums of a thread stay in registers.
 // partial: [row blocks][2 L][N] — rows 0 .. L-1 the bias gradients, L .. 2L-1 the weight gradients of the row block.
 template <int TPR, int L>
 __global__ __launch_bounds__(256) void vector_cross_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ x0g,
                                                                const float* __restrict__ sg, const float* __restrict__ w,
                                                                const float* __restrict__ bias, float* __restrict__ gin,
                                                                float* __restrict__ partial, int64_t B, int N) {
-  __shared__ float red[2][4];
-  __shared__ float4 fin[4][64];
-  int phase = 0;
-  constexpr int RP = 256 / TPR;
-  const int lane = threadIdx.x % TPR;
-  const int sub = threadIdx.x / TPR;
-  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * kVecRowsPerBlock;
-  const int64_t row1 = min(B, row0 + kVecRowsPerBlock);
-  float4 sum_b[L][kVecK], sum_w[L][kVecK];
+  VecTile<TPR> t(B, N);
+  float4 sums[2 * L][kRowSlots];  // [l]: of G_l (bias), [L + l]: of d_l * x_l (weight)
 #pragma unroll
-  for (int l = 0; l < L; ++l) {
+  for (int i = 0; i < 2 * L; ++i) {
 #pragma unroll
-    for (int k = 0; k < kVecK; ++k) sum_b[l][k] = sum_w[l][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < kRowSlots; ++k) sums[i][k] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  for (int64_t r = row0 + sub; r < row1; r += RP) {
-    float4 x0[kVecK], g[kVecK], acc[kVecK];
+  t.for_rows([&](int64_t r) {
+    float4 x0[kRowSlots], g[kRowSlots], acc[kRowSlots];
+    t.load(x0g + r * N, x0);
+    t.load(gout + r * N, g);
 #pragma unroll
-    for (int k = 0; k < kVecK; ++k) {
-      const int col = (k * TPR + lane) * 4;
-      const bool in = col < N;
-      x0[k] = in ? ld4(x0g + r * N + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-      g[k] = in ? ld4(gout + r * N + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-      acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    for (int k = 0; k < kRowSlots; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     float s[L];
 #pragma unroll
     for (int l = 0; l < L; ++l) s[l] = sg[static_cast<int64_t>(l) * B + r];
 #pragma unroll
     for (int l = L - 1; l >= 0; --l) {
       // x_l, recomputed in the forward's order
-      float4 x[kVecK];
+      float4 x[kRowSlots];
 #pragma unroll
-      for (int k = 0; k < kVecK; ++k) x[k] = x0[k];
+      for (int k = 0; k < kRowSlots; ++k) x[k] = x0[k];
 #pragma unroll
       for (int j = 0; j < l; ++j) {
-#pragma unroll
-        for (int k = 0; k < kVecK; ++k) {
-          const int col = (k * TPR + lane) * 4;
-          if (col < N) x[k] = cross_step(x0[k], s[j], ld4(bias + j * N + col), x[k]);
-        }
+        t.for_slots([=, &x, &x0, &s](int k, int col) { x[k] = cross_step(x0[k], s[j], ld4(bias + j * N + col), x[k]); });
       }
       float part = 0.f;
 #pragma unroll
-      for (int k = 0; k < kVecK; ++k) part = dot4(g[k], x0[k], part);  // columns beyond N hold zeros
-      const float d = row_sum<TPR>(part, red, phase);
-#pragma unroll
-      for (int k = 0; k < kVecK; ++k) {
-        const int col = (k * TPR + lane) * 4;
-        if (col < N) {
-          const float4 gk = g[k];
-          const float sl = s[l];
-          add4(acc[k], make_float4(gk.x * sl, gk.y * sl, gk.z * sl, gk.w * sl));
-          add4(sum_b[l][k], gk);
-          add4(sum_w[l][k], make_float4(d * x[k].x, d * x[k].y, d * x[k].z, d * x[k].w));
-          const float4 wl = ld4(w + l * N + col);
-          add4(g[k], make_float4(d * wl.x, d * wl.y, d * wl.z, d * wl.w));
-        }
-      }
+      for (int k = 0; k < kRowSlots; ++k) part = dot4(g[k], x0[k], part);  // columns beyond N hold zeros
+      const float d = t.sum(part);
+      t.for_slots([=, &g, &s, &acc, &sums, &x](int k, int col) {
+        const float4 gk = g[k];
+        const float sl = s[l];
+        add4(acc[k], make_float4(gk.x * sl, gk.y * sl, gk.z * sl, gk.w * sl));
+        add4(sums[l][k], gk);
+        add4(sums[L + l][k], make_float4(d * x[k].x, d * x[k].y, d * x[k].z, d * x[k].w));
+        const float4 wl = ld4(w + l * N + col);
+        add4(g[k], make_float4(d * wl.x, d * wl.y, d * wl.z, d * wl.w));
+      });
     }
-#pragma unroll
-    for (int k = 0; k < kVecK; ++k) {
-      const int col = (k * TPR + lane) * 4;
-      if (col < N) {
-        add4(g[k], acc[k]);
-        st4(gin + r * N + col, g[k]);
-      }
-    }
-  }
-  // the row block's column sums: TPR = 256 — every thread owns its columns alone; TPR = 64 — the four waves hold the sums of
-  // rows sub, sub + 4, ... and are added in wave order through LDS
-  float* pb = partial + static_cast<int64_t>(blockIdx.x) * 2 * L * N;
-#pragma unroll
-  for (int l = 0; l < L; ++l) {
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-#pragma unroll
-      for (int k = 0; k < kVecK; ++k) {
-        const int col = (k * TPR + lane) * 4;
-        float4 v = half == 0 ? sum_b[l][k] : sum_w[l][k];
-        float* dst = pb + static_cast<int64_t>(half * L + l) * N + col;
-        if constexpr (TPR == 256) {
-          if (col < N) st4(dst, v);
-        } else {
-          if (k * TPR * 4 < N) {  // block-uniform: some lane of this slot holds a column
-            __syncthreads();      // the previous round's reads of `fin` are done
-            fin[sub][lane] = v;
-            __syncthreads();
-            if (sub == 0 && col < N) {
-              v = fin[0][lane];
-              add4(v, fin[1][lane]);
-              add4(v, fin[2][lane]);
-              add4(v, fin[3][lane]);
-              st4(dst, v);
-            }
-          }
-        }
-      }
-    }
-  }
+    t.for_slots([&](int k, int) { add4(g[k], acc[k]); });
+    t.store(gin + r * N, g);
+  });
+  t.finish(sums, partial);
 }
 
-static int64_t vec_row_blocks(int64_t B) { return (B + kVecRowsPerBlock - 1) / kVecRowsPerBlock; }
+// The limits shared by the two entries; *nrb = row blocks (grid size).
+static int vec_limits(const char* name, int64_t B, int N, int L, int64_t* nrb) {
+  TBE_REQUIRE(L >= 1 && L <= kVecMaxL, "%s: L=%d must be in [1, %d] (the limits: N <= %d, L <= %d)", name, L, kVecMaxL, kRowMaxN,
+              kVecMaxL);
+  static_assert(kVecMaxL == 8, "the message below names it");
+  return rowreg_limits(name, B, N, kVecRowsPerBlock, nrb, ", L <= 8");
+}
 
 // ---- LowRankMixtureCrossNet: the narrow pass between the folded GEMMs -----------------------------------------------------
 // a2, grad_a2 [K, B, r] (what the batched GEMM over experts writes / reads); m, grad_m [B, K r] (what the Ucat GEMMs read /
@@ -294,7 +224,6 @@ __global__ __launch_bounds__(256) void mixture_gate_bwd_kernel(const float* __re
   if (b >= B) return;  // the whole wave
   const float p_mine = lane < K ? p[b * K + lane] : 0.f;
   float d_mine = 0.f;
-  int phase = 0;
   for (int k = 0; k < K; ++k) {
     const float pk = __shfl(p_mine, k, kWave);
     const float* __restrict__ g = gm + (b * K + k) * r;
@@ -317,7 +246,7 @@ __global__ __launch_bounds__(256) void mixture_gate_bwd_kernel(const float* __re
         }
       }
     }
-    const float d = row_sum<64>(part, nullptr, phase);
+    const float d = row_sum<64>(part);
     if (lane == k) d_mine = d;
   }
   float t = __shfl(p_mine, 0, kWave) * __shfl(d_mine, 0, kWave);
@@ -333,14 +262,10 @@ static int mix_gate_args(const char* name, std::initializer_list<const void*> te
   TBE_REQUIRE(r >= 1 && r <= (1 << 26), "%s: r=%d must be in [1, 2^26]", name, r);
   TBE_REQUIRE(B >= 0, "%s: B=%lld must be >= 0", name, (long long)B);
   if (B == 0) return TBE_OK;
-  uintptr_t bits = 0;
-  for (const void* q : tensors) {
-    TBE_REQUIRE(q != nullptr, "%s: null pointer", name);
-    bits |= reinterpret_cast<uintptr_t>(q);
-  }
-  TBE_REQUIRE((bits & 3) == 0, "%s: tensors must be 4-B aligned", name);
+  const int rc = check_pointers(name, {}, tensors);
+  if (rc != TBE_OK) return rc;
   TBE_REQUIRE((B + kMixRowsPerBlock - 1) / kMixRowsPerBlock < (1ll << 31), "%s: B=%lld too large", name, (long long)B);
-  *vec = (r & 3) == 0 && (bits & 15) == 0;
+  *vec = (r & 3) == 0 && all_aligned(tensors, 15);
   *launch = true;
   return TBE_OK;
 }
@@ -368,81 +293,41 @@ extern "C" int tbe_cross_backward_f32(const float* grad_out, const float* x0, co
   return rc != TBE_OK ? rc : launch_colsum_partials(name, partial, nrb, N, bias_grad, st);
 }
 
-#define TBE_VEC_CROSS_LIMITS(what)                                                                                      \
-  TBE_REQUIRE(B >= 0 && N > 0 && (N & 3) == 0 && L >= 1, what ": N=%d must be a positive multiple of 4 and L=%d >= 1", N, L); \
-  TBE_REQUIRE(N <= kVecMaxN && L <= kVecMaxL, what ": N=%d, L=%d beyond the limits N <= %d, L <= %d", N, L, kVecMaxN, kVecMaxL)
-
 extern "C" size_t tbe_vector_cross_backward_workspace_bytes(int64_t B, int32_t N, int32_t L) {
-  if (B <= 0 || N <= 0 || L <= 0) return 256;
-  return align_up(static_cast<size_t>(vec_row_blocks(B)) * 2 * L * N * sizeof(float), 256);
+  return rowreg_workspace_bytes(B <= 0 ? 0 : (B + kVecRowsPerBlock - 1) / kVecRowsPerBlock, 2 * L, N);
 }
 
 extern "C" int tbe_vector_cross_forward_f32(const float* x0, const float* weights, const float* bias, int64_t B, int32_t N,
                                             int32_t L, float* out, float* s, void* stream) {
-  TBE_VEC_CROSS_LIMITS("tbe_vector_cross_forward_f32");
-  if (B == 0) return TBE_OK;
-  TBE_REQUIRE(x0 && weights && bias && out && s, "tbe_vector_cross_forward_f32: null pointer");
-  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(bias) |
-                reinterpret_cast<uintptr_t>(out)) & 15) == 0 && (reinterpret_cast<uintptr_t>(s) & 3) == 0,
-              "tbe_vector_cross_forward_f32: tensors must be 16-B aligned");
-  const int64_t nrb = vec_row_blocks(B);
-  TBE_REQUIRE(nrb < (1ll << 31), "tbe_vector_cross_forward_f32: B=%lld too large", (long long)B);
+  const char* name = "tbe_vector_cross_forward_f32";
+  int64_t nrb;
+  const int rc = vec_limits(name, B, N, L, &nrb);
+  if (rc != TBE_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (N <= 64 * kVecK * 4)
-    hipLaunchKernelGGL(vector_cross_fwd_kernel<64>, dim3(static_cast<unsigned>(nrb)), dim3(256), 0, st, x0, weights, bias, out, s,
-                       B, N, L);
-  else
-    hipLaunchKernelGGL(vector_cross_fwd_kernel<256>, dim3(static_cast<unsigned>(nrb)), dim3(256), 0, st, x0, weights, bias, out,
-                       s, B, N, L);
-  TBE_CHECK_LAUNCH("tbe_vector_cross_forward_f32");
-  return TBE_OK;
+  return rowreg_run(name, B, N, nrb, {x0, weights, bias, out}, {s}, nullptr, st, [&](dim3 grid) {
+    dispatch_value<64, 256>(vec_tpr(N), [&](auto t) {
+      hipLaunchKernelGGL(vector_cross_fwd_kernel<decltype(t)::value>, grid, dim3(256), 0, st, x0, weights, bias, out, s, B, N, L);
+    });
+  });
 }
 
 extern "C" int tbe_vector_cross_backward_f32(const float* grad_out, const float* x0, const float* s, const float* weights,
                                              const float* bias, int64_t B, int32_t N, int32_t L, float* grad_in,
                                              float* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
-  TBE_VEC_CROSS_LIMITS("tbe_vector_cross_backward_f32");
-  TBE_REQUIRE(grad_params != nullptr, "tbe_vector_cross_backward_f32: null grad_params");
+  const char* name = "tbe_vector_cross_backward_f32";
+  int64_t nrb;
+  const int rc = vec_limits(name, B, N, L, &nrb);
+  if (rc != TBE_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (B == 0) {
-    if (hipMemsetAsync(grad_params, 0, sizeof(float) * 2 * L * N, st) != hipSuccess) return TBE_ERR_LAUNCH;
-    return TBE_OK;
-  }
-  TBE_REQUIRE(grad_out && x0 && s && weights && bias && grad_in && workspace, "tbe_vector_cross_backward_f32: null pointer");
-  TBE_REQUIRE(((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(weights) |
-                reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(grad_in) |
-                reinterpret_cast<uintptr_t>(workspace)) & 15) == 0 &&
-                  ((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(grad_params)) & 3) == 0,
-              "tbe_vector_cross_backward_f32: tensors must be 16-B aligned");
-  TBE_REQUIRE(workspace_bytes >= tbe_vector_cross_backward_workspace_bytes(B, N, L),
-              "tbe_vector_cross_backward_f32: workspace too small");
-  const int64_t nrb = vec_row_blocks(B);
-  TBE_REQUIRE(nrb < (1ll << 31), "tbe_vector_cross_backward_f32: B=%lld too large", (long long)B);
-  float* partial = static_cast<float*>(workspace);
-  const dim3 grid(static_cast<unsigned>(nrb));
-  const bool narrow = N <= 64 * kVecK * 4;
-#define TBE_VEC_BWD(LL)                                                                                                    \
-  case LL:                                                                                                                 \
-    if (narrow)                                                                                                            \
-      hipLaunchKernelGGL((vector_cross_bwd_kernel<64, LL>), grid, dim3(256), 0, st, grad_out, x0, s, weights, bias, grad_in, \
-                         partial, B, N);                                                                                   \
-    else                                                                                                                   \
-      hipLaunchKernelGGL((vector_cross_bwd_kernel<256, LL>), grid, dim3(256), 0, st, grad_out, x0, s, weights, bias, grad_in, \
-                         partial, B, N);                                                                                   \
-    break
-  switch (L) {
-    TBE_VEC_BWD(1);
-    TBE_VEC_BWD(2);
-    TBE_VEC_BWD(3);
-    TBE_VEC_BWD(4);
-    TBE_VEC_BWD(5);
-    TBE_VEC_BWD(6);
-    TBE_VEC_BWD(7);
-    TBE_VEC_BWD(8);
-  }
-#undef TBE_VEC_BWD
-  TBE_CHECK_LAUNCH("tbe_vector_cross_backward_f32");
-  return launch_colsum_partials("tbe_vector_cross_backward_f32", partial, nrb, 2 * L * N, grad_params, st);
+  const RowColSums cs{2 * L, grad_params, workspace, workspace_bytes};
+  return rowreg_run(name, B, N, nrb, {grad_out, x0, weights, bias, grad_in}, {s}, &cs, st, [&](dim3 grid) {
+    dispatch_value<64, 256>(vec_tpr(N), [&](auto t) {
+      dispatch_value<1, 2, 3, 4, 5, 6, 7, 8>(L, [&](auto l) {  // 1 ... kVecMaxL
+        hipLaunchKernelGGL((vector_cross_bwd_kernel<decltype(t)::value, decltype(l)::value>), grid, dim3(256), 0, st, grad_out, x0,
+                           s, weights, bias, grad_in, static_cast<float*>(workspace), B, N);
+      });
+    });
+  });
 }
 
 extern "C" int tbe_mixture_gate_forward_f32(const float* a2, const float* logits, int64_t B, int32_t K, int32_t r, float* m,

@@ -19,7 +19,7 @@
 // four 4-byte accesses on the scalar path — the same elements in the same lane in the same order, so the path a segment
 // takes changes no result bit, and the order depends on (N, segment geometry) only.  No atomics; every product and add is
 // rounded on its own (-ffp-contract=off).
-#include "common.hpp"
+#include "rowreg.hpp"  // row_sum<G>: the fixed xor butterfly over the G lanes of a row
 
 namespace tbe {
 
@@ -39,13 +39,6 @@ struct FmArgs {
   int32_t nseg;
   int32_t N;
 };
-
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
 
 // block = 256 threads = 256 / G rows; grid.x = row blocks
 template <int G, bool CAT>
@@ -93,8 +86,8 @@ __global__ __launch_bounds__(256) void fm_fwd_kernel(const FmArgs a, int64_t B, 
       }
     }
   }
-  s = group_sum<G>(s);
-  q = group_sum<G>(q);
+  s = tbe::row_sum<G>(s);  // qualified: the parameter `row_sum` hides the function
+  q = tbe::row_sum<G>(q);
   if (live && lane == 0) {
     row_sum[r] = s;
     fm[r * fm_stride] = (s * s - q) * 0.5f;  // the reference's order: square of sum - sum of squares, then * 0.5

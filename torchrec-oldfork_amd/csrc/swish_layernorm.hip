@@ -17,30 +17,23 @@
 // A constant row has var = 0, n = 0, rstd = 1 / sqrtf(eps); |z| beyond expf's range gives s = exactly 0 or 1 (1 / inf = 0,
 // 1 / (1 + 0) = 1) and no inf * 0 anywhere, since s itself is finite.
 //
-// Threads per row (TPR) by N — thread `lane` of a row holds the float4 columns lane, lane + TPR, ... (at most kSlnK = 4):
+// The row-in-registers scheme of rowreg.hpp (geometry, slot addressing, row sums, the finish of the column sums, the host side
+// of an entry); this file holds the arithmetic and the rule of N.  Threads per row (TPR) and rows per workgroup by N:
 //   N <= 64           TPR = 16:  16 rows of the workgroup in flight, one float4 slot per thread, 128 rows per workgroup
 //   64 < N <= 1024    TPR = 64:  a wave per row, four rows in flight, 1 ... 4 slots,             32 rows per workgroup
 //   1024 < N <= 4096  TPR = 256: the workgroup per row, 2 ... 4 slots,                           16 rows per workgroup
-// Row sums: every thread adds its own elements from 0.0f in slot order (x, y, z, w inside a float4), then row_sum<TPR>
-// (colsum.hpp): xor butterfly, then wave order through LDS.  Column sums (the parameter gradients): thread (sub, lane) adds
-// the rows sub, sub + 256 / TPR, ... of its row block from 0.0f; the block's sum is that of sub = 0, 1, ... left to right
-// (LDS); partial[row block][2][N] (gamma row, beta row) is finished by ONE colsum_partials launch over 2 N columns
-// (colsum.hpp, second stage).  No float atomics; every order depends on (B, N) only, so two runs are bit-identical.
+// The column sums (the parameter gradients) go to partial[row block][2][N]: gamma row, beta row.  Every order depends on
+// (B, N) only and is pinned (tests/test_rowreg_order_gpu.py), so two runs are bit-identical.
 #include <cmath>
 
-#include "colsum.hpp"
+#include "rowreg.hpp"
 
 namespace tbe {
 
-constexpr int kSlnMaxN = 4096;
-constexpr int kSlnK = 4;  // float4 slots per thread
-
 __host__ __device__ constexpr int sln_rows_per_block(int tpr) { return tpr == 16 ? 128 : tpr == 64 ? 32 : 16; }
-static int sln_tpr(int N) { return N <= 16 * 4 ? 16 : N <= 64 * kSlnK * 4 ? 64 : 256; }
-static int64_t sln_row_blocks(int64_t B, int N) {
-  const int rpb = sln_rows_per_block(sln_tpr(N));
-  return (B + rpb - 1) / rpb;
-}
+static int sln_tpr(int N) { return N <= 16 * 4 ? 16 : N <= 64 * kRowSlots * 4 ? 64 : 256; }
+template <int TPR>
+using SlnTile = RowTile<TPR, sln_rows_per_block(TPR)>;
 
 __device__ __forceinline__ float sum4(const float4 a, float acc) {
   acc += a.x;
@@ -60,63 +53,41 @@ __device__ __forceinline__ void norm_sigmoid(const float4 y, const float mean, c
                   sigmoid1(n.w * ga.w + be.w));
 }
 
-// grid = row blocks of sln_rows_per_block(TPR) rows.  stats: [2, B] — mean, then rstd.
+// stats: [2, B] — mean, then rstd.
 template <int TPR>
 __global__ __launch_bounds__(256) void swish_layernorm_fwd_kernel(const float* __restrict__ yg, const float* __restrict__ gamma,
                                                                   const float* __restrict__ beta, float eps,
                                                                   float* __restrict__ out, float* __restrict__ stats,
                                                                   int64_t B, int N) {
-  __shared__ float red[2][4];
-  int phase = 0;
-  constexpr int RP = 256 / TPR;  // rows in flight per block
-  const int lane = threadIdx.x % TPR;
-  const int sub = threadIdx.x / TPR;
-  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * sln_rows_per_block(TPR);
-  const int64_t row1 = min(B, row0 + sln_rows_per_block(TPR));
+  SlnTile<TPR> t(B, N);
   const float fn = static_cast<float>(N);
-  float4 ga[kSlnK], be[kSlnK];
-#pragma unroll
-  for (int k = 0; k < kSlnK; ++k) {
-    const int col = (k * TPR + lane) * 4;
-    ga[k] = col < N ? ld4(gamma + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-    be[k] = col < N ? ld4(beta + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  // the trip count is the same for every thread that meets at a barrier (TPR = 256: sub = 0 everywhere; else no barrier)
-  for (int64_t r = row0 + sub; r < row1; r += RP) {
-    float4 y[kSlnK];
+  float4 ga[kRowSlots], be[kRowSlots];
+  t.load(gamma, ga);
+  t.load(beta, be);
+  t.for_rows([&](int64_t r) {
+    float4 y[kRowSlots];
+    t.load(yg + r * N, y);
     float part = 0.f;
 #pragma unroll
-    for (int k = 0; k < kSlnK; ++k) {
-      const int col = (k * TPR + lane) * 4;
-      y[k] = col < N ? ld4(yg + r * N + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-      part = sum4(y[k], part);  // columns beyond N hold zeros
-    }
-    const float mean = row_sum<TPR>(part, red, phase) / fn;
+    for (int k = 0; k < kRowSlots; ++k) part = sum4(y[k], part);  // columns beyond N hold zeros
+    const float mean = t.sum(part) / fn;
     part = 0.f;
-#pragma unroll
-    for (int k = 0; k < kSlnK; ++k) {
-      const int col = (k * TPR + lane) * 4;
-      if (col < N) {
-        const float4 d = make_float4(y[k].x - mean, y[k].y - mean, y[k].z - mean, y[k].w - mean);
-        part = sum4(make_float4(d.x * d.x, d.y * d.y, d.z * d.z, d.w * d.w), part);
-      }
-    }
-    const float var = row_sum<TPR>(part, red, phase) / fn;
+    t.for_slots([&](int k, int) {
+      const float4 d = make_float4(y[k].x - mean, y[k].y - mean, y[k].z - mean, y[k].w - mean);
+      part = sum4(make_float4(d.x * d.x, d.y * d.y, d.z * d.z, d.w * d.w), part);
+    });
+    const float var = t.sum(part) / fn;
     const float rstd = 1.f / sqrtf(var + eps);
-    if (lane == 0) {
+    if (t.lane == 0) {
       stats[r] = mean;
       stats[B + r] = rstd;
     }
-#pragma unroll
-    for (int k = 0; k < kSlnK; ++k) {
-      const int col = (k * TPR + lane) * 4;
-      if (col < N) {
-        float4 n, s;
-        norm_sigmoid(y[k], mean, rstd, ga[k], be[k], n, s);
-        st4(out + r * N + col, make_float4(y[k].x * s.x, y[k].y * s.y, y[k].z * s.z, y[k].w * s.w));
-      }
-    }
-  }
+    t.for_slots([=, &y, &ga, &be](int k, int col) {
+      float4 n, s;
+      norm_sigmoid(y[k], mean, rstd, ga[k], be[k], n, s);
+      st4(out + r * N + col, make_float4(y[k].x * s.x, y[k].y * s.y, y[k].z * s.z, y[k].w * s.w));
+    });
+  });
 }
 
 // partial: [row blocks][2][N] — row 0 the gamma gradient, row 1 the beta gradient of the row block.
@@ -126,102 +97,54 @@ __global__ __launch_bounds__(256) void swish_layernorm_bwd_kernel(const float* _
                                                                   const float* __restrict__ gamma,
                                                                   const float* __restrict__ beta, float* __restrict__ gin,
                                                                   float* __restrict__ partial, int64_t B, int N) {
-  __shared__ float red[2][4];
-  __shared__ float4 fin[256];  // [RP][TPR]
-  int phase = 0;
-  constexpr int RP = 256 / TPR;
-  const int lane = threadIdx.x % TPR;
-  const int sub = threadIdx.x / TPR;
-  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * sln_rows_per_block(TPR);
-  const int64_t row1 = min(B, row0 + sln_rows_per_block(TPR));
+  SlnTile<TPR> t(B, N);
   const float fn = static_cast<float>(N);
-  float4 ga[kSlnK], be[kSlnK], sum_g[kSlnK], sum_b[kSlnK];
+  float4 ga[kRowSlots], be[kRowSlots], sums[2][kRowSlots];  // sums: of dz * n (gamma), of dz (beta)
+  t.load(gamma, ga);
+  t.load(beta, be);
 #pragma unroll
-  for (int k = 0; k < kSlnK; ++k) {
-    const int col = (k * TPR + lane) * 4;
-    ga[k] = col < N ? ld4(gamma + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-    be[k] = col < N ? ld4(beta + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-    sum_g[k] = sum_b[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  for (int64_t r = row0 + sub; r < row1; r += RP) {
+  for (int k = 0; k < kRowSlots; ++k) sums[0][k] = sums[1][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  t.for_rows([&](int64_t r) {
     const float mean = stats[r];
     const float rstd = stats[B + r];
-    float4 n[kSlnK], dn[kSlnK], gs[kSlnK];
+    float4 n[kRowSlots], dn[kRowSlots], gs[kRowSlots];
     float p1 = 0.f, p2 = 0.f;
+    // a plain loop over the slots, not t.for_slots: with these statements in a lambda the compiler schedules the body otherwise
+    // and the TPR = 256 kernel measured 5 ... 8 % slower (N = 2048, 4096)
 #pragma unroll
-    for (int k = 0; k < kSlnK; ++k) {
-      const int col = (k * TPR + lane) * 4;
+    for (int k = 0; k < kRowSlots; ++k) {
       n[k] = dn[k] = gs[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (col < N) {
-        const float4 y = ld4(yg + r * N + col);
-        const float4 g = ld4(gout + r * N + col);
+      if (t.has(k)) {
+        const float4 y = ld4(yg + r * N + t.col(k));
+        const float4 g = ld4(gout + r * N + t.col(k));
         float4 s;
         norm_sigmoid(y, mean, rstd, ga[k], be[k], n[k], s);
         const float4 dz = make_float4(((g.x * y.x) * s.x) * (1.f - s.x), ((g.y * y.y) * s.y) * (1.f - s.y),
                                       ((g.z * y.z) * s.z) * (1.f - s.z), ((g.w * y.w) * s.w) * (1.f - s.w));
         gs[k] = make_float4(g.x * s.x, g.y * s.y, g.z * s.z, g.w * s.w);
         dn[k] = make_float4(dz.x * ga[k].x, dz.y * ga[k].y, dz.z * ga[k].z, dz.w * ga[k].w);
-        add4(sum_g[k], make_float4(dz.x * n[k].x, dz.y * n[k].y, dz.z * n[k].z, dz.w * n[k].w));
-        add4(sum_b[k], dz);
+        add4(sums[0][k], make_float4(dz.x * n[k].x, dz.y * n[k].y, dz.z * n[k].z, dz.w * n[k].w));
+        add4(sums[1][k], dz);
       }
       p1 = sum4(dn[k], p1);  // columns beyond N hold zeros
       p2 = sum4(make_float4(dn[k].x * n[k].x, dn[k].y * n[k].y, dn[k].z * n[k].z, dn[k].w * n[k].w), p2);
     }
-    const float c1 = row_sum<TPR>(p1, red, phase) / fn;
-    const float c2 = row_sum<TPR>(p2, red, phase) / fn;
-#pragma unroll
-    for (int k = 0; k < kSlnK; ++k) {
-      const int col = (k * TPR + lane) * 4;
-      if (col < N) {
-        const float4 d = dn[k], nn = n[k];
-        st4(gin + r * N + col,
-            make_float4(gs[k].x + rstd * ((d.x - c1) - nn.x * c2), gs[k].y + rstd * ((d.y - c1) - nn.y * c2),
-                        gs[k].z + rstd * ((d.z - c1) - nn.z * c2), gs[k].w + rstd * ((d.w - c1) - nn.w * c2)));
-      }
-    }
-  }
-  // the row block's column sums: TPR = 256 — every thread owns its columns alone; else the RP thread groups hold the sums of
-  // the rows sub, sub + RP, ... and are added in `sub` order through LDS
-  float* pb = partial + static_cast<int64_t>(blockIdx.x) * 2 * N;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-#pragma unroll
-    for (int k = 0; k < kSlnK; ++k) {
-      const int col = (k * TPR + lane) * 4;
-      float4 v = half == 0 ? sum_g[k] : sum_b[k];
-      float* dst = pb + static_cast<int64_t>(half) * N + col;
-      if constexpr (TPR == 256) {
-        if (col < N) st4(dst, v);
-      } else {
-        if (k * TPR * 4 < N) {  // block-uniform: some lane of this slot holds a column
-          __syncthreads();      // the previous round's reads of `fin` are done
-          fin[sub * TPR + lane] = v;
-          __syncthreads();
-          if (sub == 0 && col < N) {
-            v = fin[lane];
-#pragma unroll
-            for (int j = 1; j < RP; ++j) add4(v, fin[j * TPR + lane]);
-            st4(dst, v);
-          }
-        }
-      }
-    }
-  }
+    const float c1 = t.sum(p1) / fn;
+    const float c2 = t.sum(p2) / fn;
+    t.for_slots([=, &n, &dn, &gs](int k, int col) {
+      const float4 d = dn[k], nn = n[k];
+      st4(gin + r * N + col,
+          make_float4(gs[k].x + rstd * ((d.x - c1) - nn.x * c2), gs[k].y + rstd * ((d.y - c1) - nn.y * c2),
+                      gs[k].z + rstd * ((d.z - c1) - nn.z * c2), gs[k].w + rstd * ((d.w - c1) - nn.w * c2)));
+    });
+  });
+  t.finish(sums, partial);
 }
 
-// Limits shared by the two entries; *nrb = row blocks (grid size).
-static int sln_limits(const char* name, int64_t B, int N, int64_t* nrb) {
-  TBE_REQUIRE(B >= 0 && N > 0 && (N & 3) == 0, "%s: B=%lld must be >= 0 and N=%d a positive multiple of 4", name, (long long)B, N);
-  TBE_REQUIRE(N <= kSlnMaxN, "%s: N=%d beyond the limit N <= %d", name, N, kSlnMaxN);
-  *nrb = sln_row_blocks(B, N);
-  TBE_REQUIRE(*nrb < (1ll << 31), "%s: B=%lld too large (more than 2^31 - 1 row blocks)", name, (long long)B);
-  return TBE_OK;
-}
-
-static bool all_aligned(std::initializer_list<const void*> ptrs, uintptr_t mask) {
-  uintptr_t bits = 0;
-  for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
-  return (bits & mask) == 0;
+// The limits shared by the two entries; *tpr = threads per row, *nrb = row blocks (grid size).
+static int sln_limits(const char* name, int64_t B, int N, int* tpr, int64_t* nrb) {
+  *tpr = sln_tpr(N);
+  return rowreg_limits(name, B, N, sln_rows_per_block(*tpr), nrb);
 }
 
 }  // namespace tbe
@@ -229,66 +152,42 @@ static bool all_aligned(std::initializer_list<const void*> ptrs, uintptr_t mask)
 using namespace tbe;
 
 extern "C" size_t tbe_swish_layernorm_backward_workspace_bytes(int64_t B, int32_t N) {
-  if (B <= 0 || N <= 0) return 256;
-  return align_up(static_cast<size_t>(sln_row_blocks(B, N)) * 2 * N * sizeof(float), 256);
+  if (B <= 0) return rowreg_workspace_bytes(0, 2, N);
+  const int rpb = sln_rows_per_block(sln_tpr(N));
+  return rowreg_workspace_bytes((B + rpb - 1) / rpb, 2, N);
 }
 
 extern "C" int tbe_swish_layernorm_forward_f32(const float* y, const float* gamma, const float* beta, float eps, int64_t B,
                                                int32_t N, float* out, float* stats, void* stream) {
   const char* name = "tbe_swish_layernorm_forward_f32";
+  int tpr;
   int64_t nrb;
-  const int rc = sln_limits(name, B, N, &nrb);
+  const int rc = sln_limits(name, B, N, &tpr, &nrb);
   if (rc != TBE_OK) return rc;
   TBE_REQUIRE(std::isfinite(eps) && eps >= 0.f, "%s: eps=%g must be finite and >= 0", name, static_cast<double>(eps));
-  if (B == 0) return TBE_OK;
-  TBE_REQUIRE(y && gamma && beta && out && stats, "%s: null pointer", name);
-  TBE_REQUIRE(all_aligned({y, gamma, beta, out}, 15) && all_aligned({stats}, 3), "%s: tensors must be 16-B aligned (stats: 4 B)", name);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid(static_cast<unsigned>(nrb));
-  switch (sln_tpr(N)) {
-    case 16:
-      hipLaunchKernelGGL(swish_layernorm_fwd_kernel<16>, grid, dim3(256), 0, st, y, gamma, beta, eps, out, stats, B, N);
-      break;
-    case 64:
-      hipLaunchKernelGGL(swish_layernorm_fwd_kernel<64>, grid, dim3(256), 0, st, y, gamma, beta, eps, out, stats, B, N);
-      break;
-    default:
-      hipLaunchKernelGGL(swish_layernorm_fwd_kernel<256>, grid, dim3(256), 0, st, y, gamma, beta, eps, out, stats, B, N);
-  }
-  TBE_CHECK_LAUNCH(name);
-  return TBE_OK;
+  return rowreg_run(name, B, N, nrb, {y, gamma, beta, out}, {stats}, nullptr, st, [&](dim3 grid) {
+    dispatch_value<16, 64, 256>(tpr, [&](auto t) {
+      hipLaunchKernelGGL(swish_layernorm_fwd_kernel<decltype(t)::value>, grid, dim3(256), 0, st, y, gamma, beta, eps, out, stats,
+                         B, N);
+    });
+  });
 }
 
 extern "C" int tbe_swish_layernorm_backward_f32(const float* grad_out, const float* y, const float* stats, const float* gamma,
                                                 const float* beta, int64_t B, int32_t N, float* grad_y, float* grad_params,
                                                 void* workspace, size_t workspace_bytes, void* stream) {
   const char* name = "tbe_swish_layernorm_backward_f32";
+  int tpr;
   int64_t nrb;
-  const int rc = sln_limits(name, B, N, &nrb);
+  const int rc = sln_limits(name, B, N, &tpr, &nrb);
   if (rc != TBE_OK) return rc;
-  TBE_REQUIRE(grad_params != nullptr && all_aligned({grad_params}, 3), "%s: null or misaligned grad_params", name);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (B == 0) return hipMemsetAsync(grad_params, 0, sizeof(float) * 2 * N, st) == hipSuccess ? TBE_OK : TBE_ERR_LAUNCH;
-  TBE_REQUIRE(grad_out && y && stats && gamma && beta && grad_y && workspace, "%s: null pointer", name);
-  TBE_REQUIRE(all_aligned({grad_out, y, gamma, beta, grad_y, workspace}, 15) && all_aligned({stats}, 3),
-              "%s: tensors must be 16-B aligned (stats, grad_params: 4 B)", name);
-  const size_t need = tbe_swish_layernorm_backward_workspace_bytes(B, N);
-  TBE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu bytes, %zu needed)", name, workspace_bytes, need);
-  float* partial = static_cast<float*>(workspace);
-  const dim3 grid(static_cast<unsigned>(nrb));
-  switch (sln_tpr(N)) {
-    case 16:
-      hipLaunchKernelGGL(swish_layernorm_bwd_kernel<16>, grid, dim3(256), 0, st, grad_out, y, stats, gamma, beta, grad_y,
-                         partial, B, N);
-      break;
-    case 64:
-      hipLaunchKernelGGL(swish_layernorm_bwd_kernel<64>, grid, dim3(256), 0, st, grad_out, y, stats, gamma, beta, grad_y,
-                         partial, B, N);
-      break;
-    default:
-      hipLaunchKernelGGL(swish_layernorm_bwd_kernel<256>, grid, dim3(256), 0, st, grad_out, y, stats, gamma, beta, grad_y,
-                         partial, B, N);
-  }
-  TBE_CHECK_LAUNCH(name);
-  return launch_colsum_partials(name, partial, nrb, 2 * N, grad_params, st);
+  const RowColSums cs{2, grad_params, workspace, workspace_bytes};
+  return rowreg_run(name, B, N, nrb, {grad_out, y, gamma, beta, grad_y}, {stats}, &cs, st, [&](dim3 grid) {
+    dispatch_value<16, 64, 256>(tpr, [&](auto t) {
+      hipLaunchKernelGGL(swish_layernorm_bwd_kernel<decltype(t)::value>, grid, dim3(256), 0, st, grad_out, y, stats, gamma, beta,
+                         grad_y, static_cast<float*>(workspace), B, N);
+    });
+  });
 }
