@@ -941,6 +941,67 @@ int tbe_offsets_range(const int64_t* offsets, int64_t n, int64_t range_size, int
 int tbe_copy_rows(const void* src, int64_t src_rows, const int32_t* rows, int32_t n_rows,
                   int64_t row_bytes, void* dst, void* stream);
 
+/* Fused masked attention of BERT4Rec (examples/bert4rec/models/bert4rec.py:72-82 inside :152-170), float32, one launch
+ * each way.  Per sample b and head h:
+ *   S = Q K^T / sqrt(d);  S[:, j] = -1e9 where key j is not valid;  P = softmax_j(S);  P~ = dropout(P);  O = P~ V
+ * Layout: q, k, v are logically [B, L, H, d], read where they are: element (b, l, h, c) sits at
+ *   base + b * batch_stride + l * row_stride + h * d + c          (strides in floats, given per tensor, multiples of 4)
+ * out, grad_out, dq, dk, dv are contiguous [B, L, H * d]; lse is [B, H, L].  All float pointers 16-B aligned (lse: 4-B).
+ * Mask: key_valid is uint8 [B, L], non-zero = valid; NULL = every key valid.  Masked keys get the finite -1e9 (the
+ *   reference's masked_fill), so a sample with no valid key yields the uniform 1 / L over all L keys and O = mean of V.
+ *   In the backward dS is 0 at every masked key (masked_fill cuts the gradient): such a sample has dQ = 0, adds nothing to
+ *   dK, and its dV = P~^T dO.
+ * Softmax: the row maximum is subtracted.  The forward writes lse[b, h, i] = max_j S_ij + log sum_j exp(S_ij - max), the only
+ *   state kept; the backward recomputes P = exp(S - lse) (1 / L for a sample with no valid key, where -1e9 absorbs log L),
+ *   D_i = sum_j P~_ij (dO_i . V_j) = dO_i . O_i,  dP = keep * scale * (dO V^T),  dS = P * (dP - D_i) / sqrt(d),
+ *   dQ = dS K,  dK = dS^T Q,  dV = P~^T dO.  dq / dk / dv may each be NULL (not wanted: not computed).
+ *   No [L, L] tensor reaches global memory.
+ * Dropout, 0 <= p < 1: with uint32 arithmetic (wrapping), fmix32 the murmur3 finalizer
+ *       fmix32(x): x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16
+ *   and  c   = fmix32(fmix32(fmix32(fmix32(lo32(seed) ^ 0x9e3779b9) ^ hi32(seed)) ^ lo32(call)) ^ hi32(call))
+ *        w1  = fmix32(c  ^ ((b * H + h) * 0x9e3779b1))
+ *        w2  = fmix32(w1 ^ (i * 0x85ebca6b))
+ *        r   = fmix32(w2 ^ (j * 0xc2b2ae35))
+ *   element (b, h, i, j) is kept iff r >= min(2^32 - 1, floor((double)p * 2^32)); kept elements are multiplied by the float
+ *   1 / (1 - p).  The draw depends on (seed, call, b, H, h, i, j) only; the backward regenerates it from the same arguments.
+ *   p == 0 keeps everything, multiplies by nothing, and (seed, call) do not matter.
+ * Determinism: no atomics, every sum in an order fixed by (L, d); two runs are bit-identical.
+ * Supported (tbe_attention_supported returns 1): d % 4 == 0, 4 <= d <= 128, 1 <= L <= 256, and the LDS image
+ *   4 * (2 L (d + 4) + 33 * roundup(L, 4)) bytes within 160 KiB — (100, 128), (200, 64), (256, 32), (137, 128) are inside.
+ * Errors, before anything is launched and with no byte changed: TBE_ERR_INVALID_ARGUMENT for a null or misaligned pointer,
+ *   B < 0, H / L / d < 1, an unsupported (L, d), a row stride below H * d, a batch stride below (L - 1) * row_stride + H * d,
+ *   a stride that is no multiple of 4, p outside [0, 1), B * H beyond 2^31 - 1.  B == 0 launches nothing: TBE_OK. */
+int tbe_attention_supported(int64_t L, int64_t d);
+/* examples/bert4rec/models/bert4rec.py:72-82, 152-170 */
+int tbe_attention_forward_f32(const float* q, int64_t q_batch_stride, int64_t q_row_stride,
+                              const float* k, int64_t k_batch_stride, int64_t k_row_stride,
+                              const float* v, int64_t v_batch_stride, int64_t v_row_stride,
+                              const uint8_t* key_valid, int64_t B, int32_t H, int32_t L, int32_t d,
+                              float p, uint64_t seed, int64_t call, float* out, float* lse, void* stream);
+/* the backward autograd builds for examples/bert4rec/models/bert4rec.py:72-82, 152-170 */
+int tbe_attention_backward_f32(const float* grad_out,
+                               const float* q, int64_t q_batch_stride, int64_t q_row_stride,
+                               const float* k, int64_t k_batch_stride, int64_t k_row_stride,
+                               const float* v, int64_t v_batch_stride, int64_t v_row_stride,
+                               const uint8_t* key_valid, const float* lse, int64_t B, int32_t H, int32_t L, int32_t d,
+                               float p, uint64_t seed, int64_t call, float* dq, float* dk, float* dv, void* stream);
+
+/* JaggedTensor.to_padded_dense (torchrec/sparse/jagged_tensor.py:344-363) in one launch: out [B, N] float32 from the bags
+ * values[offsets[b] .. offsets[b + 1]).  A bag of at most N values is padded with padding_value: in front of the values
+ * (right-aligned values) with pad_from_beginning, behind them otherwise.  A longer bag keeps its LAST N values with
+ * chop_from_beginning, its first N otherwise.  Integer values are converted as torch's cast does (round to nearest even:
+ * 2^24 + 1 -> 16777216.0).  values may be NULL when every bag is empty; the entry cannot check that (the offsets are on
+ * the device): a NULL values with any non-empty bag is undefined behaviour.  B == 0 or N == 0 launches nothing. */
+/* torchrec/sparse/jagged_tensor.py:303-364 */
+int tbe_jagged_to_padded_dense_i64(const int64_t* values, const int64_t* offsets, int32_t B, int32_t N, float padding_value,
+                                   int32_t pad_from_beginning, int32_t chop_from_beginning, float* out, void* stream);
+/* torchrec/sparse/jagged_tensor.py:303-364 */
+int tbe_jagged_to_padded_dense_i32(const int32_t* values, const int64_t* offsets, int32_t B, int32_t N, float padding_value,
+                                   int32_t pad_from_beginning, int32_t chop_from_beginning, float* out, void* stream);
+/* torchrec/sparse/jagged_tensor.py:303-364 */
+int tbe_jagged_to_padded_dense_f32(const float* values, const int64_t* offsets, int32_t B, int32_t N, float padding_value,
+                                   int32_t pad_from_beginning, int32_t chop_from_beginning, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

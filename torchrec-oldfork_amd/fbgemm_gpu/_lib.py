@@ -246,6 +246,18 @@ SIGNATURES = {
         ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i64, c_void_p, c_void_p]),
     "tbe_offsets_range": (ctypes.c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p]),
     "tbe_copy_rows": (ctypes.c_int, [c_void_p, c_i64, c_void_p, c_i32, c_i64, c_void_p, c_void_p]),
+    "tbe_attention_supported": (ctypes.c_int, [c_i64, c_i64]),
+    "tbe_attention_forward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_i64, c_i64] * 3 + [c_void_p, c_i64, c_i32, c_i32, c_i32, c_float, c_u64, c_i64, c_void_p, c_void_p,
+                                        c_void_p]),
+    "tbe_attention_backward_f32": (
+        ctypes.c_int,
+        [c_void_p] + [c_void_p, c_i64, c_i64] * 3 + [c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_float, c_u64, c_i64,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    **{f"tbe_jagged_to_padded_dense_{t}": (
+        ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i32, c_float, c_i32, c_i32, c_void_p, c_void_p])
+       for t in ("i64", "i32", "f32")},
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -552,3 +552,56 @@ _impl.impl("pooled_exchange_pack", _pack)
 _impl.impl("pooled_exchange_pack_into", _pack_into)
 _impl.impl("a2a_pooled_unpack", _simple_unpack)
 _impl.impl("a2a_pooled_pack", _simple_pack)
+
+
+# ---- fused masked attention (csrc/attention.hip): plain functions, not dispatcher ops — the tensors are read where the
+# projections left them (per-tensor strides) and the wanted gradients are chosen per call, which no op schema expresses.
+
+def attention_supported(L: int, d: int) -> bool:
+    """The kernel's (L, d_k) range: include/tbe_hip.h tbe_attention_supported."""
+    return bool(_lib.load().tbe_attention_supported(L, d))
+
+
+def _attention_strides(name, t, H):
+    """(batch stride, row stride) in floats of a float32 [B, L, H * d] tensor whose last dimension is dense."""
+    if t.dim() != 3 or t.dtype != torch.float32 or t.stride(2) != 1 or t.shape[2] % H:
+        raise RuntimeError(f"{name}: want float32 [B, L, H * d] with a dense last dimension, got {tuple(t.shape)} "
+                           f"{t.dtype} strides {t.stride()}")
+    return t.stride(0), t.stride(1)
+
+
+def attention_forward(q, k, v, key_valid, H, p=0.0, seed=0, call=0):
+    """(out [B, L, H * d], lse [B, H, L]) of tbe_attention_forward_f32; q, k, v [B, L, H * d] float32 views with any batch /
+    row strides, key_valid None or uint8 [B, L]."""
+    dev = require_gpu(q, k, v, key_valid)
+    B, L, HD = q.shape
+    if k.shape != q.shape or v.shape != q.shape:
+        raise RuntimeError(f"attention_forward: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} differ")
+    strides = [s for t in (q, k, v) for s in _attention_strides("attention_forward", t, H)]
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.shape != (B, L) or not key_valid.is_contiguous()):
+        raise RuntimeError("attention_forward: key_valid must be a contiguous uint8 [B, L]")
+    out = torch.empty((B, L, HD), dtype=torch.float32, device=dev)
+    lse = torch.empty((B, H, L), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_attention_forward_f32(
+            ptr(q), strides[0], strides[1], ptr(k), strides[2], strides[3], ptr(v), strides[4], strides[5], ptr(key_valid),
+            B, H, L, HD // H, p, seed, call, ptr(out), ptr(lse), stream_ptr(dev)), "tbe_attention_forward_f32")
+    return out, lse
+
+
+def attention_backward(grad_out, q, k, v, key_valid, lse, H, p=0.0, seed=0, call=0, need=(True, True, True)):
+    """(dq, dk, dv), each contiguous [B, L, H * d] or None where `need` says so (tbe_attention_backward_f32)."""
+    dev = require_gpu(grad_out, q, k, v, lse, key_valid)
+    B, L, HD = q.shape
+    strides = [s for t in (q, k, v) for s in _attention_strides("attention_backward", t, H)]
+    if grad_out.shape != q.shape or grad_out.dtype != torch.float32 or not grad_out.is_contiguous():
+        raise RuntimeError("attention_backward: grad_out must be a contiguous float32 [B, L, H * d]")
+    if lse.shape != (B, H, L) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise RuntimeError("attention_backward: lse must be the forward's [B, H, L]")
+    grads = [torch.empty((B, L, HD), dtype=torch.float32, device=dev) if w else None for w in need]
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_attention_backward_f32(
+            ptr(grad_out), ptr(q), strides[0], strides[1], ptr(k), strides[2], strides[3], ptr(v), strides[4], strides[5],
+            ptr(key_valid), ptr(lse), B, H, L, HD // H, p, seed, call, ptr(grads[0]), ptr(grads[1]), ptr(grads[2]),
+            stream_ptr(dev)), "tbe_attention_backward_f32")
+    return tuple(grads)

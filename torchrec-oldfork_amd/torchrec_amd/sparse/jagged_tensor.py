@@ -18,6 +18,9 @@ import torch
 import fbgemm_gpu  # noqa: F401  registers torch.ops.fbgemm.* (the reference loads the op library here: jagged_tensor.py:18-24)
 
 
+_PADDED_DENSE_KERNELS = {torch.int64: "i64", torch.int32: "i32", torch.float32: "f32"}  # tbe_jagged_to_padded_dense_*
+
+
 def _host_cumsum(x: List[int]) -> List[int]:
     out = [0] * (len(x) + 1)
     for i, v in enumerate(x):
@@ -60,6 +63,50 @@ class JaggedTensor:
     def to_dense(self) -> List[torch.Tensor]:
         offs = self.offsets().tolist()
         return [self._values[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
+
+    def to_padded_dense(self, desired_length: Optional[int] = None, padding_value: float = 0.0,
+                        pad_from_beginning: bool = True, chop_from_beginning: bool = True) -> torch.Tensor:
+        """Dense [B, N] from the bags (torchrec/sparse/jagged_tensor.py:303-364): N = desired_length, or the longest bag.
+        A bag of at most N values is padded with `padding_value` in front of its values (`pad_from_beginning`) or behind
+        them; a longer bag keeps its last N values (`chop_from_beginning`) or its first N.
+
+        On a HIP device with int32 / int64 / float32 values it is one kernel (tbe_jagged_to_padded_dense_*) and no
+        device-to-host copy when `desired_length` is given (one, the maximum length, otherwise); elsewhere one vectorised
+        torch expression.  Two deliberate differences from the reference's per-sample loop: the result always has the
+        dtype that torch.cat with the float padding promotes to (float32 for integer and float32 values — the reference
+        returns the values' dtype only when EVERY bag is longer than N), and an empty batch returns [0, N] where the
+        reference's torch.stack raises."""
+        values = self._values
+        if desired_length is None:
+            lengths = self.lengths()
+            N = int(lengths.max().item()) if lengths.numel() else 0
+        else:
+            N = int(desired_length)
+        if values.is_cuda and values.dim() == 1 and values.dtype in _PADDED_DENSE_KERNELS:
+            from fbgemm_gpu import _lib
+
+            offs = self.offsets().to(torch.int64).contiguous().view(-1)
+            B = offs.numel() - 1
+            vals = values.contiguous()
+            out = torch.empty((B, N), dtype=torch.float32, device=values.device)
+            name = "tbe_jagged_to_padded_dense_" + _PADDED_DENSE_KERNELS[values.dtype]
+            with torch.cuda.device(values.device):
+                _lib.check(getattr(_lib.load(), name)(
+                    _lib.ptr(vals) if vals.numel() else None, _lib.ptr(offs), B, N, padding_value, int(pad_from_beginning),
+                    int(chop_from_beginning), _lib.ptr(out), _lib.stream_ptr(values.device)), name)
+            return out
+        lengths = self.lengths().to(torch.int64).view(-1)
+        lo = torch.cumsum(lengths, 0) - lengths  # not offsets(): that is a device op of this package
+        n = torch.arange(N, device=values.device, dtype=torch.int64).unsqueeze(0)
+        ln = lengths.unsqueeze(1)
+        short = n - (N - ln) if pad_from_beginning else torch.where(n < ln, n, torch.full_like(n, -1))
+        src = torch.where(ln <= N, short, ln - N + n if chop_from_beginning else n.expand(ln.shape[0], N))
+        dtype = torch.result_type(values, torch.tensor(0.0))
+        pad = torch.full((1,), padding_value, dtype=dtype, device=values.device)
+        if values.numel() == 0:
+            return pad.expand(ln.shape[0], N).clone()
+        gathered = values.to(dtype)[(lo.unsqueeze(1) + src).clamp(0, values.numel() - 1)]
+        return torch.where(src >= 0, gathered, pad)
 
 
 class KeyedJaggedTensor:
