@@ -1002,6 +1002,83 @@ int tbe_jagged_to_padded_dense_i32(const int32_t* values, const int64_t* offsets
 int tbe_jagged_to_padded_dense_f32(const float* values, const int64_t* offsets, int32_t B, int32_t N, float padding_value,
                                    int32_t pad_from_beginning, int32_t chop_from_beginning, float* out, void* stream);
 
+/* Cross-entropy over class indices with ignore_index — nn.CrossEntropyLoss(ignore_index=0) of the BERT4Rec trainer
+ * (examples/bert4rec/bert4rec_main.py:278-295) and the backward autograd builds for it.  input [R, V] float32 with inner
+ * stride 1 and row_stride >= V (elements), target [R] int64, reduction 0 = mean, 1 = sum, 2 = none.
+ *   forward : a row whose target is ignore_index is NOT READ: its stats and its loss are 0.  Every other row is streamed once
+ *             with a running (max, sum) pair:  stats[0, r] = m = max_v x[r, v],  stats[1, r] = ls = logf(sum_v expf(x[r, v] - m)),
+ *             row loss = (m - x[r, t]) + ls.  stats [2, R] is all the backward needs besides input and target; the
+ *             log-sum-exp m + ls stays in two terms because one float32 would lose ls below the ulp of m (1e-3 at 1e4).
+ *             One finishing launch (one workgroup) writes n_valid[0] = #{r : target[r] != ignore_index}, an exact int64, and
+ *             loss[0] = sum of the row losses (sum) or that sum / (float)n_valid (mean: 0 / 0 = NaN when no row is valid, R == 0
+ *             included).  none: loss is [R] and holds the row losses.  mean / sum keep the row losses in `workspace`
+ *             (tbe_cross_entropy_workspace_bytes(R) bytes, 16-B aligned, no zeroing needed); none does not look at it.
+ *   backward: grad_input[r, v] = (expf((x[r, v] - m) - ls) - [v == t]) * s  with  s = grad_out[0] / (float)n_valid[0] (mean),
+ *             grad_out[0] (sum), grad_out[r] (none);  exact zeros in the rows whose target is ignore_index, which are not read.
+ *             n_valid is read on the device: neither call waits for the host, both can be captured into a HIP graph.
+ *             grad_input has its own row stride (>= V) and may not overlap anything.
+ * A target outside [0, V) that is not ignore_index forms no address: the row's stats, its loss and its gradient row are NaN (and
+ * so is a mean / sum loss); it counts as valid.  -inf entries are ordinary values (probability 0, gradient 0); a row that
+ * holds NaN or +inf, or -inf only, yields non-finite values.
+ * Geometry, a function of V only: 16 threads per row and 16 rows per workgroup for V <= 256, a wave per row and 4 rows per
+ * workgroup for V <= 4096, the workgroup (256 threads) per row beyond.  Columns are taken in groups of 4; group g belongs to
+ * thread g % (threads per row), which folds its groups in ascending order, 4 groups (16 columns) per fold; the threads' pairs
+ * meet in a butterfly over the wave and then in wave order.  The row losses are summed by thread r % 256 in ascending r, then
+ * butterfly and wave order: an order that depends on R only.  A group moves as one 16-byte access where its address allows,
+ * as 8 + 8 or 4 + 8 + 4 bytes elsewhere (V % 4 != 0, odd strides); the choice changes no bit: the results depend on (R, V) and
+ * the values only, not on base alignment or row stride.  Each product and add is rounded on its own; no atomics; two runs
+ * are bit-identical.
+ * Errors, before anything is launched and with no byte changed: TBE_ERR_INVALID_ARGUMENT for R < 0, V < 1, a reduction
+ * outside 0 .. 2, a row stride below V, a null pointer, a float pointer off the 4-byte grid (target, n_valid: 8 bytes;
+ * workspace: 16), a workspace shorter than tbe_cross_entropy_workspace_bytes(R) (mean / sum), more than 2^31 - 1 row blocks.
+ * R == 0: the forward runs the finishing launch only, the backward does nothing. */
+/* examples/bert4rec/bert4rec_main.py:278-295 */
+size_t tbe_cross_entropy_workspace_bytes(int64_t R);
+/* examples/bert4rec/bert4rec_main.py:278-295 */
+int tbe_cross_entropy_forward_f32(const float* input, int64_t row_stride, const int64_t* target, int64_t R, int32_t V,
+                                  int64_t ignore_index, int32_t reduction, float* stats /* [2, R] */,
+                                  float* loss /* [1]; none: [R] */, int64_t* n_valid /* [1] */, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+/* the backward autograd builds for examples/bert4rec/bert4rec_main.py:278-295 */
+int tbe_cross_entropy_backward_f32(const float* grad_out /* [1]; none: [R] */, const float* input, int64_t row_stride,
+                                   const int64_t* target, const float* stats, const int64_t* n_valid, int64_t R, int32_t V,
+                                   int64_t ignore_index, int32_t reduction, float* grad_input, int64_t grad_row_stride,
+                                   void* stream);
+
+/* Recall@k and NDCG@k of B candidate lists — recalls_and_ndcgs_for_ks (examples/bert4rec/bert4rec_metrics.py:13-61) with the
+ * score gather in front of it (examples/bert4rec/bert4rec_main.py:244-245) — in one kernel and one finishing launch, no sort.
+ * scores: float32, inner stride 1, score_row_stride (elements) >= the row width.  candidates == NULL: scores is [B, C].
+ * Otherwise scores is [B, V] and candidates [B, C] int64 (contiguous): list entry i of row b is scores[b, candidates[b, i]].
+ * labels [B, C] contiguous: uint8 / bool (label_elem_size 1), float32 (4) or int64 (8), values 0 / 1.
+ * ks: HOST array of nk distinct, ascending k with 1 <= k <= C (copied into the kernel arguments: the call can be captured).
+ * weights: DEVICE float32 [ks[nk - 1]], w[p] = 1 / log2(p + 2) as the caller computed it (the reference's expression,
+ * bert4rec_metrics.py:50-51); no logarithm is taken on the device.
+ * Per row, with s the list's scores:  pos_j = #{i : s_i > s_j} + #{i < j : s_i == s_j}  for every positive j — its place in
+ * np.argsort(-s, kind="stable").  TIE RULE: ties go to the lower index, -0.0 ties with +0.0, a NaN ranks behind every number
+ * and NaNs keep index order (the reference's unstable sort leaves ties to chance).  For each k, n_pos the row's positives:
+ *   hits = #{j positive : pos_j < k};  Recall = hits / min(k, n_pos);  DCG = sum of w[pos_j] over those hits in ascending
+ *   pos_j;  IDCG = sum of w[0 : min(k, n_pos)];  NDCG = DCG / IDCG.  Both sums run in float64, where they are exact for this
+ *   table and k <= 8192, so their order changes nothing.  A row without a positive yields NaN, and so does the mean.
+ * metrics: DEVICE float32 [2 nk] = {Recall@k_0 .., NDCG@k_0 ..}: the float32 rounding of the float64 mean over the rows, taken
+ * in an order that depends on B only.  counts: DEVICE int64 [2] = {candidates outside [0, V), labels outside {0, 1}}; such a
+ * candidate is never an address (its score is NaN) and such a label never a hit (it is 0): with a non-zero count the
+ * metrics are unspecified.  Integer compares and fixed orders only, no atomics: two runs are bit-identical.
+ * workspace: tbe_rank_metrics_workspace_bytes(B, nk) bytes, 256-B aligned, no zeroing needed.  It holds the per-row
+ * results: float32 row_values [B, 2 nk] (the layout of metrics) at offset 0 and, at the next multiple of 256 bytes, int32
+ * row_counts [B, 10] = {bad candidates, bad labels, hits of k_0 .. k_7}.
+ * Limits: 1 <= C <= 8192, 1 <= nk <= 8, 0 <= B <= 2^31 - 1.  Errors, before anything is launched and with no byte changed:
+ * TBE_ERR_INVALID_ARGUMENT for a value beyond a limit, a k outside 1 .. C or out of order, a label_elem_size other than
+ * 1 / 4 / 8, V < 1 with candidates, a row stride below the row width, a null or misaligned pointer; TBE_ERR_WORKSPACE for a
+ * short workspace (tbe_rank_metrics_workspace_bytes returns 0 for B or nk beyond the limits).  B == 0 is legal: the metrics
+ * are NaN (the mean of nothing), the counts 0. */
+/* examples/bert4rec/bert4rec_metrics.py:13-61 */
+size_t tbe_rank_metrics_workspace_bytes(int64_t B, int32_t nk);
+/* examples/bert4rec/bert4rec_metrics.py:13-61; examples/bert4rec/bert4rec_main.py:244-245 */
+int tbe_rank_metrics_f32(const float* scores, int64_t score_row_stride, const int64_t* candidates, int64_t V,
+                         const void* labels, int32_t label_elem_size, int64_t B, int32_t C, const int32_t* ks, int32_t nk,
+                         const float* weights, float* metrics, int64_t* counts, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

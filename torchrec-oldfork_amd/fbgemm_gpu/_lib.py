@@ -255,6 +255,18 @@ SIGNATURES = {
         ctypes.c_int,
         [c_void_p] + [c_void_p, c_i64, c_i64] * 3 + [c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_float, c_u64, c_i64,
                                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tbe_cross_entropy_workspace_bytes": (c_size, [c_i64]),
+    "tbe_cross_entropy_forward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "tbe_cross_entropy_backward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i64, c_i32, c_void_p, c_i64, c_void_p]),
+    "tbe_rank_metrics_workspace_bytes": (c_size, [c_i64, c_i32]),
+    "tbe_rank_metrics_f32": (
+        ctypes.c_int,
+        [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i64, c_i32, ctypes.POINTER(c_i32), c_i32, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size, c_void_p]),
     **{f"tbe_jagged_to_padded_dense_{t}": (
         ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i32, c_float, c_i32, c_i32, c_void_p, c_void_p])
        for t in ("i64", "i32", "f32")},

@@ -9,7 +9,9 @@ batch, `.compute().item()`), and `evaluate` is `_evaluate` itself.
 transform, the package's pair sort, a tie-aware integer reduction — csrc/auroc.hip) on the current stream, reads six
 integer counters back in one copy and divides them as Python integers.  The result is therefore exact (the correctly
 rounded float64 of the rational value), the same on every run and on every rank.  Out of scope: sample weights,
-multiclass, max_fpr, ROC curves, binned approximations."""
+multiclass, max_fpr, ROC curves, binned approximations.
+
+`recalls_and_ndcgs_for_ks` (ranking.py) is the BERT4Rec evaluation's Recall@k / NDCG@k on the device."""
 from typing import Any, Iterator, List, Optional, Tuple
 
 import itertools
@@ -19,7 +21,9 @@ import torch.distributed as dist
 from fbgemm_gpu import _lib
 from fbgemm_gpu._lib import check, ptr, require_gpu, stream_ptr
 
-__all__ = ["AUROC", "Accuracy", "evaluate", "MAX_SAMPLES"]
+from .ranking import recalls_and_ndcgs_for_ks
+
+__all__ = ["AUROC", "Accuracy", "evaluate", "MAX_SAMPLES", "recalls_and_ndcgs_for_ks"]
 
 MAX_SAMPLES = 1 << 29  # tbe_auroc_counts_f32 takes fewer samples than this (the pair sort's limit)
 _MIN_CAPACITY = 1024

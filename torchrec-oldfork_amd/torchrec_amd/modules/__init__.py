@@ -3,3 +3,4 @@ from .crossnet import CrossNet, LowRankCrossNet, LowRankMixtureCrossNet, VectorC
 from .deepfm import DeepFM, FactorizationMachine  # noqa: F401
 from .activation import SwishLayerNorm  # noqa: F401
 from .utils import extract_module_or_tensor_callable  # noqa: F401
+from .loss import CrossEntropyLoss, cross_entropy  # noqa: F401
