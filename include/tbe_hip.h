@@ -140,6 +140,12 @@ int tbe_profile_read_rows(int64_t* rows_updated);
  * feat_rows      [F] number of rows of the feature's table (bounds check)
  * indices [N] int64, offsets [F*B+1] int64, per_sample_weights [N] float or NULL
  * out: float buffer addressed as above; out_row_stride in elements
+ * max_D          must be >= every feat_D[f] (and <= 2048).  It ALONE selects the kernel class — lanes per row group
+ *                and 16-B column slots per lane: (16, 1) up to 64, (32, 1) up to 128, (64, 1) / (64, 2) / (64, 4) /
+ *                (64, 8) up to 256 / 512 / 1024 / 2048 — whatever the feat_D are: a narrow feature in a wide module
+ *                runs in the wide class with idle lanes.  The library does not read feat_D on the host, so a
+ *                max_D below some feat_D[f] is NOT an error it can report: columns of that feature beyond the
+ *                class's reach (4 * lanes * slots) are silently not written.
  * bounds_errors  optional device int32 counter: incremented for every index outside
  *                [0, rows); such an index contributes a zero row (never dereferenced).  Also incremented for
  *                every bag whose offsets are malformed (start < 0, end > N, start > end): such a bag is
