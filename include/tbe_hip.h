@@ -679,6 +679,16 @@ int tbe_permute_pooled_embs_f32(const float* in, float* out, const int64_t* offs
  * reference's dense rows (stride 479 floats at F = 26, D = 128) are not 16-B aligned; with a stride that is a
  * multiple of 4 and leaves room for the pair block rounded up to 4 (480) the forward stores 16 B per lane and
  * writes the pad columns as zeros, and the GEMMs of the next layer read aligned rows (lda = 480, K = 479).
+ * Alignment: dense, sparse, grad_dense and grad_sparse 16 B; `out` and `grad_out` need only 4 B.  With P = (F+1)F/2 and
+ * P4 = P rounded up to 4, the forward takes its 16-B path exactly when `out` is 16-B aligned, out_row_stride % 4 == 0 and
+ * out_row_stride >= D + P4; any other pointer or stride takes 4-B stores.  Columns of a row the forward writes:
+ *   16-B path: [0, D + P) and zeros in [D + P, D + P4);   4-B path: [0, D + P).
+ * Nothing else is written: columns from D + P4 (16-B path) or D + P (4-B path) up to the stride keep their contents, as
+ * does everything outside the B rows.  The backward reads columns [0, D + P) of a grad_out row and nothing beyond (the
+ * pad columns may hold anything, NaN included); it reads the first D of them 16 B at a time when grad_out is 16-B
+ * aligned and grad_row_stride % 4 == 0, else 4 B at a time.  No call modifies its inputs; B = 0 returns 0 and touches
+ * nothing; a non-finite value in one sample changes no other sample's results.  tests/test_interaction_abi_gpu.py holds
+ * every statement of this block bit for bit against oracle/dlrm_oracle.c.
  * ---------------------------------------------------------------------------------- */
 int tbe_dlrm_interaction_forward_f32(const float* dense, const float* sparse, int32_t B,
                                      int32_t F, int32_t D, float* out, int64_t out_row_stride,

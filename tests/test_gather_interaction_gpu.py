@@ -13,6 +13,12 @@ pytestmark = pytest.mark.gpu
 ID_SKIP = -(1 << 63)  # TBE_ID_SKIP
 SHAPES = [(1, 26, 128), (3, 1, 64), (17, 7, 128), (257, 26, 128), (4099, 27, 128), (8192, 26, 128), (2600, 5, 64)]
 ROW_MIX = [1, 3, 1000, 200000]  # some rows repeat thousands of times within a batch
+# The gather kernels share the dense ones' second row tile (on from R = F + 1 = 17) and the forward's counted wait for the
+# next sample's copy (T = ceil(P / 64) pair stores; it matters once a wave loops, B > 2048, on unaligned rows): R = 16 and
+# 17 with three trips per wave, T = 2 and 4 (the shapes above reach 1 and 6), R = 17 with fewer samples than waves.
+EDGE_SHAPES = [(4101, 15, 128), (4101, 16, 64), (4101, 11, 128), (4101, 20, 64), (5, 16, 128)]
+SHAPES += EDGE_SHAPES
+SMALL_ROW_MIX = [1, 3, 1000, 5000]  # for EDGE_SHAPES: the tables, which the oracle test copies to the host, stay small
 
 
 def _lib():
@@ -105,6 +111,12 @@ class Case:
         return out, gd, gs, int(err.item())
 
 
+def _shape_case(B, F, D):
+    """The Case of a SHAPES entry."""
+    rows = [SMALL_ROW_MIX[f % 4] for f in range(F)] if (B, F, D) in EDGE_SHAPES else None
+    return Case(B, F, D, rows=rows)
+
+
 def _assert_same(a, b, width):
     (out_a, gd_a, gs_a, _), (out_b, gd_b, gs_b, _) = a, b
     assert torch.equal(out_a, out_b)  # pad columns included: both write them as zeros
@@ -116,7 +128,7 @@ def _assert_same(a, b, width):
 @pytest.mark.parametrize("pad", [False, True], ids=["dense_rows", "padded_rows"])
 @pytest.mark.parametrize("B,F,D", SHAPES)
 def test_gather_kernels_bitwise_equal_to_the_unfused_pair(B, F, D, pad):
-    c = Case(B, F, D)
+    c = _shape_case(B, F, D)
     _assert_same(c.fused(pad), c.unfused(pad), c.width)
 
 
@@ -124,7 +136,7 @@ def test_gather_kernels_bitwise_equal_to_the_unfused_pair(B, F, D, pad):
 @pytest.mark.parametrize("B,F,D", SHAPES)
 def test_gather_kernels_bitwise_equal_to_the_oracle(B, F, D, pad):
     """oracle.tbe_forward composed with oracle.interaction_forward / interaction_backward on the same inputs."""
-    c = Case(B, F, D)
+    c = _shape_case(B, F, D)
     tabs = oracle.Tables(c.rows, [D] * F)
     tabs.weights = [np.ascontiguousarray(t.cpu().numpy()) for t in c.tables]
     pooled, bad = oracle.tbe_forward(tabs, c.ids.numpy(), np.arange(F * B + 1, dtype=np.int64))
