@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 
 #include "../../include/tbe_hip.h"
 
@@ -38,6 +39,13 @@ inline bool all_aligned(std::initializer_list<const void*> ptrs, uintptr_t mask)
   uintptr_t bits = 0;
   for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
   return (bits & mask) == 0;
+}
+
+// f(std::integral_constant<int, V>{}) for the V of the list that equals v (a row width, a TPR, a layer count); false if none
+// does
+template <int... Vs, typename F>
+bool dispatch_value(int v, F f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
 }
 
 // The pointers of entry `name`: none null, `vec` (arrays that move as float4) 16-B aligned, `scalar` 4-B aligned.

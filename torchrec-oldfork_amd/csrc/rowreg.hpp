@@ -12,7 +12,6 @@
 //                (colsum.hpp) finishes all the sums of a kernel.
 #pragma once
 #include <initializer_list>
-#include <type_traits>
 
 #include "colsum.hpp"
 
@@ -131,12 +130,6 @@ struct RowTile {
 };
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-// f(std::integral_constant<int, V>{}) for the V of the list that equals v (a TPR, a layer count); false if none does
-template <int... Vs, typename F>
-bool dispatch_value(int v, F f) {
-  return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
-}
-
 inline size_t rowreg_workspace_bytes(int64_t row_blocks, int sums, int N) {
   if (row_blocks <= 0 || sums <= 0 || N <= 0) return 256;
   return align_up(static_cast<size_t>(row_blocks) * sums * N * sizeof(float), 256);
