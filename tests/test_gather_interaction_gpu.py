@@ -14,8 +14,11 @@ ID_SKIP = -(1 << 63)  # TBE_ID_SKIP
 SHAPES = [(1, 26, 128), (3, 1, 64), (17, 7, 128), (257, 26, 128), (4099, 27, 128), (8192, 26, 128), (2600, 5, 64)]
 ROW_MIX = [1, 3, 1000, 200000]  # some rows repeat thousands of times within a batch
 # The gather kernels share the dense ones' second row tile (on from R = F + 1 = 17) and the forward's counted wait for the
-# next sample's copy (T = ceil(P / 64) pair stores; it matters once a wave loops, B > 2048, on unaligned rows): R = 16 and
-# 17 with three trips per wave, T = 2 and 4 (the shapes above reach 1 and 6), R = 17 with fewer samples than waves.
+# next sample's copy (T = ceil(P / 64) pair stores; it matters once a wave loops, B > 2048, on unaligned rows).  R = 16 and
+# 17 with three trips per wave run on the 16-B store path, which waits for everything: P = 120 and 136 are multiples of 4,
+# so the row strides 248 and 200 are those of 16-B rows, padded or not.  The counted wait loops at T = 2
+# and 4 (F = 11 and 20 on rows of D + P; the shapes above reach 1 and 6); R = 17 with fewer samples than waves.  The
+# counted wait at R = 16 | 17 and the other row layouts: tests/test_gather_interaction_abi_gpu.py.
 EDGE_SHAPES = [(4101, 15, 128), (4101, 16, 64), (4101, 11, 128), (4101, 20, 64), (5, 16, 128)]
 SHAPES += EDGE_SHAPES
 SMALL_ROW_MIX = [1, 3, 1000, 5000]  # for EDGE_SHAPES: the tables, which the oracle test copies to the host, stay small
