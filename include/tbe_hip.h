@@ -1095,6 +1095,42 @@ int tbe_rank_metrics_f32(const float* scores, int64_t score_row_stride, const in
                          const float* weights, float* metrics, int64_t* counts, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* Criteo batch builder: raw rows of the preprocessed day files -> dense_features, feature-major hashed ids and labels of one
+ * batch, in one launch.  It replaces, on the device, what the reference does per batch on the host: np.concatenate of the
+ * file slices (torchrec/datasets/criteo.py:798), the three fancy-index gathers under the batch's permutation, the strided
+ * `sparse.transpose(1, 0).reshape(-1)` copy and `labels.reshape(-1)` (_np_arrays_to_batch, criteo.py:760-784), the
+ * load-time `sparse_arr %= hashes` (criteo.py:755-758) and the later `.long()` of the ids
+ * (fbgemm_gpu/split_table_batched_embeddings_ops.py:565-566).
+ * segs: HOST array of nseg in 0 .. TBE_CRITEO_MAX_SEGMENTS descriptors, copied BY VALUE into the kernel arguments (no device
+ *   table: the call can be captured into a HIP graph).  A segment is `rows` consecutive rows of one file, as DEVICE pointers
+ *   to row-major dense [rows, 13] float32, sparse [rows, 26] int32 and labels [rows, 1] int32, each 4-byte aligned (a row
+ *   range starts wherever its first row does: no wider alignment is asked for).  The batch's source rows are numbered by
+ *   running through the segments in order; a segment with rows == 0 is skipped and its pointers are not looked at.
+ * B: rows of the batch; must equal the sum of the segment rows.
+ * hashes: DEVICE int32 [26], every entry in [1, 2^31 - 1] (the caller checks: the array lives on the device), or NULL: ids
+ *   pass through, sign-extended.  perm: DEVICE int64 [B] or NULL (identity).  bad_perm: DEVICE int32 counter or NULL.
+ * Output row j takes source row s = perm ? perm[j] : j:
+ *   dense_out[j, 0:13] = dense[s, 0:13];  labels_out[j] = labels[s, 0];
+ *   values_out[f * B + j] = floormod(sparse[s, f], hashes[f]) widened to the output type (feature-major, the layout of a
+ *   KeyedJaggedTensor with one id per bag), where floormod is numpy's: r = v % h; r += r < 0 ? h : 0, in 32-bit signed
+ *   arithmetic (no overflow for h <= 2^31 - 1): -7 mod 3 = 2, -2^31 mod (2^31 - 1) = 2^31 - 2.
+ * A perm[j] outside [0, B) forms no address: row j of all three outputs is written as zeros and *bad_perm is incremented (the
+ * library's rule for bad ids; the only atomic).  Repeats in perm are legal.  Everything is a copy or an integer operation:
+ * the result bits depend on neither alignment, segmentation nor the tile (TBE_CRITEO_TILE_ROWS output rows per workgroup).
+ * Errors, before anything is launched and with no byte changed: TBE_ERR_INVALID_ARGUMENT for nseg outside
+ * 0 .. TBE_CRITEO_MAX_SEGMENTS, a negative B or rows, a null or 4-byte-misaligned pointer in a segment with rows > 0, B not the
+ * sum of the segment rows, a null or misaligned output, 26 * B beyond 2^31 - 1 for the _i32 entry, more than 2^31 - 1 row
+ * tiles.  B == 0 launches nothing and returns TBE_OK. */
+#define TBE_CRITEO_MAX_SEGMENTS 8
+#define TBE_CRITEO_TILE_ROWS 64
+typedef struct { const float* dense; const int32_t* sparse; const int32_t* labels; int64_t rows; } tbe_criteo_segment;
+/* torchrec/datasets/criteo.py:760-784 */
+int tbe_criteo_batch_i64(const tbe_criteo_segment* segs, int32_t nseg, int64_t B, const int32_t* hashes, const int64_t* perm,
+                         float* dense_out, int64_t* values_out, int32_t* labels_out, int32_t* bad_perm, void* stream);
+/* torchrec/datasets/criteo.py:760-784; values as int32, the dtype of the reference's host batches */
+int tbe_criteo_batch_i32(const tbe_criteo_segment* segs, int32_t nseg, int64_t B, const int32_t* hashes, const int64_t* perm,
+                         float* dense_out, int32_t* values_out, int32_t* labels_out, int32_t* bad_perm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,7 +59,15 @@ class FmGradSegment(ctypes.Structure):
     _fields_ = [("g", c_void_p), ("row_stride", c_i64)]
 
 
+class CriteoSegment(ctypes.Structure):
+    """Mirror of ``tbe_criteo_segment`` (include/tbe_hip.h): `rows` consecutive raw rows of one file, device pointers."""
+
+    _fields_ = [("dense", c_void_p), ("sparse", c_void_p), ("labels", c_void_p), ("rows", c_i64)]
+
+
 FM_MAX_SEGMENTS = 8  # TBE_FM_MAX_SEGMENTS
+CRITEO_MAX_SEGMENTS = 8  # TBE_CRITEO_MAX_SEGMENTS
+CRITEO_TILE_ROWS = 64  # TBE_CRITEO_TILE_ROWS
 CHUNKS_WAVE_ORDER = 1 << 62  # TBE_CHUNKS_WAVE_ORDER
 CHUNK_SEGS_BY_VALUE = 32  # segments of one tbe_multi_chunk_sum_host_table_f32 call
 
@@ -267,6 +275,10 @@ SIGNATURES = {
         ctypes.c_int,
         [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i32, c_i64, c_i32, ctypes.POINTER(c_i32), c_i32, c_void_p, c_void_p,
          c_void_p, c_void_p, c_size, c_void_p]),
+    **{f"tbe_criteo_batch_{t}": (
+        ctypes.c_int,
+        [ctypes.POINTER(CriteoSegment), c_i32, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+       for t in ("i64", "i32")},
     **{f"tbe_jagged_to_padded_dense_{t}": (
         ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i32, c_float, c_i32, c_i32, c_void_p, c_void_p])
        for t in ("i64", "i32", "f32")},

@@ -2,12 +2,12 @@
 examples/dlrm/data/dlrm_dataloader.py:26-45, torchrec/datasets/utils.py:34-61 `Batch`).
 Unlike the reference (which replays ONE generated batch, random.py:47-49) a pool of distinct
 batches is generated so cache reuse is realistic; ids are uniform or Zipf."""
-from dataclasses import dataclass
 from typing import Iterator, List, Optional
 
 import torch
 
 from ..sparse.jagged_tensor import KeyedJaggedTensor
+from .utils import Batch  # noqa: F401  (its home is datasets/utils.py, as in the reference; re-exported for existing imports)
 
 CRITEO_1TB_ROWS = [45833188, 36746, 17245, 7413, 20243, 3, 7114, 1441, 62, 29275261, 1572176, 345138, 10, 2209,
                    11267, 128, 4, 974, 14, 48937457, 11316796, 40094537, 452104, 12606, 104, 35]
@@ -16,26 +16,6 @@ CRITEO_KAGGLE_ROWS = [1460, 583, 10131227, 2202608, 305, 24, 12517, 633, 3, 9314
 INT_FEATURE_COUNT = 13
 CAT_FEATURE_COUNT = 26
 DEFAULT_CAT_NAMES = [f"cat_{i}" for i in range(CAT_FEATURE_COUNT)]
-
-
-@dataclass
-class Batch:
-    dense_features: torch.Tensor
-    sparse_features: KeyedJaggedTensor
-    labels: torch.Tensor
-
-    def to(self, device: torch.device, non_blocking: bool = False) -> "Batch":
-        return Batch(self.dense_features.to(device, non_blocking=non_blocking),
-                     self.sparse_features.to(device, non_blocking=non_blocking),
-                     self.labels.to(device, non_blocking=non_blocking))
-
-    def record_stream(self, stream) -> None:
-        self.dense_features.record_stream(stream)
-        self.sparse_features.record_stream(stream)
-        self.labels.record_stream(stream)
-
-    def pin_memory(self) -> "Batch":
-        return Batch(self.dense_features.pin_memory(), self.sparse_features.pin_memory(), self.labels.pin_memory())
 
 
 class RandomRecDataset:
