@@ -5,6 +5,7 @@ pattern (sharded-vs-unsharded equivalence after one train step,
 torchrec/distributed/test_utils/test_model_parallel_base.py:148-294); compute is the oracle's
 (tests/_oracle_tbe.py) because the product has no CPU kernels."""
 import os
+import random
 import socket
 
 import numpy as np
@@ -17,11 +18,19 @@ import _paths  # noqa: F401
 
 
 def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+    """A port nobody listens on, for rank 0's store.  Drawn below 32768: the ports above are the ones the kernel hands to
+    outgoing connections and to bind(0), so one found free there can be taken again in the seconds the ranks need to start
+    (seen once as EADDRINUSE from rank 0's listen)."""
+    rng = random.SystemRandom()
+    for _ in range(64):
+        p = rng.randrange(20000, 32768)
+        with socket.socket() as s:
+            try:
+                s.bind(("127.0.0.1", p))
+            except OSError:
+                continue
+        return p
+    raise RuntimeError("no free port between 20000 and 32767")
 
 
 ROWS = [40, 7, 23, 90, 5]
