@@ -29,7 +29,8 @@ class Buf:
 
 
 GUARD_BYTES = 4 * GUARD
-INT_CANARY = {np.dtype(np.uint8): 0xA5, np.dtype(np.int32): 0x5A5A5A5A, np.dtype(np.int64): 0x5A5A5A5A5A5A5A5A}
+INT_CANARY = {np.dtype(np.uint8): 0xA5, np.dtype(np.int16): 0x5A5A, np.dtype(np.int32): 0x5A5A5A5A,
+              np.dtype(np.int64): 0x5A5A5A5A5A5A5A5A}
 
 
 class TypedBuf:

@@ -194,8 +194,9 @@ def test_copy_rows_rejects_unaligned_rows():
 
 
 @pytest.mark.parametrize("vec", [True, False])
-@pytest.mark.parametrize("W,B", [(4, 37), (2, 64), (8, 5)])
-def test_pooled_exchange_kernels_bit_exact_vs_oracle(W, B, vec):
+@pytest.mark.parametrize("W,B,one_feature", [(4, 37, False), (2, 64, False), (8, 5, False), (1, 37, False), (4, 9, True)],
+                         ids=["4-37", "2-64", "8-5", "1-37", "one-feature"])
+def test_pooled_exchange_kernels_bit_exact_vs_oracle(W, B, one_feature, vec):
     """csrc/pooled_exchange.hip against oracle/tbe_oracle.c, bit for bit: table-wise features (copy from / to the owner's
     slab), row-wise features (sum of W partials in rank order / broadcast) and replicated features (columns the exchange
     must leave alone) mixed in one matrix, odd batch sizes, the 1/W scale of the gradient; 16-B vector and scalar forms.
@@ -206,6 +207,8 @@ def test_pooled_exchange_kernels_bit_exact_vs_oracle(W, B, vec):
     rng = np.random.default_rng(W * 100 + B)
     dims = [128, 64, 128, 32, 128, 64, 128, 128, 16, 128]
     kinds = [0, -1, -2, 1 % W, -2, -1, (W - 1), 0, -2, 1 % W]  # owner rank, -1 row-wise, -2 replicated
+    if one_feature:  # a matrix of one row-wise feature: the column search has a single entry
+        dims, kinds = [64], [-1]
     out_col = np.concatenate([[0], np.cumsum(dims)]).astype(np.int32)
     D_total = int(out_col[-1])
     # slab of rank r = [every row-wise feature | r's table-wise features], in feature order: a row-wise feature sits at the

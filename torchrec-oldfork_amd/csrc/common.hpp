@@ -48,6 +48,31 @@ bool dispatch_value(int v, F f) {
   return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
 }
 
+// Element-size dispatch: dispatch_value<4, 8>(elem_size, [&](auto n) { using T = int_of<decltype(n)::value>; ... }).  Bytes
+// that are only moved travel as uint_of.
+template <int N>
+using int_of = std::conditional_t<N == 1, int8_t, std::conditional_t<N == 2, int16_t, std::conditional_t<N == 4, int32_t, int64_t>>>;
+template <int N>
+using uint_of = std::make_unsigned_t<int_of<N>>;
+
+// Blocks of 256 threads for n items, at least one and at most `cap` (the kernel strides over the rest).  A kernel with
+// one thread per item and no stride loop passes kNoGridCap.
+constexpr int64_t kNoGridCap = INT32_MAX;
+inline unsigned grid_blocks(int64_t n, int64_t cap = 256 * 16) {
+  const int64_t g = (n + 255) / 256;
+  return static_cast<unsigned>(g < 1 ? 1 : g > cap ? cap : g);
+}
+
+// The launch shape of the [B_local, D_total] float layout copies (a2a_pooled_layout_kernel, pooled_exchange_kernel): one
+// thread per 16-B vector if the caller vouches for every width (`multiple_of_4`) and D_total and both pointers allow it,
+// else one per float.  launch(v, p, grid): v = integral_constant 4 | 1 (VEC), p = integral_constant 1 | 0 (PACK).
+template <typename F>
+void launch_layout_copy(const float* in, float* out, int B_local, int D_total, bool multiple_of_4, bool pack, F launch) {
+  const int vec = multiple_of_4 && D_total % 4 == 0 && all_aligned({in, out}, 15) ? 4 : 1;
+  const dim3 grid(grid_blocks(static_cast<int64_t>(B_local) * (D_total / vec), 256 * 32));
+  dispatch_value<4, 1>(vec, [&](auto v) { dispatch_value<1, 0>(pack, [&](auto p) { launch(v, p, grid); }); });
+}
+
 // The pointers of entry `name`: none null, `vec` (arrays that move as float4) 16-B aligned, `scalar` 4-B aligned.
 inline int check_pointers(const char* name, std::initializer_list<const void*> vec, std::initializer_list<const void*> scalar = {}) {
   for (const auto& ptrs : {vec, scalar}) {
@@ -132,6 +157,26 @@ __device__ __forceinline__ float4 ld4(const float* p) {
 }
 __device__ __forceinline__ void st4(float* p, float4 v) {
   *reinterpret_cast<float4*>(p) = v;
+}
+
+__device__ __forceinline__ float4 scaled(float4 v, float s) {
+  v.x *= s;
+  v.y *= s;
+  v.z *= s;
+  v.w *= s;
+  return v;
+}
+
+// Largest k in [0, n) with offsets[k] <= x, for ascending offsets with offsets[0] <= x: the segment that holds element x.
+// Of equal offsets it picks the last, so empty segments are never chosen.
+template <typename T, typename I, typename X>
+__device__ __forceinline__ I last_not_above(const T* offsets, I n, X x) {
+  I lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const I mid = (lo + hi) >> 1;
+    if (offsets[mid] <= x) lo = mid; else hi = mid;
+  }
+  return lo;
 }
 
 // _Float16 rows move as 4 halves = 8 B per lane (packed; never as scalar half accesses on the vector path).

@@ -58,19 +58,14 @@ __global__ __launch_bounds__(256) void pooled_exchange_kernel(const float* __res
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     const int b = static_cast<int>(i / cols);
     const int d = static_cast<int>(i - static_cast<int64_t>(b) * cols) * VEC;
-    int lo = 0, hi = a.Fg;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_col[mid] <= d) lo = mid; else hi = mid;
-    }
-    const int src = s_src[lo];
+    const int f = last_not_above(s_col, a.Fg, d);
+    const int src = s_src[f];
     if (src < -1) continue;  // data-parallel (replicated) feature: not part of the exchange
-    const int within = s_scol[lo] + (d - s_col[lo]);
+    const int within = s_scol[f] + (d - s_col[f]);
     const int64_t mat = static_cast<int64_t>(b) * a.D_total + d;
     if (PACK) {
       if (VEC == 4) {
-        float4 v = ld4(in + mat);
-        v.x *= a.scale; v.y *= a.scale; v.z *= a.scale; v.w *= a.scale;
+        const float4 v = scaled(ld4(in + mat), a.scale);
         if (src >= 0) {
           st4(out + s_off[src] + static_cast<int64_t>(b) * s_stride[src] + within, v);
         } else {
@@ -96,8 +91,7 @@ __global__ __launch_bounds__(256) void pooled_exchange_kernel(const float* __res
             v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
           }
         }
-        v.x *= a.scale; v.y *= a.scale; v.z *= a.scale; v.w *= a.scale;
-        st4(out + mat, v);
+        st4(out + mat, scaled(v, a.scale));
       } else {
         float v;
         if (src >= 0) {
@@ -112,23 +106,15 @@ __global__ __launch_bounds__(256) void pooled_exchange_kernel(const float* __res
   }
 }
 
-static int launch_exchange(const float* in, float* out, const ExchangeArgs& a, bool pack, bool vec, hipStream_t st) {
+static int launch_exchange(const float* in, float* out, const ExchangeArgs& a, bool pack, bool all_multiple_of_4, hipStream_t st) {
   const size_t lds = (static_cast<size_t>(a.Fg) * 3 + 1 + a.W + 1) * sizeof(int32_t) + static_cast<size_t>(a.W) * sizeof(int64_t);
   if (lds > 60000) {
     set_error("pooled exchange: too many features (%d) / ranks (%d)", a.Fg, a.W);
     return TBE_ERR_UNSUPPORTED;
   }
-  const int64_t total = static_cast<int64_t>(a.B_local) * (a.D_total / (vec ? 4 : 1));
-  int64_t g = (total + 255) / 256;
-  g = std::max<int64_t>(1, std::min<int64_t>(g, 256 * 32));
-  const dim3 grid(static_cast<unsigned>(g));
-  if (vec) {
-    if (pack) hipLaunchKernelGGL((pooled_exchange_kernel<4, true>), grid, dim3(256), lds, st, in, out, a);
-    else hipLaunchKernelGGL((pooled_exchange_kernel<4, false>), grid, dim3(256), lds, st, in, out, a);
-  } else {
-    if (pack) hipLaunchKernelGGL((pooled_exchange_kernel<1, true>), grid, dim3(256), lds, st, in, out, a);
-    else hipLaunchKernelGGL((pooled_exchange_kernel<1, false>), grid, dim3(256), lds, st, in, out, a);
-  }
+  launch_layout_copy(in, out, a.B_local, a.D_total, all_multiple_of_4, pack, [&](auto v, auto p, dim3 grid) {
+    hipLaunchKernelGGL((pooled_exchange_kernel<decltype(v)::value, decltype(p)::value != 0>), grid, dim3(256), lds, st, in, out, a);
+  });
   TBE_CHECK_LAUNCH("pooled exchange");
   return TBE_OK;
 }
@@ -145,9 +131,7 @@ static int exchange_entry(const float* in, float* out, const int32_t* feat_out_c
   if (static_cast<int64_t>(B_local) * D_total == 0) return TBE_OK;
   TBE_REQUIRE(in && out && feat_out_col && feat_src && feat_slab_col && slab_offset && slab_stride, "%s: null pointer", name);
   ExchangeArgs a{feat_out_col, feat_src, feat_slab_col, slab_offset, slab_stride, Fg, W, B_local, D_total, scale};
-  const bool vec = all_multiple_of_4 && (D_total % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-  return launch_exchange(in, out, a, pack, vec, static_cast<hipStream_t>(stream));
+  return launch_exchange(in, out, a, pack, all_multiple_of_4 != 0, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int tbe_pooled_exchange_unpack(const float* recv, float* out, const int32_t* feat_out_col,

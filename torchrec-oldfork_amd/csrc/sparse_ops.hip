@@ -136,35 +136,27 @@ static size_t scan_ws_bytes(int64_t n) {
 }
 
 // ---------------------------------------------------------------------------------------
-// permute_2D data copy: one wave per 64 consecutive OUTPUT segments; the wave's output
-// range is contiguous, lanes stride over it (coalesced stores) and find their segment by
-// a 6-step cross-lane binary search over the 64 segment starts.
+// Wave segment search, shared by the permute data copy and expand_into_jagged_permute: a wave serves 64 consecutive
+// OUTPUT segments, whose output range is contiguous; its lanes stride over that range (coalesced stores) and find the
+// segment of their element by a 6-step cross-lane binary search over the 64 segment starts.
 // ---------------------------------------------------------------------------------------
-template <typename V, typename Wt>
-__global__ __launch_bounds__(256) void permute_2d_data_kernel(const int32_t* __restrict__ perm, int T_out, int B,
-                                                             const int64_t* __restrict__ in_offsets,
-                                                             const int64_t* __restrict__ out_offsets,
-                                                             const V* __restrict__ values, V* __restrict__ out_values,
-                                                             const Wt* __restrict__ weights, Wt* __restrict__ out_weights) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nseg = static_cast<int64_t>(T_out) * B;
-  const int64_t s0 = (static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6)) * kWave;
-  if (s0 >= nseg) return;
-  const int64_t s = s0 + lane;
-  int64_t ostart_l = 0, istart_l = 0;
-  const int64_t s_end = min(s0 + static_cast<int64_t>(kWave), nseg);
-  const int64_t range_begin = out_offsets[s0];
-  const int64_t range_end = out_offsets[s_end];
-  if (s < nseg) {
-    ostart_l = out_offsets[s];
-    const int64_t t = s / B;
-    const int64_t b = s - t * B;
-    istart_l = in_offsets[static_cast<int64_t>(perm[t]) * B + b];
-  } else {
-    ostart_l = range_end;  // sentinel: never selected by the search below
+struct WaveSegments {
+  int64_t ostart_l, istart_l;  // lane l: where segment s0 + l starts in the output and in the input
+
+  // `src_start(s)` is segment s's start in the input.  Lanes past the last segment hold `range_end`, the end of the
+  // wave's output range: a sentinel the search never selects, since every element lies below it.
+  template <typename T, typename SrcStart>
+  __device__ __forceinline__ WaveSegments(const T* __restrict__ out_offsets, int64_t s, int64_t nseg, int64_t range_end,
+                                          SrcStart src_start)
+      : ostart_l(range_end), istart_l(0) {
+    if (s < nseg) {
+      ostart_l = static_cast<int64_t>(out_offsets[s]);
+      istart_l = src_start(s);
+    }
   }
-  for (int64_t eb = range_begin; eb < range_end; eb += kWave) {
-    const int64_t e = eb + lane;
+
+  // Input position of output element e; every lane of the wave calls it together.
+  __device__ __forceinline__ int64_t source_of(int64_t e) const {
     // largest segment k in [0, 64) with ostart[k] <= e
     int k = 0;
 #pragma unroll
@@ -175,35 +167,46 @@ __global__ __launch_bounds__(256) void permute_2d_data_kernel(const int32_t* __r
     }
     const int64_t os = shfl64(ostart_l, k);
     const int64_t is = shfl64(istart_l, k);
+    return is + (e - os);
+  }
+};
+
+// permute_2D data copy (permute_1D is its B = 1 case).
+template <typename V, typename Wt>
+__global__ __launch_bounds__(256) void permute_2d_data_kernel(const int32_t* __restrict__ perm, int T_out, int B,
+                                                             const int64_t* __restrict__ in_offsets,
+                                                             const int64_t* __restrict__ out_offsets,
+                                                             const V* __restrict__ values, V* __restrict__ out_values,
+                                                             const Wt* __restrict__ weights, Wt* __restrict__ out_weights) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nseg = static_cast<int64_t>(T_out) * B;
+  const int64_t s0 = (static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6)) * kWave;
+  if (s0 >= nseg) return;
+  const int64_t s_end = min(s0 + static_cast<int64_t>(kWave), nseg);
+  const int64_t range_begin = out_offsets[s0];
+  const int64_t range_end = out_offsets[s_end];
+  const WaveSegments seg(out_offsets, s0 + lane, nseg, range_end, [&](int64_t s) {
+    const int64_t t = s / B;
+    const int64_t b = s - t * B;
+    return in_offsets[static_cast<int64_t>(perm[t]) * B + b];
+  });
+  for (int64_t eb = range_begin; eb < range_end; eb += kWave) {
+    const int64_t e = eb + lane;
+    const int64_t src = seg.source_of(e);
     if (e < range_end) {
-      const int64_t src = is + (e - os);
       out_values[e] = values[src];
       if (weights != nullptr) out_weights[e] = weights[src];
     }
   }
 }
 
-template <typename LenT>
-__global__ __launch_bounds__(256) void permute_lengths_kernel(const int32_t* __restrict__ perm, int T_out, int B,
-                                                             const LenT* __restrict__ lengths, LenT* __restrict__ out) {
-  const int64_t n = static_cast<int64_t>(T_out) * B;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
-       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const int64_t t = i / B;
-    const int64_t b = i - t * B;
-    out[i] = lengths[static_cast<int64_t>(perm[t]) * B + b];
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // expand_into_jagged_permute: out[output_offset[i] + k] = input_offset[permute[i]] + k for k inside output segment i.
-// The scheme of permute_2d_data_kernel with the copy replaced by the index itself: a wave serves 64 consecutive output
-// segments, its lanes stride over their contiguous output range (coalesced stores) and find their segment by the
-// cross-lane search.  The recat of KJTAllToAll has FEW, LONG segments (F_local x W of them, a batch each), so the 64
-// segments' range is dealt to `splits` waves in interleaved 64-element chunks (wave j takes chunks j, j + splits, ...):
-// one wave alone took 1.37 ms for 32 segments of ~8192 on the MI355X.  Stores are confined to [0, output_size) and a
-// permute entry outside [0, P) reads nothing, so offsets that break the caller's contract cannot make the kernel touch
-// memory it was not given.
+// The scheme of permute_2d_data_kernel with the copy replaced by the index itself.  The recat of KJTAllToAll has FEW,
+// LONG segments (F_local x W of them, a batch each), so the 64 segments' range is dealt to `splits` waves in interleaved
+// 64-element chunks (wave j takes chunks j, j + splits, ...): one wave alone took 1.37 ms for 32 segments of ~8192 on the
+// MI355X.  Stores are confined to [0, output_size) and a permute entry outside [0, P) reads nothing, so offsets that
+// break the caller's contract cannot make the kernel touch memory it was not given.
 // ---------------------------------------------------------------------------------------
 constexpr int kExpandChunksPerWave = 16;  // chunks of 64 outputs a wave should find in an average range
 constexpr int kExpandMaxSplits = 4096;
@@ -220,59 +223,65 @@ __global__ __launch_bounds__(256) void expand_into_jagged_permute_kernel(const T
   const int64_t j = wave - group * splits;
   const int64_t s0 = group * kWave;
   if (s0 >= P) return;
-  const int64_t s = s0 + lane;
   const int64_t s_end = min(s0 + static_cast<int64_t>(kWave), P);
   const int64_t range_begin = static_cast<int64_t>(out_offsets[s0]);
   const int64_t range_end = min(static_cast<int64_t>(out_offsets[s_end]), output_size);
-  int64_t ostart_l = range_end, istart_l = 0;  // lanes past P: a sentinel the search below never selects
-  if (s < P) {
-    ostart_l = static_cast<int64_t>(out_offsets[s]);
+  const WaveSegments seg(out_offsets, s0 + lane, P, range_end, [&](int64_t s) {
     const int64_t p = static_cast<int64_t>(perm[s]);
-    if (static_cast<uint64_t>(p) < static_cast<uint64_t>(P)) istart_l = static_cast<int64_t>(in_offsets[p]);
-  }
+    return static_cast<uint64_t>(p) < static_cast<uint64_t>(P) ? static_cast<int64_t>(in_offsets[p]) : int64_t{0};
+  });
   for (int64_t eb = range_begin + j * kWave; eb < range_end; eb += static_cast<int64_t>(splits) * kWave) {
     const int64_t e = eb + lane;
-    // largest segment k in [0, 64) with ostart[k] <= e
-    int k = 0;
-#pragma unroll
-    for (int step = 32; step >= 1; step >>= 1) {
-      const int cand = k + step;
-      const int64_t v = shfl64(ostart_l, cand & 63);
-      if (cand < kWave && v <= e) k = cand;
-    }
-    const int64_t os = shfl64(ostart_l, k);
-    const int64_t is = shfl64(istart_l, k);
-    if (e >= 0 && e < range_end) out[e] = static_cast<T>(is + (e - os));
+    const int64_t src = seg.source_of(e);
+    if (e >= 0 && e < range_end) out[e] = static_cast<T>(src);
   }
 }
 
 // ---------------------------------------------------------------------------------------
-// block_bucketize_sparse_features.  Thread per bag for count and scatter (a bag's entries in
-// new_lengths / cursor are touched by that thread only => no atomics, stable order).
+// block_bucketize_sparse_features.  Thread per bag for count and scatter (a bag's (bucket, bag) counters are touched by
+// that thread only => no atomics, stable order).  The counters live in LDS while they fit (kLds, my_size <= 32): layout
+// [bucket][thread] puts a thread's counters in one bank column, so the increments never conflict, and there is no global
+// read-modify-write, no memset, and new_lengths is written coalesced.  Above that they live in global memory:
+// new_lengths / cursor [bucket][bag], zeroed by the host.
 // ---------------------------------------------------------------------------------------
-template <typename LenT, typename IdxT>
+constexpr int kBucketizeLdsMaxBuckets = 32;
+
+template <bool kLds, typename LenT, typename IdxT>
 __global__ __launch_bounds__(256) void bucketize_count_kernel(const int64_t* __restrict__ offsets, int64_t lengths_size,
                                                              int B, const IdxT* __restrict__ indices,
                                                              const IdxT* __restrict__ block_sizes, int my_size,
                                                              LenT* __restrict__ new_lengths) {
+  extern __shared__ int32_t cnt[];  // kLds: [my_size][256]
+  if constexpr (kLds) {
+    for (int p = 0; p < my_size; ++p) cnt[p * 256 + threadIdx.x] = 0;
+  }
   const int64_t bag = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (bag >= lengths_size) return;
   const int f = static_cast<int>(bag / B);
   const uint64_t blk = static_cast<uint64_t>(block_sizes[f]);
   const int64_t s = offsets[bag], e = offsets[bag + 1];
   for (int64_t i = s; i < e; ++i) {
-    const uint64_t idx = static_cast<uint64_t>(indices[i]);
-    const uint64_t p = idx / blk;
-    if (p < static_cast<uint64_t>(my_size)) new_lengths[p * lengths_size + bag] += 1;
+    const uint64_t p = static_cast<uint64_t>(indices[i]) / blk;
+    if (p >= static_cast<uint64_t>(my_size)) continue;
+    if constexpr (kLds) cnt[p * 256 + threadIdx.x] += 1;
+    else new_lengths[p * lengths_size + bag] += 1;
+  }
+  if constexpr (kLds) {
+    for (int p = 0; p < my_size; ++p)
+      new_lengths[static_cast<int64_t>(p) * lengths_size + bag] = static_cast<LenT>(cnt[p * 256 + threadIdx.x]);
   }
 }
 
-template <typename LenT, typename IdxT>
+template <bool kLds, typename LenT, typename IdxT>
 __global__ __launch_bounds__(256) void bucketize_scatter_kernel(
     const int64_t* __restrict__ offsets, int64_t lengths_size, int B, const IdxT* __restrict__ indices,
     const IdxT* __restrict__ block_sizes, int my_size, const float* __restrict__ weights,
     const int64_t* __restrict__ new_offsets, int32_t* __restrict__ cursor, IdxT* __restrict__ new_indices,
     float* __restrict__ new_weights, IdxT* __restrict__ new_pos, IdxT* __restrict__ unbucketize_permute) {
+  extern __shared__ int32_t cur[];  // kLds: [my_size][256] running position inside (bucket, bag); else `cursor` is
+  if constexpr (kLds) {
+    for (int p = 0; p < my_size; ++p) cur[p * 256 + threadIdx.x] = 0;
+  }
   const int64_t bag = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (bag >= lengths_size) return;
   const int f = static_cast<int>(bag / B);
@@ -286,64 +295,10 @@ __global__ __launch_bounds__(256) void bucketize_scatter_kernel(
       continue;
     }
     const int64_t slot = static_cast<int64_t>(p) * lengths_size + bag;
-    const int c = cursor[slot];
-    cursor[slot] = c + 1;
+    int c;  // this id's position inside its (bucket, bag)
+    if constexpr (kLds) c = cur[p * 256 + threadIdx.x]++;
+    else c = cursor[slot]++;
     const int64_t dst = new_offsets[slot] + c;
-    new_indices[dst] = static_cast<IdxT>(idx - p * blk);
-    if (weights != nullptr) new_weights[dst] = weights[i];
-    if (new_pos != nullptr) new_pos[dst] = static_cast<IdxT>(i - s);
-    if (unbucketize_permute != nullptr) unbucketize_permute[i] = static_cast<IdxT>(dst);
-  }
-}
-
-// Same two steps with the per-bag bucket counters in LDS (my_size <= 32): layout [bucket][thread]
-// puts a thread's counters in one bank column, so the increments never conflict.
-constexpr int kBucketizeLdsMaxBuckets = 32;
-
-template <typename LenT, typename IdxT>
-__global__ __launch_bounds__(256) void bucketize_count_lds_kernel(const int64_t* __restrict__ offsets,
-                                                                 int64_t lengths_size, int B,
-                                                                 const IdxT* __restrict__ indices,
-                                                                 const IdxT* __restrict__ block_sizes, int my_size,
-                                                                 LenT* __restrict__ new_lengths) {
-  extern __shared__ int32_t cnt[];  // [my_size][256]
-  for (int p = 0; p < my_size; ++p) cnt[p * 256 + threadIdx.x] = 0;
-  const int64_t bag = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (bag >= lengths_size) return;
-  const int f = static_cast<int>(bag / B);
-  const uint64_t blk = static_cast<uint64_t>(block_sizes[f]);
-  const int64_t s = offsets[bag], e = offsets[bag + 1];
-  for (int64_t i = s; i < e; ++i) {
-    const uint64_t p = static_cast<uint64_t>(indices[i]) / blk;
-    if (p < static_cast<uint64_t>(my_size)) cnt[p * 256 + threadIdx.x] += 1;
-  }
-  for (int p = 0; p < my_size; ++p)
-    new_lengths[static_cast<int64_t>(p) * lengths_size + bag] = static_cast<LenT>(cnt[p * 256 + threadIdx.x]);
-}
-
-template <typename LenT, typename IdxT>
-__global__ __launch_bounds__(256) void bucketize_scatter_lds_kernel(
-    const int64_t* __restrict__ offsets, int64_t lengths_size, int B, const IdxT* __restrict__ indices,
-    const IdxT* __restrict__ block_sizes, int my_size, const float* __restrict__ weights,
-    const int64_t* __restrict__ new_offsets, IdxT* __restrict__ new_indices, float* __restrict__ new_weights,
-    IdxT* __restrict__ new_pos, IdxT* __restrict__ unbucketize_permute) {
-  extern __shared__ int32_t cur[];  // [my_size][256] running position inside (bucket, bag)
-  for (int p = 0; p < my_size; ++p) cur[p * 256 + threadIdx.x] = 0;
-  const int64_t bag = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (bag >= lengths_size) return;
-  const int f = static_cast<int>(bag / B);
-  const uint64_t blk = static_cast<uint64_t>(block_sizes[f]);
-  const int64_t s = offsets[bag], e = offsets[bag + 1];
-  for (int64_t i = s; i < e; ++i) {
-    const uint64_t idx = static_cast<uint64_t>(indices[i]);
-    const uint64_t p = idx / blk;
-    if (p >= static_cast<uint64_t>(my_size)) {
-      if (unbucketize_permute != nullptr) unbucketize_permute[i] = static_cast<IdxT>(-1);
-      continue;
-    }
-    const int c = cur[p * 256 + threadIdx.x];
-    cur[p * 256 + threadIdx.x] = c + 1;
-    const int64_t dst = new_offsets[static_cast<int64_t>(p) * lengths_size + bag] + c;
     new_indices[dst] = static_cast<IdxT>(idx - p * blk);
     if (weights != nullptr) new_weights[dst] = weights[i];
     if (new_pos != nullptr) new_pos[dst] = static_cast<IdxT>(i - s);
@@ -375,26 +330,14 @@ __global__ __launch_bounds__(256) void a2a_pooled_layout_kernel(const float* __r
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     const int b = static_cast<int>(i / cols);
     const int d = static_cast<int>(i - static_cast<int64_t>(b) * cols) * VEC;
-    int lo = 0, hi = W;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (cum[mid] <= d) lo = mid; else hi = mid;
-    }
-    const int Dr = cum[lo + 1] - cum[lo];
-    const int64_t slab = static_cast<int64_t>(B_local) * cum[lo] + static_cast<int64_t>(b) * Dr + (d - cum[lo]);
+    const int r = last_not_above(cum, W, d);
+    const int Dr = cum[r + 1] - cum[r];
+    const int64_t slab = static_cast<int64_t>(B_local) * cum[r] + static_cast<int64_t>(b) * Dr + (d - cum[r]);
     const int64_t mat = static_cast<int64_t>(b) * D_total + d;
     const int64_t si = PACK ? mat : slab;
     const int64_t di = PACK ? slab : mat;
-    if (VEC == 4) {
-      float4 v = ld4(src + si);
-      v.x *= scale;
-      v.y *= scale;
-      v.z *= scale;
-      v.w *= scale;
-      st4(dst + di, v);
-    } else {
-      dst[di] = src[si] * scale;
-    }
+    if (VEC == 4) st4(dst + di, scaled(ld4(src + si), scale));
+    else dst[di] = src[si] * scale;
   }
 }
 
@@ -424,13 +367,9 @@ __global__ __launch_bounds__(256) void dense_to_jagged_2d_kernel(const float* __
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     const int d = static_cast<int>(i % D);
     const int64_t row = i / D;
-    int lo = 0, hi = B;  // largest b with offsets[b] <= row
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (offsets[mid] <= row) lo = mid; else hi = mid;
-    }
-    const int64_t l = row - offsets[lo];
-    values[i] = l < max_L ? dense[(static_cast<int64_t>(lo) * max_L + l) * D + d] : 0.f;
+    const int b = last_not_above(offsets, B, row);
+    const int64_t l = row - offsets[b];
+    values[i] = l < max_L ? dense[(static_cast<int64_t>(b) * max_L + l) * D + d] : 0.f;
   }
 }
 
@@ -449,20 +388,8 @@ __global__ __launch_bounds__(256) void offsets_range_kernel(const int64_t* __res
                                                            int64_t range_size, int64_t* __restrict__ out) {
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < range_size;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    int64_t lo = 0, hi = n;  // largest k with offsets[k] <= i
-    while (hi - lo > 1) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    out[i] = i - offsets[lo];
+    out[i] = i - offsets[last_not_above(offsets, n, i)];
   }
-}
-
-static unsigned grid_for(int64_t n, int per_block = 256, int64_t cap = 256 * 16) {
-  int64_t g = (n + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return static_cast<unsigned>(g);
 }
 
 }  // namespace tbe
@@ -483,9 +410,12 @@ extern "C" int tbe_cumsum(const void* in, void* out, int64_t n, int32_t elem_siz
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   int64_t* ws = static_cast<int64_t*>(workspace);
-  if (elem_size == 4)
-    return run_scan<int32_t, int32_t>(static_cast<const int32_t*>(in), static_cast<int32_t*>(out), n, nullptr, 1, mode, ws, nullptr, st);
-  return run_scan<int64_t, int64_t>(static_cast<const int64_t*>(in), static_cast<int64_t*>(out), n, nullptr, 1, mode, ws, nullptr, st);
+  int rc = TBE_OK;
+  dispatch_value<4, 8>(elem_size, [&](auto size) {
+    using T = int_of<decltype(size)::value>;
+    rc = run_scan<T, T>(static_cast<const T*>(in), static_cast<T*>(out), n, nullptr, 1, mode, ws, nullptr, st);
+  });
+  return rc;
 }
 
 extern "C" size_t tbe_permute_2d_workspace_bytes(int32_t T_in, int32_t T_out, int32_t B) {
@@ -507,40 +437,15 @@ extern "C" int tbe_permute_2d_lengths(const int32_t* permute, int32_t T_in, int3
   const int64_t n_in = static_cast<int64_t>(T_in) * B;
   const int64_t n_out = static_cast<int64_t>(T_out) * B;
   const int Bs = std::max(B, 1);
-  int rc;
-  if (len_elem_size == 4) {
-    rc = run_scan<int32_t, int64_t>(static_cast<const int32_t*>(lengths), in_offsets, n_in, nullptr, Bs, 0, ws, nullptr, st);
-    if (rc != TBE_OK) return rc;
-    rc = run_scan<int32_t, int64_t>(static_cast<const int32_t*>(lengths), out_offsets, n_out, permute, Bs, 0, ws,
-                                    static_cast<int32_t*>(out_lengths), st);
-  } else {
-    rc = run_scan<int64_t, int64_t>(static_cast<const int64_t*>(lengths), in_offsets, n_in, nullptr, Bs, 0, ws, nullptr, st);
-    if (rc != TBE_OK) return rc;
-    rc = run_scan<int64_t, int64_t>(static_cast<const int64_t*>(lengths), out_offsets, n_out, permute, Bs, 0, ws,
-                                    static_cast<int64_t*>(out_lengths), st);
-  }
+  int rc = TBE_OK;
+  dispatch_value<4, 8>(len_elem_size, [&](auto size) {
+    using LenT = int_of<decltype(size)::value>;
+    const LenT* len = static_cast<const LenT*>(lengths);
+    rc = run_scan<LenT, int64_t>(len, in_offsets, n_in, nullptr, Bs, 0, ws, nullptr, st);
+    // the gathered scan: out_offsets of the permuted rows, and the rows themselves into out_lengths
+    if (rc == TBE_OK) rc = run_scan<LenT, int64_t>(len, out_offsets, n_out, permute, Bs, 0, ws, static_cast<LenT*>(out_lengths), st);
+  });
   return rc;
-}
-
-template <typename V>
-static int launch_permute_data(const int32_t* permute, int T_out, int B, const int64_t* in_offsets,
-                               const int64_t* out_offsets, const void* values, void* out_values, const void* weights,
-                               void* out_weights, int w_elem, hipStream_t st) {
-  const int64_t nseg = static_cast<int64_t>(T_out) * B;
-  const unsigned grid = static_cast<unsigned>((nseg + 255) / 256);
-#define TBE_P(WT)                                                                                              \
-  hipLaunchKernelGGL((permute_2d_data_kernel<V, WT>), dim3(grid), dim3(256), 0, st, permute, T_out, B, in_offsets, \
-                     out_offsets, static_cast<const V*>(values), static_cast<V*>(out_values),                  \
-                     static_cast<const WT*>(weights), static_cast<WT*>(out_weights))
-  switch (w_elem) {
-    case 1: TBE_P(uint8_t); break;
-    case 2: TBE_P(uint16_t); break;
-    case 8: TBE_P(uint64_t); break;
-    default: TBE_P(uint32_t); break;
-  }
-#undef TBE_P
-  TBE_CHECK_LAUNCH("tbe_permute_2d_data");
-  return TBE_OK;
 }
 
 extern "C" int tbe_permute_2d_data(const int32_t* permute, int32_t T_out, int32_t B, const int64_t* in_offsets,
@@ -555,14 +460,18 @@ extern "C" int tbe_permute_2d_data(const int32_t* permute, int32_t T_out, int32_
   if (weights != nullptr)
     TBE_REQUIRE(w_elem_size == 1 || w_elem_size == 2 || w_elem_size == 4 || w_elem_size == 8,
                 "tbe_permute_2d_data: w_elem_size %d", w_elem_size);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int we = weights != nullptr ? w_elem_size : 4;
-  switch (val_elem_size) {
-    case 1: return launch_permute_data<uint8_t>(permute, T_out, B, in_offsets, out_offsets, values, out_values, weights, out_weights, we, st);
-    case 2: return launch_permute_data<uint16_t>(permute, T_out, B, in_offsets, out_offsets, values, out_values, weights, out_weights, we, st);
-    case 4: return launch_permute_data<uint32_t>(permute, T_out, B, in_offsets, out_offsets, values, out_values, weights, out_weights, we, st);
-    default: return launch_permute_data<uint64_t>(permute, T_out, B, in_offsets, out_offsets, values, out_values, weights, out_weights, we, st);
-  }
+  const dim3 grid(grid_blocks(static_cast<int64_t>(T_out) * B, kNoGridCap));  // 4 waves of 64 segments a block
+  dispatch_value<1, 2, 4, 8>(val_elem_size, [&](auto vsize) {
+    dispatch_value<1, 2, 4, 8>(weights != nullptr ? w_elem_size : 4, [&](auto wsize) {
+      using V = uint_of<decltype(vsize)::value>;
+      using Wt = uint_of<decltype(wsize)::value>;
+      hipLaunchKernelGGL((permute_2d_data_kernel<V, Wt>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), permute, T_out, B,
+                         in_offsets, out_offsets, static_cast<const V*>(values), static_cast<V*>(out_values),
+                         static_cast<const Wt*>(weights), static_cast<Wt*>(out_weights));
+    });
+  });
+  TBE_CHECK_LAUNCH("tbe_permute_2d_data");
+  return TBE_OK;
 }
 
 // permute_1D_sparse_data is the B = 1 case of permute_2D: the same scan and data kernels serve it.  The
@@ -608,14 +517,12 @@ extern "C" int tbe_expand_into_jagged_permute(const void* permute, const void* i
   const int64_t blocks = (groups * splits + 3) / 4;
   TBE_REQUIRE(blocks <= INT32_MAX, "tbe_expand_into_jagged_permute: P=%lld too large", (long long)P);
   const unsigned grid = static_cast<unsigned>(blocks);
-  if (elem_size == 4)
-    hipLaunchKernelGGL((expand_into_jagged_permute_kernel<int32_t>), dim3(grid), dim3(256), 0, st,
-                       static_cast<const int32_t*>(permute), P, static_cast<const int32_t*>(input_offset),
-                       static_cast<const int32_t*>(output_offset), output_size, splits, static_cast<int32_t*>(out));
-  else
-    hipLaunchKernelGGL((expand_into_jagged_permute_kernel<int64_t>), dim3(grid), dim3(256), 0, st,
-                       static_cast<const int64_t*>(permute), P, static_cast<const int64_t*>(input_offset),
-                       static_cast<const int64_t*>(output_offset), output_size, splits, static_cast<int64_t*>(out));
+  dispatch_value<4, 8>(elem_size, [&](auto size) {
+    using T = int_of<decltype(size)::value>;
+    hipLaunchKernelGGL((expand_into_jagged_permute_kernel<T>), dim3(grid), dim3(256), 0, st, static_cast<const T*>(permute), P,
+                       static_cast<const T*>(input_offset), static_cast<const T*>(output_offset), output_size, splits,
+                       static_cast<T*>(out));
+  });
   TBE_CHECK_LAUNCH("tbe_expand_into_jagged_permute");
   return TBE_OK;
 }
@@ -640,44 +547,27 @@ BucketizeWs carve_bucketize(void* ws, int64_t lengths_size, int32_t my_size) {
   return w;
 }
 
-template <typename LenT, typename IdxT>
-int run_bucketize(const void* lengths, int64_t lengths_size, const void* indices, int64_t N, const void* block_sizes,
-                  int F, int my_size, const float* weights, bool bucketize_pos, bool sequence, void* new_lengths,
-                  void* new_indices, float* new_weights, void* new_pos, void* unbucketize_permute,
-                  const BucketizeWs& w, hipStream_t st) {
-  (void)N;
+template <bool kLds, typename LenT, typename IdxT>
+int run_bucketize(const void* lengths, int64_t lengths_size, const void* indices, const void* block_sizes, int F, int my_size,
+                  const float* weights, bool bucketize_pos, bool sequence, void* new_lengths, void* new_indices,
+                  float* new_weights, void* new_pos, void* unbucketize_permute, const BucketizeWs& w, hipStream_t st) {
   const int B = static_cast<int>(lengths_size / F);
   const int64_t nl = lengths_size * my_size;
   int rc = run_scan<LenT, int64_t>(static_cast<const LenT*>(lengths), w.offsets, lengths_size, nullptr, 1, 0, w.scan_ws, nullptr, st);
   if (rc != TBE_OK) return rc;
-  const unsigned grid = static_cast<unsigned>((lengths_size + 255) / 256);
-  if (my_size <= kBucketizeLdsMaxBuckets) {
-    // per-thread bucket counters / cursors live in LDS ([bucket][thread], conflict-free): no global
-    // read-modify-write, no memsets, new_lengths written coalesced
-    const size_t lds = static_cast<size_t>(my_size) * 256 * sizeof(int32_t);
-    hipLaunchKernelGGL((bucketize_count_lds_kernel<LenT, IdxT>), dim3(grid), dim3(256), lds, st, w.offsets, lengths_size, B,
-                       static_cast<const IdxT*>(indices), static_cast<const IdxT*>(block_sizes), my_size,
-                       static_cast<LenT*>(new_lengths));
-    TBE_CHECK_LAUNCH("bucketize count");
-    rc = run_scan<LenT, int64_t>(static_cast<const LenT*>(new_lengths), w.new_offsets, nl, nullptr, 1, 0, w.scan_ws, nullptr, st);
-    if (rc != TBE_OK) return rc;
-    hipLaunchKernelGGL((bucketize_scatter_lds_kernel<LenT, IdxT>), dim3(grid), dim3(256), lds, st, w.offsets, lengths_size, B,
-                       static_cast<const IdxT*>(indices), static_cast<const IdxT*>(block_sizes), my_size, weights,
-                       w.new_offsets, static_cast<IdxT*>(new_indices), new_weights,
-                       bucketize_pos ? static_cast<IdxT*>(new_pos) : nullptr,
-                       sequence ? static_cast<IdxT*>(unbucketize_permute) : nullptr);
-    TBE_CHECK_LAUNCH("bucketize scatter");
-    return TBE_OK;
+  const dim3 grid(grid_blocks(lengths_size, kNoGridCap));  // a thread per bag
+  const size_t lds = kLds ? static_cast<size_t>(my_size) * 256 * sizeof(int32_t) : 0;
+  if constexpr (!kLds) {
+    (void)hipMemsetAsync(new_lengths, 0, nl * sizeof(LenT), st);
+    (void)hipMemsetAsync(w.cursor, 0, nl * sizeof(int32_t), st);
   }
-  (void)hipMemsetAsync(new_lengths, 0, nl * sizeof(LenT), st);
-  (void)hipMemsetAsync(w.cursor, 0, nl * sizeof(int32_t), st);
-  hipLaunchKernelGGL((bucketize_count_kernel<LenT, IdxT>), dim3(grid), dim3(256), 0, st, w.offsets, lengths_size, B,
+  hipLaunchKernelGGL((bucketize_count_kernel<kLds, LenT, IdxT>), grid, dim3(256), lds, st, w.offsets, lengths_size, B,
                      static_cast<const IdxT*>(indices), static_cast<const IdxT*>(block_sizes), my_size,
                      static_cast<LenT*>(new_lengths));
   TBE_CHECK_LAUNCH("bucketize count");
   rc = run_scan<LenT, int64_t>(static_cast<const LenT*>(new_lengths), w.new_offsets, nl, nullptr, 1, 0, w.scan_ws, nullptr, st);
   if (rc != TBE_OK) return rc;
-  hipLaunchKernelGGL((bucketize_scatter_kernel<LenT, IdxT>), dim3(grid), dim3(256), 0, st, w.offsets, lengths_size, B,
+  hipLaunchKernelGGL((bucketize_scatter_kernel<kLds, LenT, IdxT>), grid, dim3(256), lds, st, w.offsets, lengths_size, B,
                      static_cast<const IdxT*>(indices), static_cast<const IdxT*>(block_sizes), my_size, weights,
                      w.new_offsets, w.cursor, static_cast<IdxT*>(new_indices), new_weights,
                      bucketize_pos ? static_cast<IdxT*>(new_pos) : nullptr,
@@ -714,28 +604,29 @@ extern "C" int tbe_block_bucketize(const void* lengths, int32_t len_elem_size, i
     return TBE_ERR_WORKSPACE;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define TBE_B(LT, IT)                                                                                          \
-  return run_bucketize<LT, IT>(lengths, lengths_size, indices, N, block_sizes, F, my_size, weights, bucketize_pos != 0, \
-                               sequence != 0, new_lengths, new_indices, new_weights, new_pos, unbucketize_permute, w, st)
-  if (len_elem_size == 4 && idx_elem_size == 4) TBE_B(int32_t, int32_t);
-  if (len_elem_size == 4 && idx_elem_size == 8) TBE_B(int32_t, int64_t);
-  if (len_elem_size == 8 && idx_elem_size == 4) TBE_B(int64_t, int32_t);
-  TBE_B(int64_t, int64_t);
-#undef TBE_B
+  int rc = TBE_OK;
+  dispatch_value<4, 8>(len_elem_size, [&](auto lsize) {
+    dispatch_value<4, 8>(idx_elem_size, [&](auto isize) {
+      dispatch_value<1, 0>(my_size <= kBucketizeLdsMaxBuckets, [&](auto lds) {
+        rc = run_bucketize<decltype(lds)::value != 0, int_of<decltype(lsize)::value>, int_of<decltype(isize)::value>>(
+            lengths, lengths_size, indices, block_sizes, F, my_size, weights, bucketize_pos != 0, sequence != 0, new_lengths,
+            new_indices, new_weights, new_pos, unbucketize_permute, w, st);
+      });
+    });
+  });
+  return rc;
 }
 
-static int a2a_layout(const float* src, float* dst, const int32_t* dims, int W, int B_local, int D_total, float scale,
-                      bool pack, int vec_ok, hipStream_t st) {
+static int a2a_entry(const float* in, float* out, const int32_t* dim_sum_per_rank, int32_t W, int32_t B_local,
+                     int32_t D_total, int32_t dims_multiple_of_4, float scale, bool pack, void* stream, const char* name) {
+  TBE_REQUIRE(W > 0 && B_local >= 0 && D_total >= 0, "%s: bad sizes", name);
+  if (static_cast<int64_t>(B_local) * D_total == 0) return TBE_OK;
+  TBE_REQUIRE(in && out && dim_sum_per_rank, "%s: null pointer", name);
   const size_t lds = (static_cast<size_t>(W) + 1) * sizeof(int32_t);
-  const int64_t total = static_cast<int64_t>(B_local) * (D_total / (vec_ok ? 4 : 1));
-  const unsigned grid = grid_for(total, 256, 256 * 32);
-  if (vec_ok) {
-    if (pack) hipLaunchKernelGGL((a2a_pooled_layout_kernel<4, true>), dim3(grid), dim3(256), lds, st, src, dst, dims, W, B_local, D_total, scale);
-    else hipLaunchKernelGGL((a2a_pooled_layout_kernel<4, false>), dim3(grid), dim3(256), lds, st, src, dst, dims, W, B_local, D_total, scale);
-  } else {
-    if (pack) hipLaunchKernelGGL((a2a_pooled_layout_kernel<1, true>), dim3(grid), dim3(256), lds, st, src, dst, dims, W, B_local, D_total, scale);
-    else hipLaunchKernelGGL((a2a_pooled_layout_kernel<1, false>), dim3(grid), dim3(256), lds, st, src, dst, dims, W, B_local, D_total, scale);
-  }
+  launch_layout_copy(in, out, B_local, D_total, dims_multiple_of_4 != 0, pack, [&](auto v, auto p, dim3 grid) {
+    hipLaunchKernelGGL((a2a_pooled_layout_kernel<decltype(v)::value, decltype(p)::value != 0>), grid, dim3(256), lds,
+                       static_cast<hipStream_t>(stream), in, out, dim_sum_per_rank, W, B_local, D_total, scale);
+  });
   TBE_CHECK_LAUNCH("a2a pooled layout");
   return TBE_OK;
 }
@@ -743,23 +634,15 @@ static int a2a_layout(const float* src, float* dst, const int32_t* dims, int W, 
 extern "C" int tbe_a2a_pooled_unpack(const float* recv, float* out, const int32_t* dim_sum_per_rank, int32_t W,
                                      int32_t B_local, int32_t D_total, int32_t dims_multiple_of_4, float scale,
                                      void* stream) {
-  TBE_REQUIRE(W > 0 && B_local >= 0 && D_total >= 0, "tbe_a2a_pooled_unpack: bad sizes");
-  if (static_cast<int64_t>(B_local) * D_total == 0) return TBE_OK;
-  TBE_REQUIRE(recv && out && dim_sum_per_rank, "tbe_a2a_pooled_unpack: null pointer");
-  const int vec = dims_multiple_of_4 && (D_total % 4 == 0) && ((reinterpret_cast<uintptr_t>(recv) & 15) == 0) &&
-                  ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-  return a2a_layout(recv, out, dim_sum_per_rank, W, B_local, D_total, scale, false, vec, static_cast<hipStream_t>(stream));
+  return a2a_entry(recv, out, dim_sum_per_rank, W, B_local, D_total, dims_multiple_of_4, scale, false, stream,
+                   "tbe_a2a_pooled_unpack");
 }
 
 extern "C" int tbe_a2a_pooled_pack(const float* grad, float* send, const int32_t* dim_sum_per_rank, int32_t W,
                                    int32_t B_local, int32_t D_total, int32_t dims_multiple_of_4, float scale,
                                    void* stream) {
-  TBE_REQUIRE(W > 0 && B_local >= 0 && D_total >= 0, "tbe_a2a_pooled_pack: bad sizes");
-  if (static_cast<int64_t>(B_local) * D_total == 0) return TBE_OK;
-  TBE_REQUIRE(grad && send && dim_sum_per_rank, "tbe_a2a_pooled_pack: null pointer");
-  const int vec = dims_multiple_of_4 && (D_total % 4 == 0) && ((reinterpret_cast<uintptr_t>(grad) & 15) == 0) &&
-                  ((reinterpret_cast<uintptr_t>(send) & 15) == 0);
-  return a2a_layout(grad, send, dim_sum_per_rank, W, B_local, D_total, scale, true, vec, static_cast<hipStream_t>(stream));
+  return a2a_entry(grad, send, dim_sum_per_rank, W, B_local, D_total, dims_multiple_of_4, scale, true, stream,
+                   "tbe_a2a_pooled_pack");
 }
 
 extern "C" int tbe_jagged_2d_to_dense_f32(const float* values, const int64_t* offsets, int32_t B, int32_t D,
@@ -768,7 +651,7 @@ extern "C" int tbe_jagged_2d_to_dense_f32(const float* values, const int64_t* of
   const int64_t total = static_cast<int64_t>(B) * max_L * D;
   if (total == 0) return TBE_OK;
   TBE_REQUIRE(offsets && dense, "tbe_jagged_2d_to_dense_f32: null pointer");
-  hipLaunchKernelGGL(jagged_2d_to_dense_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), values,
+  hipLaunchKernelGGL(jagged_2d_to_dense_kernel, dim3(grid_blocks(total)), dim3(256), 0, static_cast<hipStream_t>(stream), values,
                      offsets, B, D, max_L, dense);
   TBE_CHECK_LAUNCH("tbe_jagged_2d_to_dense_f32");
   return TBE_OK;
@@ -779,7 +662,7 @@ extern "C" int tbe_dense_to_jagged_2d_f32(const float* dense, const int64_t* off
   TBE_REQUIRE(B >= 0 && D >= 0 && max_L >= 0 && N >= 0, "tbe_dense_to_jagged_2d_f32: bad sizes");
   if (N * D == 0) return TBE_OK;
   TBE_REQUIRE(B > 0 && dense && offsets && values, "tbe_dense_to_jagged_2d_f32: null pointer");
-  hipLaunchKernelGGL(dense_to_jagged_2d_kernel, dim3(grid_for(N * D)), dim3(256), 0, static_cast<hipStream_t>(stream), dense,
+  hipLaunchKernelGGL(dense_to_jagged_2d_kernel, dim3(grid_blocks(N * D)), dim3(256), 0, static_cast<hipStream_t>(stream), dense,
                      offsets, B, D, max_L, N, values);
   TBE_CHECK_LAUNCH("tbe_dense_to_jagged_2d_f32");
   return TBE_OK;
@@ -789,7 +672,7 @@ extern "C" int tbe_offsets_range(const int64_t* offsets, int64_t n, int64_t rang
   TBE_REQUIRE(n >= 0 && range_size >= 0, "tbe_offsets_range: bad sizes");
   if (range_size == 0) return TBE_OK;
   TBE_REQUIRE(n > 0 && offsets && out, "tbe_offsets_range: null pointer / empty offsets");
-  hipLaunchKernelGGL(offsets_range_kernel, dim3(grid_for(range_size)), dim3(256), 0, static_cast<hipStream_t>(stream), offsets, n,
+  hipLaunchKernelGGL(offsets_range_kernel, dim3(grid_blocks(range_size)), dim3(256), 0, static_cast<hipStream_t>(stream), offsets, n,
                      range_size, out);
   TBE_CHECK_LAUNCH("tbe_offsets_range");
   return TBE_OK;

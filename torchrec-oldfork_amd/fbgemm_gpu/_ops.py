@@ -81,36 +81,27 @@ def asynchronous_exclusive_cumsum(t_in: torch.Tensor) -> torch.Tensor:
     return _cumsum(t_in, 2)
 
 
-def permute_2D_sparse_data(
-    permute: torch.Tensor,
-    lengths: torch.Tensor,
-    values: torch.Tensor,
-    weights: Optional[torch.Tensor] = None,
-    permuted_lengths_sum: Optional[int] = None,
-) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
-    dev = require_gpu(permute, lengths, values, weights)
-    if lengths.dim() != 2:
-        raise RuntimeError("permute_2D_sparse_data: lengths must be 2-D [T, B]")
-    if lengths.dtype not in (torch.int32, torch.int64):
-        raise RuntimeError(f"permute_2D_sparse_data: lengths dtype {lengths.dtype}")
-    T_in, B = lengths.shape
-    T_out = permute.numel()
-    perm = permute.to(torch.int32).contiguous()
+def _permute_sparse_data(lengths_entry, data_entry, sizes, ws_bytes, out_shape, permute, lengths, values, weights,
+                         permuted_lengths_sum):
+    """The body permute_2D_sparse_data and permute_1D_sparse_data share: the `lengths_entry` call (offsets of input and
+    output segments, permuted lengths), the output size, the allocations and the `data_entry` call.  `sizes` are the
+    segment counts the two entries take after `permute`: (T_in, T_out, B) or (L, P); the data entry takes all but the first."""
+    dev = permute.device
+    perm = permute.to(torch.int32).contiguous().view(-1)
     lengths_c = lengths.contiguous()
     values_c = values.contiguous().view(-1)
     weights_c = weights.contiguous().view(-1) if weights is not None else None
     lib = _lib.load()
-    out_lengths = torch.empty((T_out, B), dtype=lengths.dtype, device=dev)
-    in_offsets = torch.empty(T_in * B + 1, dtype=torch.int64, device=dev)
-    out_offsets = torch.empty(T_out * B + 1, dtype=torch.int64, device=dev)
-    ws = workspace(lib.tbe_permute_2d_workspace_bytes(T_in, T_out, B), dev)
+    out_lengths = torch.empty(out_shape, dtype=lengths.dtype, device=dev)
+    in_offsets = torch.empty(lengths.numel() + 1, dtype=torch.int64, device=dev)
+    out_offsets = torch.empty(out_lengths.numel() + 1, dtype=torch.int64, device=dev)
+    ws = workspace(ws_bytes, dev)
     st = stream_ptr(dev)
     with torch.cuda.device(dev):
         check(
-            lib.tbe_permute_2d_lengths(ptr(perm), T_in, T_out, B, ptr(lengths_c),
-                                       lengths_c.element_size(), ptr(out_lengths), ptr(in_offsets),
-                                       ptr(out_offsets), ptr(ws), ws.numel(), st),
-            "tbe_permute_2d_lengths",
+            getattr(lib, lengths_entry)(ptr(perm), *sizes, ptr(lengths_c), lengths_c.element_size(), ptr(out_lengths),
+                                        ptr(in_offsets), ptr(out_offsets), ptr(ws), ws.numel(), st),
+            lengths_entry,
         )
         if permuted_lengths_sum is None:
             # data-dependent output size: one D2H read, as the reference op does
@@ -121,13 +112,31 @@ def permute_2D_sparse_data(
             if weights_c is not None else None
         )
         check(
-            lib.tbe_permute_2d_data(ptr(perm), T_out, B, ptr(in_offsets), ptr(out_offsets),
-                                    ptr(values_c), ptr(out_values), values_c.element_size(),
-                                    ptr(weights_c), ptr(out_weights),
-                                    weights_c.element_size() if weights_c is not None else 4, st),
-            "tbe_permute_2d_data",
+            getattr(lib, data_entry)(ptr(perm), *sizes[1:], ptr(in_offsets), ptr(out_offsets), ptr(values_c),
+                                     ptr(out_values), values_c.element_size(), ptr(weights_c), ptr(out_weights),
+                                     weights_c.element_size() if weights_c is not None else 4, st),
+            data_entry,
         )
     return out_lengths, out_values, out_weights
+
+
+def permute_2D_sparse_data(
+    permute: torch.Tensor,
+    lengths: torch.Tensor,
+    values: torch.Tensor,
+    weights: Optional[torch.Tensor] = None,
+    permuted_lengths_sum: Optional[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    require_gpu(permute, lengths, values, weights)
+    if lengths.dim() != 2:
+        raise RuntimeError("permute_2D_sparse_data: lengths must be 2-D [T, B]")
+    if lengths.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"permute_2D_sparse_data: lengths dtype {lengths.dtype}")
+    T_in, B = lengths.shape
+    T_out = permute.numel()
+    return _permute_sparse_data("tbe_permute_2d_lengths", "tbe_permute_2d_data", (T_in, T_out, B),
+                                _lib.load().tbe_permute_2d_workspace_bytes(T_in, T_out, B), (T_out, B), permute, lengths,
+                                values, weights, permuted_lengths_sum)
 
 
 def permute_1D_sparse_data(
@@ -139,7 +148,7 @@ def permute_1D_sparse_data(
 ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """out_lengths[i] = lengths[permute[i]]; segment i of the output values (and weights) is segment permute[i] of the
     input.  permute [P] need not have as many entries as lengths [L]: entries may repeat or be left out."""
-    dev = require_gpu(permute, lengths, values, weights)
+    require_gpu(permute, lengths, values, weights)
     if lengths.dim() != 1:
         raise RuntimeError("permute_1D_sparse_data: lengths must be 1-D [L]")
     if lengths.dtype not in (torch.int32, torch.int64):
@@ -147,42 +156,11 @@ def permute_1D_sparse_data(
     L, P = lengths.numel(), permute.numel()
     if L == 0 and P > 0:
         raise RuntimeError(f"permute_1D_sparse_data: {P} permute entries into empty lengths")
-    perm = permute.to(torch.int32).contiguous().view(-1)
-    lengths_c = lengths.contiguous()
-    values_c = values.contiguous().view(-1)
-    weights_c = weights.contiguous().view(-1) if weights is not None else None
-    lib = _lib.load()
-    ws_bytes = lib.tbe_permute_1d_workspace_bytes(L, P)
+    ws_bytes = _lib.load().tbe_permute_1d_workspace_bytes(L, P)
     if ws_bytes == 0:
         raise RuntimeError(f"permute_1D_sparse_data: L={L} / P={P} segments do not fit the kernels' 32-bit segment count")
-    out_lengths = torch.empty(P, dtype=lengths.dtype, device=dev)
-    in_offsets = torch.empty(L + 1, dtype=torch.int64, device=dev)
-    out_offsets = torch.empty(P + 1, dtype=torch.int64, device=dev)
-    ws = workspace(ws_bytes, dev)
-    st = stream_ptr(dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tbe_permute_1d_lengths(ptr(perm), L, P, ptr(lengths_c), lengths_c.element_size(),
-                                       ptr(out_lengths), ptr(in_offsets), ptr(out_offsets), ptr(ws),
-                                       ws.numel(), st),
-            "tbe_permute_1d_lengths",
-        )
-        if permuted_lengths_sum is None:
-            # data-dependent output size: one D2H read, as permute_2D_sparse_data does
-            permuted_lengths_sum = int(out_offsets[-1].item())
-        out_values = torch.empty(permuted_lengths_sum, dtype=values.dtype, device=dev)
-        out_weights = (
-            torch.empty(permuted_lengths_sum, dtype=weights_c.dtype, device=dev)
-            if weights_c is not None else None
-        )
-        check(
-            lib.tbe_permute_1d_data(ptr(perm), P, ptr(in_offsets), ptr(out_offsets), ptr(values_c),
-                                    ptr(out_values), values_c.element_size(), ptr(weights_c),
-                                    ptr(out_weights),
-                                    weights_c.element_size() if weights_c is not None else 4, st),
-            "tbe_permute_1d_data",
-        )
-    return out_lengths, out_values, out_weights
+    return _permute_sparse_data("tbe_permute_1d_lengths", "tbe_permute_1d_data", (L, P), ws_bytes, (P,), permute, lengths,
+                                values, weights, permuted_lengths_sum)
 
 
 def expand_into_jagged_permute(permute: torch.Tensor, input_offset: torch.Tensor, output_offset: torch.Tensor,
