@@ -164,7 +164,8 @@ OPTS = {
     "adagrad": (ADAGRAD, dict(eps=1e-3)),
     "adam_weight_decay_iteration3": (ADAM, dict(eps=1e-3, weight_decay=0.02, iteration=3)),
 }
-STATEFUL_CONFIGS = {"d128": ([128], "narrow_sum"), "d13_260": ([13, 260], "wide_mean"), "d1024": ([1024], "wide_sum")}
+STATEFUL_CONFIGS = {"d128": ([128], "narrow_sum"), "d13_260": ([13, 260], "wide_mean"), "d1024": ([1024], "wide_sum"),
+                    "d40_12": ([40, 12], "narrow_sum")}  # max_D <= 64: G = 16, four groups per wave, four-way LDS combine
 TOL = 2e-5  # rtol = atol of test_tbe_gpu.py::test_backward_fused_vs_oracle; the gradient itself is exact here
 
 

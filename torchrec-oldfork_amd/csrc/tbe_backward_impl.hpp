@@ -10,8 +10,8 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.hpp"
 #include "radix_sort.hpp"
+#include "tbe_row.hpp"
 
 namespace tbe {
 
@@ -87,43 +87,6 @@ __device__ __forceinline__ uint32_t payload_pos(PayT p) {
   else return static_cast<uint32_t>(p);
 }
 
-__device__ __forceinline__ float4 ldc(const float* row, int d, int D, bool vec) {
-  float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (vec) {
-    x = ld4(row + d);
-  } else {
-    if (d + 0 < D) x.x = row[d + 0];
-    if (d + 1 < D) x.y = row[d + 1];
-    if (d + 2 < D) x.z = row[d + 2];
-    if (d + 3 < D) x.w = row[d + 3];
-  }
-  return x;
-}
-__device__ __forceinline__ void stc(float* row, int d, int D, bool vec, float4 x) {
-  if (vec) {
-    st4(row + d, x);
-  } else {
-    if (d + 0 < D) row[d + 0] = x.x;
-    if (d + 1 < D) row[d + 1] = x.y;
-    if (d + 2 < D) row[d + 2] = x.z;
-    if (d + 3 < D) row[d + 3] = x.w;
-  }
-}
-
-__device__ __forceinline__ float4 ldc(const _Float16* row, int d, int D, bool vec) {
-  float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (vec) {
-    const half4 h = ldh4(row + d);
-    x = make_float4(static_cast<float>(h.x), static_cast<float>(h.y), static_cast<float>(h.z), static_cast<float>(h.w));
-  } else {
-    if (d + 0 < D) x.x = static_cast<float>(row[d + 0]);
-    if (d + 1 < D) x.y = static_cast<float>(row[d + 1]);
-    if (d + 2 < D) x.z = static_cast<float>(row[d + 2]);
-    if (d + 3 < D) x.w = static_cast<float>(row[d + 3]);
-  }
-  return x;
-}
-
 // Stochastic rounding of a finite FP32 value x to one of its two FP16 neighbours lo <= x <= hi:
 // P(hi) = (x - lo) / (hi - lo) in steps of 2^-13, from 13 random bits.  A representable x is kept.
 //  * |x| >= 2^-14 (normal halves): the 13 float mantissa bits a half drops are the position of x
@@ -172,7 +135,7 @@ struct RowRounding {
   uint32_t rowh;
 };
 __device__ __forceinline__ void stw(float* row, int d, int D, bool vec, float4 x, const RowRounding&) {
-  stc(row, d, D, vec, x);
+  store_cols(row, d, D, vec, x);
 }
 // _Float16 rows: nearest-even is the IEEE conversion (a plain cast); one 8-B store on the vector path.
 __device__ __forceinline__ void stw(_Float16* row, int d, int D, bool vec, float4 x, const RowRounding& rr) {
@@ -191,14 +154,7 @@ __device__ __forceinline__ void stw(_Float16* row, int d, int D, bool vec, float
     h.z = static_cast<_Float16>(x.z);
     h.w = static_cast<_Float16>(x.w);
   }
-  if (vec) {
-    sth4(row + d, h);
-  } else {
-    if (d + 0 < D) row[d + 0] = h.x;
-    if (d + 1 < D) row[d + 1] = h.y;
-    if (d + 2 < D) row[d + 2] = h.z;
-    if (d + 3 < D) row[d + 3] = h.w;
-  }
+  store_cols(row, d, D, vec, h);
 }
 // The hash of a row's key, where the table type and the rounding mode need one (0 otherwise): the update kernel
 // computes it next to the key it loaded, the fix-up kernel from the key of the run.
@@ -218,6 +174,25 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
+// The step every optimizer ends with: w - s * g to the table row, each lane its columns.
+template <typename WT, int G, int NV>
+__device__ __forceinline__ void store_step(WT* wrow, int D, bool vec, int gl, float s, const float4 (&w)[NV],
+                                           const float4 (&g)[NV], const RowRounding& rr) {
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int d = (v * G + gl) * 4;
+    if (d < D) stw(wrow, d, D, vec, fmaf4(-s, g[v], w[v]), rr);
+  }
+}
+
+// Max of v over the groups of a wave, on every lane (v is group-uniform): a wave-uniform trip count for loops that shuffle.
+template <int G>
+__device__ __forceinline__ int wave_max_over_groups(int v) {
+#pragma unroll
+  for (int o = 32; o >= G; o >>= 1) v = max(v, __shfl_xor(v, o, kWave));
+  return v;
+}
+
 // OPTC of the row-norm family (LAMB, PARTIAL_ROWWISE_ADAM, PARTIAL_ROWWISE_LAMB, LARS_SGD; chosen at run time inside
 // it): its own instantiations, so that the generic ones (OPTC = -1) keep their register footprint.
 constexpr int kOptNormFamily = -2;
@@ -225,20 +200,9 @@ __host__ __device__ __forceinline__ bool is_norm_family(int optimizer) {
   return optimizer >= TBE_OPT_LAMB && optimizer <= TBE_OPT_LARS_SGD;
 }
 
-// x . x added to s in column order; columns beyond D must be zero in x.
-__device__ __forceinline__ float sumsq4(float4 x, float s) {
-  s = fmaf(x.x, x.x, s);
-  s = fmaf(x.y, x.y, s);
-  s = fmaf(x.z, x.z, s);
-  return fmaf(x.w, x.w, s);
-}
-// Zeroes the columns of x (columns [d, d+4)) that lie beyond D: values computed from zero-filled loads need not be zero.
-__device__ __forceinline__ float4 mask_tail(float4 x, int d, int D) {
-  if (d + 1 >= D) x.y = 0.f;
-  if (d + 2 >= D) x.z = 0.f;
-  if (d + 3 >= D) x.w = 0.f;
-  return x;
-}
+// The exponential moving averages of g and g * g that ADAM and the row-norm family keep.
+__device__ __forceinline__ float ema_moment1(float b1, float m1, float g) { return fmaf(b1, m1, (1.f - b1) * g); }
+__device__ __forceinline__ float ema_moment2(float b2, float m2, float g) { return fmaf(b2, m2, (1.f - b2) * g * g); }
 
 // The row-norm family (formulas: include/tbe_hip.h, tbe_backward_*_ex_*).  Two passes over register-resident data: the
 // first updates the element-wise state (loaded and stored once, never held), leaves the update direction u in g's
@@ -249,7 +213,7 @@ __device__ __forceinline__ void apply_row_norm(const BwdArgs& a, int f, int64_t 
   const int optimizer = a.opt.optimizer;
   const float lr = a.opt.learning_rate, wd = a.opt.weight_decay;
   float* m1row = reinterpret_cast<float*>(a.feat_state0[f]) + local_row * D;
-  const bool m1vec = vec && ((reinterpret_cast<uintptr_t>(m1row) & 15) == 0);
+  const bool m1vec = vec && row_aligned(m1row);
   // columns beyond D are zero in w and g (never loaded)
   float ww = 0.f;
 #pragma unroll
@@ -263,21 +227,21 @@ __device__ __forceinline__ void apply_row_norm(const BwdArgs& a, int f, int64_t 
     const float wn = sqrtf(group_sum<G>(ww)), gn = sqrtf(group_sum<G>(gg));
     const float alr = (wn > 0.f && gn > 0.f) ? lr * a.eta * wn / (gn + wd * wn) : lr;
     const float mom = a.momentum;
-#define TBE_LARS1(c)                                        \
-  m.c = fmaf(mom, m.c, alr * fmaf(wd, w[v].c, g[v].c));     \
-  r.c = w[v].c - m.c;
+    const auto lars = [=](float& m, float& r, float w, float g) {
+      m = fmaf(mom, m, alr * fmaf(wd, w, g));
+      r = w - m;
+    };
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int d = (v * G + gl) * 4;
       if (d < D) {
-        float4 m = ldc(m1row, d, D, m1vec);
+        float4 m = load_cols(m1row, d, D, m1vec);
         float4 r;
-        TBE_LARS1(x) TBE_LARS1(y) TBE_LARS1(z) TBE_LARS1(w)
-        stc(m1row, d, D, m1vec, m);
+        each4(lars, m, r, w[v], g[v]);
+        store_cols(m1row, d, D, m1vec, m);
         stw(wrow, d, D, vec, r, rr);
       }
     }
-#undef TBE_LARS1
     return;
   }
   const float b1 = a.opt.beta1, b2 = a.opt.beta2, eps = a.opt.eps;
@@ -288,7 +252,7 @@ __device__ __forceinline__ void apply_row_norm(const BwdArgs& a, int f, int64_t 
   bool m2vec = false;
   if (lamb) {
     m2row = reinterpret_cast<float*>(a.feat_state1[f]) + local_row * D;
-    m2vec = vec && ((reinterpret_cast<uintptr_t>(m2row) & 15) == 0);
+    m2vec = vec && row_aligned(m2row);
   } else {
     float ss = 0.f;
 #pragma unroll
@@ -302,50 +266,37 @@ __device__ __forceinline__ void apply_row_norm(const BwdArgs& a, int f, int64_t 
   }
   const float m1div = adam ? a.bias1 : 1.f;
   float uu = 0.f;
-#define TBE_NORM_M1(c) m1.c = fmaf(b1, m1.c, (1.f - b1) * g[v].c);
-#define TBE_NORM_M2(c)                                   \
-  m2.c = fmaf(b2, m2.c, (1.f - b2) * g[v].c * g[v].c);   \
-  den.c = sqrtf(m2.c) + eps;
-#define TBE_NORM_U(c) u.c = (m1.c / m1div) / den.c + wd * w[v].c;
+  const auto moment1 = [=](float& m1, float g) { m1 = ema_moment1(b1, m1, g); };
+  const auto moment2_den = [=](float& m2, float& den, float g) {
+    m2 = ema_moment2(b2, m2, g);
+    den = sqrtf(m2) + eps;
+  };
+  const auto direction = [=](float& u, float m1, float den, float w) { u = (m1 / m1div) / den + wd * w; };
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     const int d = (v * G + gl) * 4;
     if (d < D) {
-      float4 m1 = ldc(m1row, d, D, m1vec);
-      TBE_NORM_M1(x) TBE_NORM_M1(y) TBE_NORM_M1(z) TBE_NORM_M1(w)
-      stc(m1row, d, D, m1vec, m1);
+      float4 m1 = load_cols(m1row, d, D, m1vec);
+      each4(moment1, m1, g[v]);
+      store_cols(m1row, d, D, m1vec, m1);
       float4 den = make_float4(den_row, den_row, den_row, den_row);
       if (lamb) {
-        float4 m2 = ldc(m2row, d, D, m2vec);
-        TBE_NORM_M2(x) TBE_NORM_M2(y) TBE_NORM_M2(z) TBE_NORM_M2(w)
-        stc(m2row, d, D, m2vec, m2);
+        float4 m2 = load_cols(m2row, d, D, m2vec);
+        each4(moment2_den, m2, den, g[v]);
+        store_cols(m2row, d, D, m2vec, m2);
       }
       float4 u;
-      TBE_NORM_U(x) TBE_NORM_U(y) TBE_NORM_U(z) TBE_NORM_U(w)
+      each4(direction, u, m1, den, w[v]);
       g[v] = mask_tail(u, d, D);
       uu = sumsq4(g[v], uu);
     }
   }
-#undef TBE_NORM_M1
-#undef TBE_NORM_M2
-#undef TBE_NORM_U
   float step = lr;
   if (!adam) {  // the trust ratio |w| / |u|, 1 when either norm is zero
     const float wn = sqrtf(group_sum<G>(ww)), un = sqrtf(group_sum<G>(uu));
     if (wn > 0.f && un > 0.f) step = lr * (wn / un);
   }
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const int d = (v * G + gl) * 4;
-    if (d < D) {
-      float4 r;
-      r.x = fmaf(-step, g[v].x, w[v].x);
-      r.y = fmaf(-step, g[v].y, w[v].y);
-      r.z = fmaf(-step, g[v].z, w[v].z);
-      r.w = fmaf(-step, g[v].w, w[v].w);
-      stw(wrow, d, D, vec, r, rr);
-    }
-  }
+  store_step<WT, G, NV>(wrow, D, vec, gl, step, w, g, rr);
 }
 
 // Applies the optimizer to one table row.  `g` = coalesced gradient columns held by this lane,
@@ -363,18 +314,7 @@ __device__ __forceinline__ void apply_row(const BwdArgs& a, int f, int64_t local
   const int optimizer = OPTC >= 0 ? OPTC : a.opt.optimizer;
   const float lr = a.opt.learning_rate;
   if (optimizer == TBE_OPT_EXACT_SGD) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int d = (v * G + gl) * 4;
-      if (d < D) {
-        float4 r;
-        r.x = fmaf(-lr, g[v].x, w[v].x);
-        r.y = fmaf(-lr, g[v].y, w[v].y);
-        r.z = fmaf(-lr, g[v].z, w[v].z);
-        r.w = fmaf(-lr, g[v].w, w[v].w);
-        stw(wrow, d, D, vec, r, rr);
-      }
-    }
+    store_step<WT, G, NV>(wrow, D, vec, gl, lr, w, g, rr);
   } else if (optimizer == TBE_OPT_EXACT_ROWWISE_ADAGRAD) {
     const float wd = a.opt.weight_decay;
     float ss = 0.f;
@@ -382,17 +322,8 @@ __device__ __forceinline__ void apply_row(const BwdArgs& a, int f, int64_t local
     for (int v = 0; v < NV; ++v) {
       const int d = (v * G + gl) * 4;
       if (d < D) {
-        if (wd != 0.f) {
-          g[v].x = fmaf(wd, w[v].x, g[v].x);
-          g[v].y = fmaf(wd, w[v].y, g[v].y);
-          g[v].z = fmaf(wd, w[v].z, g[v].z);
-          g[v].w = fmaf(wd, w[v].w, g[v].w);
-        }
-        // columns beyond D are zero in g (never loaded), so the vector form is safe
-        ss = fmaf(g[v].x, g[v].x, ss);
-        ss = fmaf(g[v].y, g[v].y, ss);
-        ss = fmaf(g[v].z, g[v].z, ss);
-        ss = fmaf(g[v].w, g[v].w, ss);
+        if (wd != 0.f) fma4(g[v], wd, w[v]);
+        ss = sumsq4(g[v], ss);  // columns beyond D are zero in g (never loaded)
       }
     }
     ss = group_sum<G>(ss);
@@ -400,70 +331,57 @@ __device__ __forceinline__ void apply_row(const BwdArgs& a, int f, int64_t local
     const float m_new = *m + ss / static_cast<float>(D);
     const float mult = lr / (sqrtf(m_new) + a.opt.eps);
     if (gl == 0) *m = m_new;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int d = (v * G + gl) * 4;
-      if (d < D) {
-        float4 r;
-        r.x = fmaf(-mult, g[v].x, w[v].x);
-        r.y = fmaf(-mult, g[v].y, w[v].y);
-        r.z = fmaf(-mult, g[v].z, w[v].z);
-        r.w = fmaf(-mult, g[v].w, w[v].w);
-        stw(wrow, d, D, vec, r, rr);
-      }
-    }
+    store_step<WT, G, NV>(wrow, D, vec, gl, mult, w, g, rr);
   } else if (optimizer == TBE_OPT_DENSE_GRAD) {
     float* grow = reinterpret_cast<float*>(a.feat_state0[f]) + local_row * D;
+    const bool gvec = vec && row_aligned(grow);
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int d = (v * G + gl) * 4;
-      if (d < D) stc(grow, d, D, vec && ((reinterpret_cast<uintptr_t>(grow) & 15) == 0), g[v]);
+      if (d < D) store_cols(grow, d, D, gvec, g[v]);
     }
   } else if (optimizer == TBE_OPT_EXACT_ADAGRAD) {
     float* mrow = reinterpret_cast<float*>(a.feat_state0[f]) + local_row * D;
-    const bool mvec = vec && ((reinterpret_cast<uintptr_t>(mrow) & 15) == 0);
+    const bool mvec = vec && row_aligned(mrow);
+    const float eps = a.opt.eps;
+    const auto accumulate = [](float& m, float g) { m = fmaf(g, g, m); };
+    const auto step = [=](float& r, float m, float w, float g) { r = w - lr * g / (sqrtf(m) + eps); };
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int d = (v * G + gl) * 4;
       if (d < D) {
-        float4 m = ldc(mrow, d, D, mvec);
-        m.x = fmaf(g[v].x, g[v].x, m.x);
-        m.y = fmaf(g[v].y, g[v].y, m.y);
-        m.z = fmaf(g[v].z, g[v].z, m.z);
-        m.w = fmaf(g[v].w, g[v].w, m.w);
-        stc(mrow, d, D, mvec, m);
+        float4 m = load_cols(mrow, d, D, mvec);
+        each4(accumulate, m, g[v]);
+        store_cols(mrow, d, D, mvec, m);
         float4 r;
-        r.x = w[v].x - lr * g[v].x / (sqrtf(m.x) + a.opt.eps);
-        r.y = w[v].y - lr * g[v].y / (sqrtf(m.y) + a.opt.eps);
-        r.z = w[v].z - lr * g[v].z / (sqrtf(m.z) + a.opt.eps);
-        r.w = w[v].w - lr * g[v].w / (sqrtf(m.w) + a.opt.eps);
+        each4(step, r, m, w[v], g[v]);
         stw(wrow, d, D, vec, r, rr);
       }
     }
   } else if (optimizer == TBE_OPT_ADAM) {
     float* m1row = reinterpret_cast<float*>(a.feat_state0[f]) + local_row * D;
     float* m2row = reinterpret_cast<float*>(a.feat_state1[f]) + local_row * D;
-    const bool mvec = vec && ((reinterpret_cast<uintptr_t>(m1row) & 15) == 0) &&
-                      ((reinterpret_cast<uintptr_t>(m2row) & 15) == 0);
+    const bool mvec = vec && row_aligned(m1row) && row_aligned(m2row);
     const float b1 = a.opt.beta1, b2 = a.opt.beta2, eps = a.opt.eps, wd = a.opt.weight_decay;
-#define TBE_ADAM1(c)                                                     \
-  m1.c = fmaf(b1, m1.c, (1.f - b1) * g[v].c);                            \
-  m2.c = fmaf(b2, m2.c, (1.f - b2) * g[v].c * g[v].c);                   \
-  r.c = w[v].c - lr * ((m1.c / a.bias1) / (sqrtf(m2.c / a.bias2) + eps) + wd * w[v].c);
+    const float bias1 = a.bias1, bias2 = a.bias2;
+    const auto adam = [=](float& m1, float& m2, float& r, float w, float g) {
+      m1 = ema_moment1(b1, m1, g);
+      m2 = ema_moment2(b2, m2, g);
+      r = w - lr * ((m1 / bias1) / (sqrtf(m2 / bias2) + eps) + wd * w);
+    };
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int d = (v * G + gl) * 4;
       if (d < D) {
-        float4 m1 = ldc(m1row, d, D, mvec);
-        float4 m2 = ldc(m2row, d, D, mvec);
+        float4 m1 = load_cols(m1row, d, D, mvec);
+        float4 m2 = load_cols(m2row, d, D, mvec);
         float4 r;
-        TBE_ADAM1(x) TBE_ADAM1(y) TBE_ADAM1(z) TBE_ADAM1(w)
-        stc(m1row, d, D, mvec, m1);
-        stc(m2row, d, D, mvec, m2);
+        each4(adam, m1, m2, r, w[v], g[v]);
+        store_cols(m1row, d, D, mvec, m1);
+        store_cols(m2row, d, D, mvec, m2);
         stw(wrow, d, D, vec, r, rr);
       }
     }
-#undef TBE_ADAM1
   }
 }
 
@@ -510,9 +428,7 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
 
   // The loop trip count must be wave-uniform for the shuffles: use the max span over groups.
   const int span = static_cast<int>(i1 - i0);
-  int max_span = span;
-#pragma unroll
-  for (int o = 32; o >= G; o >>= 1) max_span = max(max_span, __shfl_xor(max_span, o, kWave));
+  const int max_span = wave_max_over_groups<G>(span);
 
   for (int sb = 0; sb < max_span; sb += G) {
     const int64_t kk = i0 + sb + gl;
@@ -556,9 +472,7 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
     }
     const uint32_t rowh_k = row_hash_if_needed<WT>(a, static_cast<uint64_t>(key_k));
     const int n = active ? static_cast<int>(min<int64_t>(G, i1 - (i0 + sb))) : 0;
-    int max_n = n;
-#pragma unroll
-    for (int o = 32; o >= G; o >>= 1) max_n = max(max_n, __shfl_xor(max_n, o, kWave));
+    const int max_n = wave_max_over_groups<G>(n);
 
     for (int j = 0; j < max_n; j += U) {
       float4 x[U][NV];
@@ -586,14 +500,14 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
         fu[u] = __shfl(f_k, src, kWave);
         lrow[u] = shfl64(lrow_k, src);
         rowh[u] = sizeof(WT) == 2 ? static_cast<uint32_t>(__shfl(static_cast<int>(rowh_k), src, kWave)) : 0u;
-        const bool gvec = FAST || (((Du[u] & 3) == 0) && ((reinterpret_cast<uintptr_t>(gp) & 15) == 0));
-        vecu[u] = FAST || (((Du[u] & 3) == 0) && ((reinterpret_cast<uintptr_t>(wp[u]) & kRowAlignMask<WT>) == 0));
+        const bool gvec = FAST || row_vec(Du[u], gp);
+        vecu[u] = FAST || row_vec(Du[u], wp[u]);
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
           const int d = (v * G + gl) * 4;
-          x[u][v] = (val[u] && d < Du[u]) ? ldc(gp, d, Du[u], gvec) : make_float4(0.f, 0.f, 0.f, 0.f);
+          x[u][v] = (val[u] && d < Du[u]) ? load_cols(gp, d, Du[u], gvec) : make_float4(0.f, 0.f, 0.f, 0.f);
           // the current weight row (not needed when the coalesced gradient is only written out: DENSE_GRAD)
-          wr[u][v] = (OPTC != TBE_OPT_DENSE_GRAD && lst[u] && d < Du[u]) ? ldc(wp[u], d, Du[u], vecu[u])
+          wr[u][v] = (OPTC != TBE_OPT_DENSE_GRAD && lst[u] && d < Du[u]) ? load_cols(wp[u], d, Du[u], vecu[u])
                                                                           : make_float4(0.f, 0.f, 0.f, 0.f);
         }
       }
@@ -603,20 +517,10 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
           if (!FAST && a.max_gradient >= 0.f) {  // gradient clipping: the loaded element, before weight and MEAN division
             const float mg = a.max_gradient;
 #pragma unroll
-            for (int v = 0; v < NV; ++v) {
-              x[u][v].x = fminf(fmaxf(x[u][v].x, -mg), mg);
-              x[u][v].y = fminf(fmaxf(x[u][v].y, -mg), mg);
-              x[u][v].z = fminf(fmaxf(x[u][v].z, -mg), mg);
-              x[u][v].w = fminf(fmaxf(x[u][v].w, -mg), mg);
-            }
+            for (int v = 0; v < NV; ++v) x[u][v] = clamp4(x[u][v], -mg, mg);
           }
 #pragma unroll
-          for (int v = 0; v < NV; ++v) {
-            acc[v].x = fmaf(wt[u], x[u][v].x, acc[v].x);
-            acc[v].y = fmaf(wt[u], x[u][v].y, acc[v].y);
-            acc[v].z = fmaf(wt[u], x[u][v].z, acc[v].z);
-            acc[v].w = fmaf(wt[u], x[u][v].w, acc[v].w);
-          }
+          for (int v = 0; v < NV; ++v) fma4(acc[v], wt[u], x[u][v]);
           tail_open = !lst[u];
           if (lst[u]) {
             if (started_here) {
@@ -670,15 +574,6 @@ __global__ __launch_bounds__(256, MINW) void bwd_update_kernel(BwdArgs a) {
 // workgroup: 4*NG groups, LDS-staged partials, fixed combine order => bitwise reproducible.
 constexpr int kLongChain = 24;
 
-template <typename KeyT, int G, int NV>
-struct FixupRow {
-  int f;
-  int D;
-  int64_t lrow;
-  float* wrow;
-  bool vec;
-};
-
 template <int G, int NV>
 __device__ __forceinline__ void sum_partials(const float* __restrict__ base, int max_D_pad, int64_t first,
                                              int begin, int end, int D, int gl, float4 (&acc)[NV]) {
@@ -697,13 +592,58 @@ __device__ __forceinline__ void sum_partials(const float* __restrict__ base, int
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        acc[v].x += x[u][v].x;
-        acc[v].y += x[u][v].y;
-        acc[v].z += x[u][v].z;
-        acc[v].w += x[u][v].w;
-      }
+      for (int v = 0; v < NV; ++v) add4(acc[v], x[u][v]);
   }
+}
+
+// Finishes the run that origin `chunk` opened and the next `len` chunks continue (key_run: its row key) with N groups,
+// of which the caller is group i: one wave's NG, or (BLOCK) the workgroup's 4 * NG, staging in set[0..N).  The row comes
+// from the origin chunk's last contribution.  Every group sums its slice of the chain's partial_first rows and stages
+// the sum; group 0 (always the finisher) then adds, per column, to partial_last the groups' sums in ascending group order
+// (this order is the contract: the fixed combine order that makes the result bitwise reproducible) and applies the
+// optimizer.  BLOCK also selects the barrier between staging and combining: __syncthreads, else the wave's fence.
+template <typename WT, typename PayT, int G, int NV, int OPTC, bool BLOCK, typename KeyT>
+__device__ __forceinline__ void finish_run(const BwdArgs& a, int64_t chunk, KeyT key_run, int len, int i, int gl,
+                                           float4 (*set)[NV][G]) {
+  constexpr int N = (BLOCK ? 4 : 1) * (kWave / G);
+  const PayT pay = static_cast<const PayT*>(a.payload_sorted)[(chunk + 1) * a.C - 1];
+  const int f = static_cast<int>(payload_bag<PayT>(pay) / static_cast<uint32_t>(a.B));
+  const int D = a.feat_D[f];
+  const int64_t lrow = static_cast<int64_t>(key_run) - a.feat_row_base[f];
+  WT* wrow = reinterpret_cast<WT*>(a.feat_weights[f]) + lrow * D;
+  const bool vec = row_vec(D, wrow);
+  float4 acc[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int per = (len + N - 1) / N;
+  sum_partials<G, NV>(a.partial_first, a.max_D_pad, chunk + 1, min(len, i * per), min(len, (i + 1) * per), D, gl, acc);
+  if (N > 1) {
+    if (BLOCK) __syncthreads();  // the previous run's group 0 is done with `set`
+#pragma unroll
+    for (int v = 0; v < NV; ++v) set[i][v][gl] = acc[v];
+    if (BLOCK) {
+      __syncthreads();
+    } else {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  }
+  if (i != 0) return;
+  float4 tot[NV], w[NV];
+  const float* pl = a.partial_last + chunk * a.max_D_pad;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int d = (v * G + gl) * 4;
+    tot[v] = (d < D) ? ld4(pl + d) : make_float4(0.f, 0.f, 0.f, 0.f);
+    w[v] = (d < D) ? load_cols(wrow, d, D, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    if (!BLOCK) add4(tot[v], acc[v]);  // group 0's own sum: a wave has it in registers, the workgroup reads set[0]
+    for (int og = BLOCK ? 0 : 1; og < N; ++og) add4(tot[v], set[og][v][gl]);
+  }
+  apply_row<WT, G, NV, OPTC>(a, f, lrow, D, vec, gl, wrow, w, tot, row_hash_if_needed<WT>(a, static_cast<uint64_t>(key_run)));
 }
 
 template <typename WT, typename KeyT, typename PayT, int G, int NV, int OPTC>
@@ -721,7 +661,6 @@ __global__ __launch_bounds__(256) void bwd_fixup_kernel(BwdArgs a) {
   const int q = wave * NG + g;  // group index inside the block
   const int64_t nchunks = (a.N + a.C - 1) / a.C;
   const KeyT* __restrict__ skey = static_cast<const KeyT*>(a.keys_sorted);
-  const PayT* __restrict__ spay = static_cast<const PayT*>(a.payload_sorted);
   const int count = *a.origin_count;
 
   for (int base = blockIdx.x * 4; base < count; base += gridDim.x * 4) {  // block-uniform
@@ -748,50 +687,7 @@ __global__ __launch_bounds__(256) void bwd_fixup_kernel(BwdArgs a) {
           long_len[s] = len;
         }
       } else {
-        const PayT pay = spay[(chunk + 1) * a.C - 1];
-        const int f = static_cast<int>(payload_bag<PayT>(pay) / static_cast<uint32_t>(a.B));
-        const int D = a.feat_D[f];
-        const int64_t lrow = static_cast<int64_t>(key_run) - a.feat_row_base[f];
-        WT* wrow = reinterpret_cast<WT*>(a.feat_weights[f]) + lrow * D;
-        const bool vec = ((D & 3) == 0) && ((reinterpret_cast<uintptr_t>(wrow) & kRowAlignMask<WT>) == 0);
-        float4 acc[NV];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-        const int per = (len + NG - 1) / NG;
-        sum_partials<G, NV>(a.partial_first, a.max_D_pad, chunk + 1, min(len, g * per), min(len, (g + 1) * per), D, gl, acc);
-        if (NG > 1) {
-#pragma unroll
-          for (int v = 0; v < NV; ++v) part[q][v][gl] = acc[v];
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        if (g == 0) {
-          float4 tot[NV], w[NV];
-          const float* pl = a.partial_last + chunk * a.max_D_pad;
-#pragma unroll
-          for (int v = 0; v < NV; ++v) {
-            const int d = (v * G + gl) * 4;
-            tot[v] = (d < D) ? ld4(pl + d) : make_float4(0.f, 0.f, 0.f, 0.f);
-            w[v] = (d < D) ? ldc(wrow, d, D, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
-          }
-#pragma unroll
-          for (int v = 0; v < NV; ++v) {
-            tot[v].x += acc[v].x;
-            tot[v].y += acc[v].y;
-            tot[v].z += acc[v].z;
-            tot[v].w += acc[v].w;
-            for (int og = 1; og < NG; ++og) {
-              const float4 o = part[wave * NG + og][v][gl];
-              tot[v].x += o.x;
-              tot[v].y += o.y;
-              tot[v].z += o.z;
-              tot[v].w += o.w;
-            }
-          }
-          apply_row<WT, G, NV, OPTC>(a, f, lrow, D, vec, gl, wrow, w, tot,
-                            row_hash_if_needed<WT>(a, static_cast<uint64_t>(key_run)));
-        }
+        finish_run<WT, PayT, G, NV, OPTC, false>(a, chunk, key_run, len, g, gl, part + wave * NG);
       }
     }
     __syncthreads();
@@ -799,41 +695,7 @@ __global__ __launch_bounds__(256) void bwd_fixup_kernel(BwdArgs a) {
     for (int s = 0; s < nl; ++s) {  // block-uniform
       const int64_t chunk = long_chunk[s];
       const int len = long_len[s];
-      const KeyT key_run = skey[(chunk + 1) * a.C - 1];
-      const PayT pay = spay[(chunk + 1) * a.C - 1];
-      const int f = static_cast<int>(payload_bag<PayT>(pay) / static_cast<uint32_t>(a.B));
-      const int D = a.feat_D[f];
-      const int64_t lrow = static_cast<int64_t>(key_run) - a.feat_row_base[f];
-      WT* wrow = reinterpret_cast<WT*>(a.feat_weights[f]) + lrow * D;
-      const bool vec = ((D & 3) == 0) && ((reinterpret_cast<uintptr_t>(wrow) & kRowAlignMask<WT>) == 0);
-      float4 acc[NV];
-#pragma unroll
-      for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-      const int per = (len + NGB - 1) / NGB;
-      sum_partials<G, NV>(a.partial_first, a.max_D_pad, chunk + 1, min(len, q * per), min(len, (q + 1) * per), D, gl, acc);
-      __syncthreads();  // previous iteration's readers are done with `part`
-#pragma unroll
-      for (int v = 0; v < NV; ++v) part[q][v][gl] = acc[v];
-      __syncthreads();
-      if (q == 0) {
-        float4 tot[NV], w[NV];
-        const float* pl = a.partial_last + chunk * a.max_D_pad;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          const int d = (v * G + gl) * 4;
-          tot[v] = (d < D) ? ld4(pl + d) : make_float4(0.f, 0.f, 0.f, 0.f);
-          w[v] = (d < D) ? ldc(wrow, d, D, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
-          for (int oq = 0; oq < NGB; ++oq) {
-            const float4 o = part[oq][v][gl];
-            tot[v].x += o.x;
-            tot[v].y += o.y;
-            tot[v].z += o.z;
-            tot[v].w += o.w;
-          }
-        }
-        apply_row<WT, G, NV, OPTC>(a, f, lrow, D, vec, gl, wrow, w, tot,
-                            row_hash_if_needed<WT>(a, static_cast<uint64_t>(key_run)));
-      }
+      finish_run<WT, PayT, G, NV, OPTC, true>(a, chunk, skey[(chunk + 1) * a.C - 1], len, q, gl, part);
     }
     __syncthreads();
   }
@@ -882,60 +744,74 @@ static int carve(void* ws, int64_t N, int32_t max_D, int32_t key_bits, BwdWorksp
   return TBE_OK;
 }
 
+using BwdKernel = void (*)(BwdArgs);
+
+// One launch of an update or fix-up kernel (256 threads), bracketed as `profile_slot` (-1: not bracketed).
+static int launch_bwd(const char* what, int profile_slot, BwdKernel kernel, unsigned grid, const BwdArgs& a, hipStream_t st) {
+  {
+    ProfileSpan span(profile_slot, st);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, a);
+  }
+  TBE_CHECK_LAUNCH(what);
+  return TBE_OK;
+}
+
+// The update kernel (OPTC, FAST, SKIP) of a (WT, KeyT, PayT, G, NV), or nullptr where none is built.  FAST kernels keep
+// U = 4 rows in flight at 4 waves per SIMD and exist for the one (G, NV) pair that can reach them, DENSE_GRAD (the
+// replicated tiny tables of a sharded collection) for FP32 tables only; the others take U from NV.  SKIP kernels exist
+// for what a skip-single call can be: float tables of dim <= 128 with bag payloads (backward_entry checks).
+template <typename WT, typename KeyT, typename PayT, int G, int NV, int OPTC, bool FAST, bool SKIP>
+static BwdKernel update_kernel() {
+  constexpr bool built = (!FAST || (G == 32 && NV == 1 && (OPTC != TBE_OPT_DENSE_GRAD || sizeof(WT) == 4))) &&
+                         (!SKIP || (std::is_same_v<WT, float> && sizeof(PayT) == 4 && NV == 1 && G <= 32));
+  if constexpr (built) {
+    return bwd_update_kernel<WT, KeyT, PayT, G, NV, OPTC, FAST, FAST ? 4 : BwdUnroll<NV>::U, FAST ? 4 : 1, SKIP>;
+  } else {
+    return nullptr;
+  }
+}
+
 template <typename WT, typename KeyT, typename PayT, int G, int NV>
 static int launch_update(const BwdArgs& a, hipStream_t st) {
   constexpr int NG = kWave / G;
   const int64_t nchunks = (a.N + a.C - 1) / a.C;
   const int64_t groups_per_block = 4 * NG;
   const unsigned grid = static_cast<unsigned>((nchunks + groups_per_block - 1) / groups_per_block);
-  {
-    ProfileSpan span(TBE_PROFILE_BWD_UPDATE_KERNEL, st);
-    // (a launch with gradient clipping takes the generic kernel: the fast ones have no clamp)
-    const bool fast = a.fast_D > 0 && a.pooling_mode == TBE_POOL_SUM && a.psw == nullptr && a.max_gradient < 0.f;
-    const int oc = a.opt.optimizer;
-#define TBE_UPD(OPTC, FAST_, UU, MW) \
-  hipLaunchKernelGGL((bwd_update_kernel<WT, KeyT, PayT, G, NV, OPTC, FAST_, UU, MW>), dim3(grid), dim3(256), 0, st, a)
-#define TBE_UPD_SKIP(OPTC, FAST_, UU, MW) \
-  hipLaunchKernelGGL((bwd_update_kernel<WT, KeyT, PayT, G, NV, OPTC, FAST_, UU, MW, true>), dim3(grid), dim3(256), 0, st, a)
-    if (a.skip_single) {
-      // EXACT_SGD on float tables of dim <= 128 with bag payloads (backward_entry checks): the two kernels such a call takes
-      if constexpr (std::is_same_v<WT, float> && sizeof(PayT) == 4 && NV == 1 && G <= 32) {
-        if (G == 32 && fast) {
-          if constexpr (G == 32) TBE_UPD_SKIP(TBE_OPT_EXACT_SGD, true, 4, 4);
-        } else {
-          TBE_UPD_SKIP(-1, false, BwdUnroll<NV>::U, 1);
-        }
-      } else {
-        set_error("tbe_backward update: no kernel that skips single contributions for this configuration");
-        return TBE_ERR_UNSUPPORTED;
-      }
-    } else if (is_norm_family(oc)) {
-      TBE_UPD(kOptNormFamily, false, BwdUnroll<NV>::U, 1);
-    } else if constexpr (G == 32 && NV == 1) {  // the fast kernels exist for the one (G, NV) pair that can reach them
-      if (fast && oc == TBE_OPT_EXACT_SGD) {
-        TBE_UPD(TBE_OPT_EXACT_SGD, true, 4, 4);
-      } else if (fast && oc == TBE_OPT_EXACT_ROWWISE_ADAGRAD) {
-        TBE_UPD(TBE_OPT_EXACT_ROWWISE_ADAGRAD, true, 4, 4);
-      } else if (fast && oc == TBE_OPT_DENSE_GRAD && sizeof(WT) == 4) {
-        // the replicated tiny tables of a sharded collection (dense gradient); FP32 tables only
-        if constexpr (sizeof(WT) == 4) TBE_UPD(TBE_OPT_DENSE_GRAD, true, 4, 4);
-      } else {
-        TBE_UPD(-1, false, BwdUnroll<NV>::U, 1);
-      }
-    } else {
-      TBE_UPD(-1, false, BwdUnroll<NV>::U, 1);
+  // (a launch with gradient clipping takes the generic kernel: the fast ones have no clamp)
+  const bool fast = a.fast_D > 0 && a.pooling_mode == TBE_POOL_SUM && a.psw == nullptr && a.max_gradient < 0.f;
+  const int oc = a.opt.optimizer;
+  const bool skip = a.skip_single != 0, norm = is_norm_family(oc);
+  // The kernel of a call: the first row whose condition holds and whose kernel is built.
+  const struct {
+    bool when;
+    BwdKernel kernel;
+  } table[] = {
+      {skip && fast, update_kernel<WT, KeyT, PayT, G, NV, TBE_OPT_EXACT_SGD, true, true>()},
+      {skip, update_kernel<WT, KeyT, PayT, G, NV, -1, false, true>()},
+      {!skip && norm, update_kernel<WT, KeyT, PayT, G, NV, kOptNormFamily, false, false>()},
+      {!skip && fast && oc == TBE_OPT_EXACT_SGD, update_kernel<WT, KeyT, PayT, G, NV, TBE_OPT_EXACT_SGD, true, false>()},
+      {!skip && fast && oc == TBE_OPT_EXACT_ROWWISE_ADAGRAD,
+       update_kernel<WT, KeyT, PayT, G, NV, TBE_OPT_EXACT_ROWWISE_ADAGRAD, true, false>()},
+      {!skip && fast && oc == TBE_OPT_DENSE_GRAD, update_kernel<WT, KeyT, PayT, G, NV, TBE_OPT_DENSE_GRAD, true, false>()},
+      {!skip, update_kernel<WT, KeyT, PayT, G, NV, -1, false, false>()},
+  };
+  BwdKernel update = nullptr;
+  for (const auto& row : table) {
+    if (row.when && row.kernel != nullptr) {
+      update = row.kernel;
+      break;
     }
-#undef TBE_UPD
-#undef TBE_UPD_SKIP
   }
-  TBE_CHECK_LAUNCH("tbe_backward update");
+  if (update == nullptr) {  // only a skip-single call can get here: the last row is built for every configuration
+    set_error("tbe_backward update: no kernel that skips single contributions for this configuration");
+    return TBE_ERR_UNSUPPORTED;
+  }
+  const int rc = launch_bwd("tbe_backward update", TBE_PROFILE_BWD_UPDATE_KERNEL, update, grid, a, st);
+  if (rc != TBE_OK) return rc;
   const unsigned fgrid = static_cast<unsigned>(std::min<int64_t>((nchunks + 3) / 4, 1024));
-  if (is_norm_family(a.opt.optimizer))
-    hipLaunchKernelGGL((bwd_fixup_kernel<WT, KeyT, PayT, G, NV, kOptNormFamily>), dim3(fgrid), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((bwd_fixup_kernel<WT, KeyT, PayT, G, NV, -1>), dim3(fgrid), dim3(256), 0, st, a);
-  TBE_CHECK_LAUNCH("tbe_backward fixup");
-  return TBE_OK;
+  return launch_bwd("tbe_backward fixup", -1,
+                    norm ? bwd_fixup_kernel<WT, KeyT, PayT, G, NV, kOptNormFamily> : bwd_fixup_kernel<WT, KeyT, PayT, G, NV, -1>,
+                    fgrid, a, st);
 }
 
 constexpr int kPhasePrepare = 1;  // gradient-independent: linearize + sort

@@ -24,7 +24,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.hpp"
+#include "tbe_row.hpp"
 
 namespace tbe {
 
@@ -47,51 +47,17 @@ struct FwdArgs {
   int32_t bags_per_wave;  // 64, or 16 for small launches (more waves => more rows in flight)
 };
 
-__device__ __forceinline__ void fma4(float4& a, float w, const float4& x) {
-  a.x = fmaf(w, x.x, a.x);
-  a.y = fmaf(w, x.y, a.y);
-  a.z = fmaf(w, x.z, a.z);
-  a.w = fmaf(w, x.w, a.w);
-}
-
-// Loads columns [d, d+4) of a row; `vec` selects the 16-B path, otherwise 4 guarded scalars.
-__device__ __forceinline__ float4 load_cols(const float* row, int d, int D, bool vec) {
-  float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (vec) {
-    x = ld4(row + d);
-  } else {
-    if (d + 0 < D) x.x = row[d + 0];
-    if (d + 1 < D) x.y = row[d + 1];
-    if (d + 2 < D) x.z = row[d + 2];
-    if (d + 3 < D) x.w = row[d + 3];
-  }
-  return x;
-}
-// _Float16 rows: one 8-B load of 4 halves (hipcc does not merge scalar half loads), plain up-casts.
-__device__ __forceinline__ float4 load_cols(const _Float16* row, int d, int D, bool vec) {
-  float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (vec) {
-    const half4 h = ldh4(row + d);
-    x = make_float4(static_cast<float>(h.x), static_cast<float>(h.y), static_cast<float>(h.z), static_cast<float>(h.w));
-  } else {
-    if (d + 0 < D) x.x = static_cast<float>(row[d + 0]);
-    if (d + 1 < D) x.y = static_cast<float>(row[d + 1]);
-    if (d + 2 < D) x.z = static_cast<float>(row[d + 2]);
-    if (d + 3 < D) x.w = static_cast<float>(row[d + 3]);
-  }
-  return x;
-}
-__device__ __forceinline__ void store_cols(float* row, int d, int D, bool vec, float4 x) {
-  if (vec) {
-    st4(row + d, x);
-  } else {
-    if (d + 0 < D) row[d + 0] = x.x;
-    if (d + 1 < D) row[d + 1] = x.y;
-    if (d + 2 < D) row[d + 2] = x.z;
-    if (d + 3 < D) row[d + 3] = x.w;
+// The end of a bag: its pooled columns, scaled by 1 / len under MEAN (an empty bag stays 0), to the output row.
+template <int G, int NV>
+__device__ __forceinline__ void store_pooled(float* orow, int D, bool vec, int gl, bool mean_f, int len, const float4 (&acc)[NV]) {
+  float scale = 1.f;
+  if (mean_f) scale = len > 0 ? 1.f / static_cast<float>(len) : 0.f;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int d = (v * G + gl) * 4;
+    if (d < D) store_cols(orow, d, D, vec, mean_f ? scaled(acc[v], scale) : acc[v]);
   }
 }
-
 
 template <typename WT, int G, int NV, bool WEIGHTED, bool MEAN>
 __global__ __launch_bounds__(256) void tbe_fwd_short_kernel(FwdArgs a) {
@@ -110,9 +76,7 @@ __global__ __launch_bounds__(256) void tbe_fwd_short_kernel(FwdArgs a) {
   const int64_t Doff = a.feat_out_offset[f];
   const RowWindow win = load_window(a.feat_rows, a.feat_window, f);
   const bool mean_f = MEAN && (a.feat_pooling == nullptr || a.feat_pooling[f] == TBE_POOL_MEAN);
-  const bool vec = ((D & 3) == 0) && ((Doff & 3) == 0) && ((a.out_stride & 3) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(W) & kRowAlignMask<WT>) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0);
+  const bool vec = row_vec(D, W, Doff, a.out_stride, a.out);
 
   // Coalesced metadata: lane l owns bag (f, bag0 + l).
   const int64_t* __restrict__ offs = a.offsets + static_cast<int64_t>(f) * a.B;
@@ -209,25 +173,8 @@ __global__ __launch_bounds__(256) void tbe_fwd_short_kernel(FwdArgs a) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int b = bag0 + p + u * NG + g;
-      if (b < a.B && p + u * NG + g < bpw) {
-        float scale = 1.f;
-        if (mean_f) scale = len[u] > 0 ? 1.f / static_cast<float>(len[u]) : 0.f;
-        float* orow = a.out + static_cast<int64_t>(b) * a.out_stride + Doff;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          const int d = (v * G + gl) * 4;
-          if (d < D) {
-            float4 r = acc[u][v];
-            if (mean_f) {
-              r.x *= scale;
-              r.y *= scale;
-              r.z *= scale;
-              r.w *= scale;
-            }
-            store_cols(orow, d, D, vec, r);
-          }
-        }
-      }
+      if (b < a.B && p + u * NG + g < bpw)
+        store_pooled<G, NV>(a.out + static_cast<int64_t>(b) * a.out_stride + Doff, D, vec, gl, mean_f, len[u], acc[u]);
     }
   }
   if (a.bounds_errors != nullptr && nbad > 0 && gl == 0) atomicAdd(a.bounds_errors, nbad);
@@ -253,9 +200,7 @@ __global__ __launch_bounds__(256) void tbe_fwd_long_kernel(FwdArgs a) {
   const int64_t Doff = a.feat_out_offset[f];
   const RowWindow win = load_window(a.feat_rows, a.feat_window, f);
   const bool mean_f = MEAN && (a.feat_pooling == nullptr || a.feat_pooling[f] == TBE_POOL_MEAN);
-  const bool vec = ((D & 3) == 0) && ((Doff & 3) == 0) && ((a.out_stride & 3) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(W) & kRowAlignMask<WT>) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0);
+  const bool vec = row_vec(D, W, Doff, a.out_stride, a.out);
   int64_t s = a.offsets[bag];
   int64_t e = a.offsets[bag + 1];
   if (s < 0 || e > a.N || s > e) {  // malformed offsets: empty bag, counted, never dereferenced (wave-uniform)
@@ -314,36 +259,11 @@ __global__ __launch_bounds__(256) void tbe_fwd_long_kernel(FwdArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if (g == 0) {
 #pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        for (int og = 1; og < NG; ++og) {
-          const float4 o = part[wave][og][v][gl];
-          acc[v].x += o.x;
-          acc[v].y += o.y;
-          acc[v].z += o.z;
-          acc[v].w += o.w;
-        }
-      }
+      for (int v = 0; v < NV; ++v)
+        for (int og = 1; og < NG; ++og) add4(acc[v], part[wave][og][v][gl]);
     }
   }
-  if (g == 0) {
-    float scale = 1.f;
-    if (mean_f) scale = len > 0 ? 1.f / static_cast<float>(len) : 0.f;
-    float* orow = a.out + static_cast<int64_t>(b) * a.out_stride + Doff;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int d = (v * G + gl) * 4;
-      if (d < D) {
-        float4 r = acc[v];
-        if (mean_f) {
-          r.x *= scale;
-          r.y *= scale;
-          r.z *= scale;
-          r.w *= scale;
-        }
-        store_cols(orow, d, D, vec, r);
-      }
-    }
-  }
+  if (g == 0) store_pooled<G, NV>(a.out + static_cast<int64_t>(b) * a.out_stride + Doff, D, vec, gl, mean_f, len, acc);
   if (a.bounds_errors != nullptr && nbad > 0 && gl == 0) atomicAdd(a.bounds_errors, nbad);
 }
 
@@ -365,7 +285,7 @@ __global__ __launch_bounds__(256) void tbe_fwd_nobag_kernel(const uint64_t* feat
   const int wave = threadIdx.x >> 6;
   const int g = lane / G;
   const int gl = lane % G;
-  const bool vec = ((D & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
+  const bool vec = row_vec(D, out);
   const int64_t per_wave = NG * U;
   const int64_t nwaves = static_cast<int64_t>(gridDim.x) * 4;
   int nbad = 0;
@@ -391,7 +311,7 @@ __global__ __launch_bounds__(256) void tbe_fwd_nobag_kernel(const uint64_t* feat
       const WT* W = reinterpret_cast<const WT*>(feat_weights[f]);
       const bool ok = in && static_cast<uint64_t>(ix) < static_cast<uint64_t>(feat_rows[f]);
       if (in && !ok) ++nbad;
-      const bool v16 = vec && ((reinterpret_cast<uintptr_t>(W) & kRowAlignMask<WT>) == 0);
+      const bool v16 = vec && row_aligned(W);
       const WT* row = W + ix * D;
 #pragma unroll
       for (int v = 0; v < NV; ++v) {

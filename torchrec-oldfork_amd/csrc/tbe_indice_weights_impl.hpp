@@ -44,15 +44,6 @@ struct IwgArgs {
   int32_t bags_per_wave;
 };
 
-// Lane partial of <g, x> over the lane's 4 columns (fixed order; -ffp-contract=off keeps it).
-__device__ __forceinline__ float dot4(const float4& g, const float4& x, float acc) {
-  acc = fmaf(g.x, x.x, acc);
-  acc = fmaf(g.y, x.y, acc);
-  acc = fmaf(g.z, x.z, acc);
-  acc = fmaf(g.w, x.w, acc);
-  return acc;
-}
-
 // Sums 4 per-lane values over the G lanes of a group.  Lane gl of the group ends with the group
 // total of value iwg_slot(gl): steps xor 1 and xor 2 each halve the number of live values, the
 // remaining steps are a plain butterfly.  The order of additions depends on G only.
@@ -70,13 +61,6 @@ __device__ __forceinline__ float reduce4(const float (&p)[4], int gl) {
 #pragma unroll
   for (int m = 4; m < G; m <<= 1) r += __shfl_xor(r, m, kWave);
   return r;
-}
-
-template <typename WT>
-__device__ __forceinline__ bool iwg_vec(const IwgArgs& a, const WT* W, int D, int64_t Doff) {
-  return ((D & 3) == 0) && ((Doff & 3) == 0) && ((a.grad_stride & 3) == 0) &&
-         ((reinterpret_cast<uintptr_t>(W) & kRowAlignMask<WT>) == 0) &&
-         ((reinterpret_cast<uintptr_t>(a.grad_out) & 15) == 0);
 }
 
 template <typename WT, int G, int NV, bool MEAN>
@@ -97,7 +81,7 @@ __global__ __launch_bounds__(256) void tbe_iwg_short_kernel(IwgArgs a) {
   const int64_t Doff = a.feat_out_offset[f];
   const RowWindow win = load_window(a.feat_rows, a.feat_window, f);
   const bool mean_f = MEAN && (a.feat_pooling == nullptr || a.feat_pooling[f] == TBE_POOL_MEAN);
-  const bool vec = iwg_vec(a, W, D, Doff);
+  const bool vec = row_vec(D, W, Doff, a.grad_stride, a.grad_out);
 
   // Coalesced metadata: lane l owns bag (f, bag0 + l).
   const int64_t* __restrict__ offs = a.offsets + static_cast<int64_t>(f) * a.B;
@@ -188,7 +172,7 @@ __global__ __launch_bounds__(256) void tbe_iwg_long_kernel(IwgArgs a) {
   const int64_t Doff = a.feat_out_offset[f];
   const RowWindow win = load_window(a.feat_rows, a.feat_window, f);
   const bool mean_f = MEAN && (a.feat_pooling == nullptr || a.feat_pooling[f] == TBE_POOL_MEAN);
-  const bool vec = iwg_vec(a, W, D, Doff);
+  const bool vec = row_vec(D, W, Doff, a.grad_stride, a.grad_out);
   const int64_t s = a.offsets[bag];
   const int64_t e = a.offsets[bag + 1];
   if (s < 0 || e > a.N || s > e || s == e) return;  // malformed or empty (wave-uniform): nothing to write
