@@ -1131,6 +1131,59 @@ int tbe_criteo_batch_i64(const tbe_criteo_segment* segs, int32_t nseg, int64_t B
 int tbe_criteo_batch_i32(const tbe_criteo_segment* segs, int32_t nseg, int64_t B, const int32_t* hashes, const int64_t* perm,
                          float* dense_out, int32_t* values_out, int32_t* labels_out, int32_t* bad_perm, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Quantized inference tables: row-wise INT8 / INT4 / INT2 storage, its quantizer and its pooled lookup.  They replace
+ * torch.ops.fbgemm.FloatToFusedNBitRowwiseQuantizedSBHalf (torchrec/quant/embedding_modules.py:79) and
+ * IntNBitTableBatchedEmbeddingBagsCodegen.__call__ (torchrec/quant/embedding_modules.py:168-184, :209-213).
+ *
+ * Format (fbgemm's; parity unpinned, the fbgemm submodule is absent from the reference tree).  Bit rate b = 8, 4 or 2;
+ * epb = 8 / b elements per byte; D a multiple of 2 * epb.  Element j of a row is an unsigned b-bit value q_j in byte j / epb
+ * at bit (j % epb) * b.  The header is two IEEE halves: scale, then bias.
+ *   compat layout  uint8 [R, D / epb + 4]: data first, the header in the last 4 bytes (what the op returns);
+ *   table layout   header in bytes 0..3, data from byte 4; row stride = D / epb + 4 rounded up to 16; padding bytes zero.
+ * Quantizing a float32 row x, every step in FP32, no contraction:
+ *   minimum = float(half(min_j x_j))                          (round to nearest even; the stored bias)
+ *   range   = max_j x_j - minimum
+ *   scale   = float(half(range == 0 ? 1 : range / (2^b - 1)));   if (scale == 0) scale = 1
+ *   inv     = 1 / scale;   if (isinf(inv)) { scale = 1; inv = 1; }
+ *   q_j     = clamp(lrintf((x_j - minimum) * inv), 0, 2^b - 1);   stored scale = half(scale)
+ * The dequantized value is fmaf(float(q), float(scale16), float(bias16)).
+ *
+ * tbe_quantize_nbit_f32: in [R, D] float32 with row stride in_row_stride (elements), read once, one launch.  The output
+ * layout is (data_offset, header_offset, out_row_stride in bytes): (4, 0, >= the table row stride) writes the table layout
+ * with 16-byte stores, padding included (out and out_row_stride on the 16-byte grid); (0, D / epb, >= D / epb + 4) writes the
+ * compat layout (out and out_row_stride even; each row leaves as the aligned 16-byte lines it covers plus 2-byte stores at its
+ * ends).  Errors, before any launch: bit_rate other than 8 / 4 / 2, D % (2 * epb) != 0, D > 4096, any other layout, a stride
+ * below the row, R * stride beyond 2^63, a null pointer with R > 0, a misaligned pointer or stride.  R == 0 launches nothing.
+ *
+ * tbe_forward_nbit_{i32,i64}: the pooled lookup over table-layout tables, ONE launch for all features; ids and offsets share
+ * the entry's integer type and are read as they are.  Per feature: feat_weights (table base, 16-byte aligned), feat_D,
+ * feat_bit_rate (8 / 4 / 2; features of different bit rates may share a launch), feat_row_bytes (the table's row stride: a
+ * multiple of 16, >= D / epb + 4; D <= 2048; a stride beyond the rounded row size is legal and its padding is never read), feat_rows, feat_out_offset, feat_pooling (as in tbe_forward_pooled_f32).  Like
+ * that entry the library does not read the feat_* arrays on the host.  out is float32 (out_f16 = 0) or float16 (1), addressed
+ * out[b * out_row_stride + feat_out_offset[f] + d], strides and offsets in elements.
+ * Arithmetic of a bag, FP32, in bag order (no float atomics; two runs give the same bits):
+ *   acc_d = fmaf(w_i * scale_i, q_id, acc_d);   bacc = fmaf(w_i, bias_i, bacc);   out_d = acc_d + bacc
+ * (w_i = per_sample_weights[i] or 1); MEAN multiplies out_d by 1.f / len; an empty bag gives +0; a float16 output is out_d
+ * rounded once, to nearest even.  An id outside [0, rows) forms no address, contributes zero and is counted in
+ * bounds_errors; a bag whose offsets are negative, decreasing or beyond N is empty and counted.  Row addresses are 64-bit.
+ * ---------------------------------------------------------------------------------- */
+/* torchrec/quant/embedding_modules.py:79 */
+int tbe_quantize_nbit_f32(const float* in, int64_t R, int32_t D, int64_t in_row_stride, int32_t bit_rate, uint8_t* out,
+                          int64_t out_row_stride, int32_t data_offset, int32_t header_offset, void* stream);
+/* torchrec/quant/embedding_modules.py:209-213 (the reference casts ids and offsets with .int() first) */
+int tbe_forward_nbit_i32(const uint64_t* feat_weights, const int32_t* feat_D, const int32_t* feat_bit_rate,
+                         const int32_t* feat_row_bytes, const int64_t* feat_rows, const int64_t* feat_out_offset,
+                         const int32_t* feat_pooling, int32_t F, int32_t B, const int32_t* indices, int64_t N,
+                         const int32_t* offsets, const float* per_sample_weights, int32_t pooling_mode, void* out,
+                         int32_t out_f16, int64_t out_row_stride, int32_t* bounds_errors, void* stream);
+/* torchrec/quant/embedding_modules.py:209-213; int64 ids and offsets, as a KeyedJaggedTensor holds them */
+int tbe_forward_nbit_i64(const uint64_t* feat_weights, const int32_t* feat_D, const int32_t* feat_bit_rate,
+                         const int32_t* feat_row_bytes, const int64_t* feat_rows, const int64_t* feat_out_offset,
+                         const int32_t* feat_pooling, int32_t F, int32_t B, const int64_t* indices, int64_t N,
+                         const int64_t* offsets, const float* per_sample_weights, int32_t pooling_mode, void* out,
+                         int32_t out_f16, int64_t out_row_stride, int32_t* bounds_errors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,135 @@
+"""Kernel timing of the quantized lookup (csrc/tbe_nbit.hip) next to tbe_forward_pooled_f32 on the same ids, and of the
+quantizer next to a device copy of its input bytes, at the Criteo-1TB shape (development tool; bench.py never takes these
+paths).  Every variant is timed once per round, the rounds alternate the variants, and the record keeps each variant's
+median, minimum and maximum over the rounds (HIP events around back-to-back C-ABI calls: `iters` of them, or as many as
+fill a window of 30 ms).
+Usage: python tools/nbitbench.py [--batch 65536,4096] [--pooling 1,20] [--cap ROWS] [--rounds 7] [--iters 20] [--json FILE]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+import _paths  # noqa: E402,F401
+from fbgemm_gpu import _lib  # noqa: E402
+from fbgemm_gpu.split_embedding_configs import SparseType  # noqa: E402
+from fbgemm_gpu.split_table_batched_embeddings_ops import (  # noqa: E402
+    ComputeDevice, EmbeddingLocation, IntNBitTableBatchedEmbeddingBagsCodegen, SplitTableBatchedEmbeddingBagsCodegen)
+
+CRITEO_ROWS = [45833188, 36746, 17245, 7413, 20243, 3, 7114, 1441, 62, 29275261, 1572176, 345138, 10, 2209,
+               11267, 128, 4, 974, 14, 48937457, 11316796, 40094537, 452104, 12606, 104, 35]
+TYPES = {"int8": SparseType.INT8, "int4": SparseType.INT4, "int2": SparseType.INT2}
+
+
+def timed(fn, iters):
+    """milliseconds per call of `iters` back-to-back calls (the queue stays full: device time, not launch time)"""
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / iters
+
+
+WINDOW_MS = 30.0  # every timed window lasts at least this long: a shorter one measures the clock and the scheduler
+
+
+def rounds_of(variants, rounds, iters):
+    """per variant: median / min / max over the rounds, and the calls per window (`iters`, or more to fill WINDOW_MS)"""
+    times, calls = {name: [] for name in variants}, {}
+    for name, fn in variants.items():  # warm-up (code objects, the ids' first trip through the caches) sizes the window
+        timed(fn, 2)
+        calls[name] = max(iters, int(WINDOW_MS / timed(fn, 5)) + 1)
+    for _ in range(rounds):
+        for name, fn in variants.items():
+            times[name].append(timed(fn, calls[name]))
+    return {name: {"median_us": 1e3 * statistics.median(t), "min_us": 1e3 * min(t), "max_us": 1e3 * max(t),
+                   "calls_per_window": calls[name]} for name, t in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", default="65536,4096")
+    ap.add_argument("--pooling", default="1,20")
+    ap.add_argument("--cap", type=int, default=0, help="cap rows per table (0 = full size: 85 GiB of float32 tables)")
+    ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=20, help="least calls per timed window")
+    ap.add_argument("--json", default="")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    lib, st = _lib.load(), None
+    rows = [min(r, args.cap) if args.cap else r for r in CRITEO_ROWS]
+    F, D = len(rows), args.dim
+    fp32 = SplitTableBatchedEmbeddingBagsCodegen([(r, D, EmbeddingLocation.DEVICE, ComputeDevice.CUDA) for r in rows], device=dev)
+    for w, r in zip(fp32.split_embedding_weights(), rows):
+        w.uniform_(-(1.0 / r) ** 0.5, (1.0 / r) ** 0.5)
+    record = {"rows": rows, "dim": D, "rounds": args.rounds, "iters": args.iters, "window_ms": WINDOW_MS, "lookup": [], "quantizer": []}
+
+    # the quantizer on the largest table, next to a device copy of the same input bytes
+    big = max(range(F), key=lambda t: rows[t])
+    src = fp32.split_embedding_weights()[big]
+    dst = torch.empty_like(src)
+    nbit = {}
+    for name, ty in TYPES.items():
+        m = nbit[name] = IntNBitTableBatchedEmbeddingBagsCodegen(
+            [(f"t{t}", r, D, ty, EmbeddingLocation.DEVICE) for t, r in enumerate(rows)], device=dev, row_alignment=16)
+        for t, w in enumerate(fp32.split_embedding_weights()):
+            m.quantize_table_(t, w)
+        res = rounds_of({"copy": lambda: dst.copy_(src), "quantize": lambda m=m: m.quantize_table_(big, src)}, args.rounds, args.iters)
+        in_bytes, out_bytes = src.numel() * 4, rows[big] * m.row_bytes[big]
+        rec = {"type": name, "rows": rows[big], "in_bytes": in_bytes, "out_bytes": out_bytes, **res}
+        rec["quantize_TBps"] = (in_bytes + out_bytes) / (res["quantize"]["median_us"] * 1e-6) / 1e12
+        rec["copy_TBps"] = 2 * in_bytes / (res["copy"]["median_us"] * 1e-6) / 1e12
+        record["quantizer"].append(rec)
+        print(json.dumps(rec), flush=True)
+    del dst
+
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    for B in [int(b) for b in args.batch.split(",")]:
+        for L in [int(p) for p in args.pooling.split(",")]:
+            ids = torch.cat([torch.randint(0, r, (B * L,), generator=g, device=dev, dtype=torch.int64) for r in rows])
+            offsets = torch.arange(F * B + 1, dtype=torch.int64, device=dev) * L
+            N = ids.numel()
+            lay = fp32._get_layout()
+            out32 = torch.empty((B, F * D), dtype=torch.float32, device=dev)
+            out16 = torch.empty((B, F * D), dtype=torch.float16, device=dev)
+
+            def run_fp32():
+                lib.tbe_forward_pooled_f32(lay.feat_weights.data_ptr(), lay.feat_D.data_ptr(), lay.feat_out_offset.data_ptr(),
+                                           lay.feat_rows.data_ptr(), F, B, D, ids.data_ptr(), N, offsets.data_ptr(), None, 0,
+                                           None, out32.data_ptr(), F * D, None, None, st)
+
+            variants, bytes_of = {"fp32": run_fp32}, {"fp32": N * (D * 4 + 8) + F * B * (8 + D * 4)}
+            for name in TYPES:
+                for f16 in (False, True):  # the output type is the entry's flag: one set of tables serves both
+                    m = nbit[name]
+                    meta = [x.data_ptr() for x in m._feature_meta()]
+                    out = out16 if f16 else out32
+
+                    def run(meta=meta, out=out, f16=f16):
+                        lib.tbe_forward_nbit_i64(*meta, None, F, B, ids.data_ptr(), N, offsets.data_ptr(), None, 0,
+                                                 out.data_ptr(), int(f16), F * D, None, st)
+
+                    key = f"{name}_out_{'f16' if f16 else 'f32'}"
+                    variants[key] = run
+                    bytes_of[key] = N * (m.row_bytes[0] + 8) + F * B * (8 + D * (2 if f16 else 4))
+            res = rounds_of(variants, args.rounds, args.iters)
+            for key, r in res.items():
+                r["algorithmic_bytes"] = bytes_of[key]
+                r["TBps"] = bytes_of[key] / (r["median_us"] * 1e-6) / 1e12
+            rec = {"batch": B, "pooling": L, "variants": res}
+            record["lookup"].append(rec)
+            print(json.dumps(rec), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(record, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -279,6 +279,12 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.POINTER(CriteoSegment), c_i32, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
        for t in ("i64", "i32")},
+    "tbe_quantize_nbit_f32": (
+        ctypes.c_int, [c_void_p, c_i64, c_i32, c_i64, c_i32, c_void_p, c_i64, c_i32, c_i32, c_void_p]),
+    **{f"tbe_forward_nbit_{t}": (
+        ctypes.c_int,
+        [c_void_p] * 7 + [c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_i64, c_void_p, c_void_p])
+       for t in ("i32", "i64")},
     **{f"tbe_jagged_to_padded_dense_{t}": (
         ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i32, c_float, c_i32, c_i32, c_void_p, c_void_p])
        for t in ("i64", "i32", "f32")},

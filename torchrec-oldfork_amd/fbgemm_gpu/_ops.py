@@ -12,6 +12,7 @@ Schemas are the ones the reference calls:
   * jagged_2d_to_dense                  examples/bert4rec/models/bert4rec.py:394-400
   * permute_pooled_embs(_auto_grad)     fbgemm_gpu/permute_pooled_embedding_modules.py, the callback of
                                         torchrec/distributed/sharding/cw_sharding.py:221-231
+  * FloatToFusedNBitRowwiseQuantizedSBHalf  torchrec/quant/embedding_modules.py:79
 Only the CUDA (= HIP on ROCm) dispatch key is registered: a CPU tensor raises
 ``NotImplementedError`` from the dispatcher — there is no CPU fallback in the product.
 """
@@ -42,6 +43,7 @@ _DEFS = [
     "Tensor inv_offset_dim_list, Tensor inv_permute_list) -> Tensor",
     "permute_pooled_embs_auto_grad(Tensor pooled_embs, Tensor offset_dim_list, Tensor permute_list, "
     "Tensor inv_offset_dim_list, Tensor inv_permute_list) -> Tensor",
+    "FloatToFusedNBitRowwiseQuantizedSBHalf(Tensor input, int bit_rate) -> Tensor",
 ]
 
 _def_lib = torch.library.Library("fbgemm", "DEF")
@@ -340,6 +342,38 @@ def _permute_pooled_backward(ctx, grad_out):
     return grad_in, None, None, None, None
 
 
+def quantize_nbit_rows(input: torch.Tensor, bit_rate: int, out: torch.Tensor, out_row_stride: int, data_offset: int,
+                       header_offset: int) -> None:
+    """Rows of `input` (float32 [R, D], unit column stride, any row stride) quantized into the uint8 storage `out` (its
+    first byte is row 0) in the layout (data_offset, header_offset, out_row_stride) of include/tbe_hip.h
+    `tbe_quantize_nbit_f32`: one launch of csrc/tbe_nbit.hip."""
+    dev = require_gpu(input, out)
+    if input.dim() != 2 or input.dtype != torch.float32:
+        raise RuntimeError("FloatToFusedNBitRowwiseQuantizedSBHalf: input must be float32 [R, D]")
+    R, D = input.shape
+    if bit_rate not in (8, 4, 2) or D == 0 or D % (2 * (8 // bit_rate)) != 0 or D > 4096:
+        raise RuntimeError(f"FloatToFusedNBitRowwiseQuantizedSBHalf: D={D} with bit_rate={bit_rate} is not supported: "
+                           "bit_rate is 8, 4 or 2 and D a multiple of 2 * (8 / bit_rate), at most 4096")
+    if input.stride(1) != 1 or (R > 1 and input.stride(0) < D):
+        input = input.contiguous()
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_quantize_nbit_f32(ptr(input), R, D, max(input.stride(0), D), bit_rate, ptr(out),
+                                                out_row_stride, data_offset, header_offset, stream_ptr(dev)),
+              "tbe_quantize_nbit_f32")
+
+
+def float_to_fused_nbit_rowwise_quantized_sb_half(input: torch.Tensor, bit_rate: int) -> torch.Tensor:
+    """uint8 [R, D / epb + 4]: the packed row, then scale and bias as two halves (the compat layout)."""
+    dev = require_gpu(input)
+    if input.dim() != 2:
+        raise RuntimeError("FloatToFusedNBitRowwiseQuantizedSBHalf: input must be float32 [R, D]")
+    R, D = input.shape
+    nb = D * bit_rate // 8 if bit_rate in (8, 4, 2) else 0
+    out = torch.empty((R, nb + 4), dtype=torch.uint8, device=dev)
+    quantize_nbit_rows(input, bit_rate, out, nb + 4, 0, nb)
+    return out
+
+
 torch.library.register_autograd("fbgemm::permute_pooled_embs_auto_grad", _permute_pooled_backward,
                                 setup_context=_permute_pooled_setup)
 torch.library.register_autograd("fbgemm::jagged_2d_to_dense", _jagged_2d_to_dense_backward,
@@ -358,3 +392,4 @@ _impl_lib.impl("permute_pooled_embs_auto_grad", permute_pooled_embs)
 # the variable-batch recat of KJTAllToAll (torchrec_amd/distributed/dist_data.py)
 _impl_lib.impl("permute_1D_sparse_data", permute_1D_sparse_data)
 _impl_lib.impl("expand_into_jagged_permute", expand_into_jagged_permute)
+_impl_lib.impl("FloatToFusedNBitRowwiseQuantizedSBHalf", float_to_fused_nbit_rowwise_quantized_sb_half)

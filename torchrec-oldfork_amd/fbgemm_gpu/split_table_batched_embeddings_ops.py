@@ -101,14 +101,203 @@ class OptimizerArgsView:
     momentum: float
 
 
-def rounded_row_size_in_bytes(dim: int, weight_ty: SparseType) -> int:
-    raise NotImplementedError("quantized inference TBE is out of scope of the MI355X hot path")
+def rounded_row_size_in_bytes(dim: int, weight_ty: SparseType, row_alignment: int = 16) -> int:
+    """Bytes of one table row: the elements (dim * bits / 8), for the integer types the 4-byte (scale, bias) header, rounded
+    up to `row_alignment` (include/tbe_hip.h "Quantized inference tables": the table layout's row stride)."""
+    bits = weight_ty.bit_rate()
+    if dim * bits % 8 != 0:
+        raise ValueError(f"dim {dim} of {weight_ty} does not fill whole bytes")
+    nbytes = dim * bits // 8 + (4 if bits <= 8 else 0)
+    return -(-nbytes // row_alignment) * row_alignment
+
+
+_NBIT_TYPES = (SparseType.INT8, SparseType.INT4, SparseType.INT2)
 
 
 class IntNBitTableBatchedEmbeddingBagsCodegen(nn.Module):
-    def __init__(self, *args, **kwargs) -> None:
+    """Inference-only pooled lookup over row-wise quantized INT8 / INT4 / INT2 tables (csrc/tbe_nbit.hip), with the
+    constructor the reference calls at torchrec/quant/embedding_modules.py:168-184.
+
+    ``embedding_specs``: ``[(name, rows, dim, SparseType, EmbeddingLocation)]``; tables of different bit rates and dims may
+    share the module and are served by ONE launch.  All tables live in one uint8 buffer in the table layout (header first,
+    rows of ``rounded_row_size_in_bytes(dim, ty, 16)`` bytes).  ``weight_lists``: per table ``(uint8 [rows, dim * bits / 8],
+    uint8 [rows, 4] scale and bias halves)``, copied in at construction."""
+
+    def __init__(
+        self,
+        embedding_specs: List[Tuple[str, int, int, SparseType, EmbeddingLocation]],
+        feature_table_map: Optional[List[int]] = None,
+        index_remapping: Optional[List[torch.Tensor]] = None,
+        pooling_mode: PoolingMode = PoolingMode.SUM,
+        device: Optional[torch.device] = None,
+        bounds_check_mode: BoundsCheckMode = BoundsCheckMode.WARNING,
+        weight_lists: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None,
+        pruning_hash_load_factor: float = 0.5,
+        use_array_for_index_remapping: bool = True,
+        output_dtype: SparseType = SparseType.FP16,
+        row_alignment: Optional[int] = None,
+    ) -> None:
         super().__init__()
-        raise NotImplementedError("quantized inference TBE is out of scope of the MI355X hot path")
+        if index_remapping is not None:
+            raise NotImplementedError("IntNBitTableBatchedEmbeddingBagsCodegen: index_remapping (pruned tables) is not implemented")
+        if not embedding_specs:
+            raise ValueError("embedding_specs is empty")
+        names, rows, dims, types, locations = zip(*embedding_specs)
+        bad = [str(loc) for loc in locations if EmbeddingLocation(loc) != EmbeddingLocation.DEVICE]
+        if bad:
+            raise NotImplementedError(f"IntNBitTableBatchedEmbeddingBagsCodegen: EmbeddingLocation {bad}: only "
+                                      "EmbeddingLocation.DEVICE tables are implemented (HOST would be CPU compute: there is "
+                                      "no CPU fallback)")
+        for ty in types:
+            if ty not in _NBIT_TYPES:
+                raise NotImplementedError(f"IntNBitTableBatchedEmbeddingBagsCodegen: weights_ty {ty}: this module serves INT8, "
+                                          "INT4 and INT2 tables; FP32 / FP16 tables belong to "
+                                          "SplitTableBatchedEmbeddingBagsCodegen")
+        self.pooling_mode = PoolingMode(pooling_mode)
+        if self.pooling_mode == PoolingMode.NONE:
+            raise NotImplementedError("IntNBitTableBatchedEmbeddingBagsCodegen: PoolingMode.NONE (sequence embeddings) is not "
+                                      "implemented")
+        if output_dtype not in (SparseType.FP16, SparseType.FP32):
+            raise NotImplementedError(f"IntNBitTableBatchedEmbeddingBagsCodegen: output_dtype {output_dtype}: only FP16 and "
+                                      "FP32 outputs are implemented")
+        if row_alignment not in (None, 16):
+            raise NotImplementedError(f"IntNBitTableBatchedEmbeddingBagsCodegen: row_alignment {row_alignment}: table rows "
+                                      "are read as aligned 16-byte chunks, so the alignment is 16")
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.current_device = torch.device(device)
+        if self.current_device.type not in ("cuda", "meta"):
+            raise RuntimeError(f"IntNBitTableBatchedEmbeddingBagsCodegen on device '{self.current_device}': this module only "
+                               "runs on a HIP device; there is no CPU fallback")
+        T = len(rows)
+        self.embedding_specs = list(embedding_specs)
+        self.table_names = list(names)
+        self.rows_per_table = [int(r) for r in rows]
+        self.dims_per_table = [int(d) for d in dims]
+        self.types_per_table = list(types)
+        for d, ty in zip(self.dims_per_table, types):
+            if d <= 0 or d > 2048 or d % (2 * (8 // ty.bit_rate())) != 0:
+                raise ValueError(f"embedding dim {d} of an {ty} table must be a multiple of {2 * (8 // ty.bit_rate())} in "
+                                 "(0, 2048]")
+        self.feature_table_map = list(feature_table_map) if feature_table_map is not None else list(range(T))
+        if any(t < 0 or t >= T for t in self.feature_table_map):
+            raise ValueError("feature_table_map entry out of range")
+        self.T, self.F = T, len(self.feature_table_map)
+        self.output_dtype = output_dtype
+        self.bounds_check_mode = BoundsCheckMode(bounds_check_mode)
+        self.row_bytes = [rounded_row_size_in_bytes(d, ty, 16) for d, ty in zip(self.dims_per_table, types)]
+        self.table_offsets = [0]
+        for r, rb in zip(self.rows_per_table, self.row_bytes):
+            self.table_offsets.append(self.table_offsets[-1] + r * rb)
+        self.feat_D = [self.dims_per_table[t] for t in self.feature_table_map]
+        self.D_offsets = [0]
+        for d in self.feat_D:
+            self.D_offsets.append(self.D_offsets[-1] + d)
+        self.total_D = self.D_offsets[-1]
+        # zeros: the padding bytes of every row stay zero whatever is assigned later
+        self.register_buffer("weights", torch.zeros(self.table_offsets[-1], dtype=torch.uint8, device=self.current_device),
+                             persistent=False)
+        self._meta_key, self._meta = None, None
+        self._bounds_errors: Optional[torch.Tensor] = None
+        if weight_lists is not None:
+            self.assign_embedding_weights(weight_lists)
+
+    def _table_rows(self, t: int) -> torch.Tensor:
+        """uint8 [rows, row bytes] view of table t (header, data, padding)."""
+        lo, hi = self.table_offsets[t], self.table_offsets[t + 1]
+        return self.weights.detach()[lo:hi].view(self.rows_per_table[t], self.row_bytes[t])
+
+    def split_embedding_weights(self, split_scale_shifts: bool = True) -> List[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
+        """Per table, views into the module's buffer: (data [rows, dim * bits / 8], scale_shift [rows, 4]), or with
+        ``split_scale_shifts=False`` (the whole rows [rows, row bytes]: header, data, padding; None)."""
+        out = []
+        for t in range(self.T):
+            rows = self._table_rows(t)
+            if split_scale_shifts:
+                nb = self.dims_per_table[t] * self.types_per_table[t].bit_rate() // 8
+                out.append((rows[:, 4:4 + nb], rows[:, :4]))
+            else:
+                out.append((rows, None))
+        return out
+
+    def assign_embedding_weights(self, q_weight_list: List[Tuple[torch.Tensor, Optional[torch.Tensor]]]) -> None:
+        """Copies (data, scale_shift) per table into the buffer (``initialize_weights`` then has nothing left to do)."""
+        if len(q_weight_list) != self.T:
+            raise ValueError(f"{len(q_weight_list)} weight pairs for {self.T} tables")
+        for (dst_w, dst_ss), (w, ss) in zip(self.split_embedding_weights(), q_weight_list):
+            if tuple(w.shape) != tuple(dst_w.shape) or ss is None or tuple(ss.shape) != tuple(dst_ss.shape):
+                raise ValueError(f"quantized weights of shape {tuple(w.shape)} / {None if ss is None else tuple(ss.shape)} "
+                                 f"for a table of {tuple(dst_w.shape)} / {tuple(dst_ss.shape)}")
+            dst_w.copy_(w.view(torch.uint8) if w.dtype != torch.uint8 else w)
+            dst_ss.copy_(ss.view(torch.uint8) if ss.dtype != torch.uint8 else ss)
+
+    def initialize_weights(self) -> None:
+        """The buffer is allocated (zeroed) at construction: nothing is deferred."""
+
+    def quantize_table_(self, t: int, weight: torch.Tensor) -> None:
+        """Table t from a float32 [rows, dim] tensor: the quantizer kernel writes the table layout in place."""
+        from . import _ops
+
+        if tuple(weight.shape) != (self.rows_per_table[t], self.dims_per_table[t]):
+            raise ValueError(f"table {t} is {(self.rows_per_table[t], self.dims_per_table[t])}, not {tuple(weight.shape)}")
+        _ops.quantize_nbit_rows(weight.detach(), self.types_per_table[t].bit_rate(), self._table_rows(t), self.row_bytes[t],
+                                4, 0)
+
+    def _feature_meta(self):
+        key = self.weights.data_ptr()
+        if self._meta_key != key:
+            dev, ftm = self.weights.device, self.feature_table_map  # follows the buffer: .to(other device) moves both
+
+            def dev_tensor(vals, dtype):
+                return torch.tensor(vals, dtype=dtype).to(dev)
+
+            self._meta = (
+                dev_tensor([key + self.table_offsets[t] for t in ftm], torch.int64),
+                dev_tensor(self.feat_D, torch.int32),
+                dev_tensor([self.types_per_table[t].bit_rate() for t in ftm], torch.int32),
+                dev_tensor([self.row_bytes[t] for t in ftm], torch.int32),
+                dev_tensor([self.rows_per_table[t] for t in ftm], torch.int64),
+                dev_tensor(self.D_offsets[:-1], torch.int64),
+            )
+            self._meta_key = key
+        return self._meta
+
+    def _errors(self) -> torch.Tensor:
+        if self._bounds_errors is None or self._bounds_errors.device != self.weights.device:
+            self._bounds_errors = torch.zeros(1, dtype=torch.int32, device=self.weights.device)
+        return self._bounds_errors
+
+    def bounds_check_errors(self) -> int:
+        """Out-of-range ids and malformed bags seen so far (they contribute zero rows).  Syncs."""
+        return int(self._errors().item())
+
+    def forward(self, indices: torch.Tensor, offsets: torch.Tensor,
+                per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        dev = require_gpu(indices, offsets, per_sample_weights, self.weights)
+        if indices.dtype not in (torch.int32, torch.int64):
+            raise RuntimeError(f"indices of dtype {indices.dtype}: int32 or int64")
+        if offsets.dtype != indices.dtype:  # F * B + 1 entries: the ids are never cast
+            offsets = offsets.to(indices.dtype)
+        indices, offsets = indices.contiguous().view(-1), offsets.contiguous().view(-1)
+        if (offsets.numel() - 1) % self.F != 0:
+            raise RuntimeError(f"offsets has {offsets.numel()} entries; expected F*B+1 with F={self.F}")
+        B = (offsets.numel() - 1) // self.F
+        if per_sample_weights is not None:
+            per_sample_weights = per_sample_weights.float().contiguous().view(-1)
+            if per_sample_weights.numel() != indices.numel():
+                raise RuntimeError("per_sample_weights must have one entry per index")
+        f16 = self.output_dtype == SparseType.FP16
+        out = torch.empty((B, self.total_D), dtype=torch.float16 if f16 else torch.float32, device=dev)
+        counter = None if self.bounds_check_mode in (BoundsCheckMode.IGNORE, BoundsCheckMode.NONE) else ptr(self._errors())
+        lib = _lib.load()
+        name = "tbe_forward_nbit_i32" if indices.dtype == torch.int32 else "tbe_forward_nbit_i64"
+        with torch.cuda.device(dev):
+            check(getattr(lib, name)(*(ptr(m) for m in self._feature_meta()), None, self.F, B, ptr(indices), indices.numel(),
+                                     ptr(offsets), ptr(per_sample_weights), int(self.pooling_mode), ptr(out), int(f16),
+                                     self.total_D, counter, stream_ptr(dev)), name)
+        if self.bounds_check_mode == BoundsCheckMode.FATAL and self.bounds_check_errors() > 0:
+            raise RuntimeError("BoundsCheckMode.FATAL: out-of-range indices or malformed bags in this lookup")
+        return out
 
 
 def _bit_length(n: int) -> int:

@@ -2,8 +2,9 @@
 import enum
 from dataclasses import dataclass, field
 from math import sqrt
-from typing import List, Optional
+from typing import Dict, List, Optional
 
+import torch
 from fbgemm_gpu.split_embedding_configs import SparseType
 from fbgemm_gpu.split_table_batched_embeddings_ops import PoolingMode
 
@@ -19,6 +20,23 @@ class PoolingType(enum.Enum):
 class DataType(enum.Enum):
     FP32 = "FP32"
     FP16 = "FP16"
+    INT8 = "INT8"
+    INT4 = "INT4"
+    INT2 = "INT2"
+
+
+DATA_TYPE_NUM_BITS: Dict[DataType, int] = {DataType.FP32: 32, DataType.FP16: 16, DataType.INT8: 8, DataType.INT4: 4,
+                                           DataType.INT2: 2}
+_INTEGER_DATA_TYPES = (DataType.INT8, DataType.INT4, DataType.INT2)
+
+
+def dtype_to_data_type(dtype: torch.dtype) -> DataType:
+    """The table data type a quantization config's weight dtype asks for (torchrec/modules/embedding_configs.py:48-56)."""
+    by_dtype = {torch.qint8: DataType.INT8, torch.quint8: DataType.INT8, torch.quint4x2: DataType.INT4,
+                torch.quint2x4: DataType.INT2}
+    if dtype not in by_dtype:
+        raise ValueError(f"Invalid data type {dtype}")
+    return by_dtype[dtype]
 
 
 def pooling_type_to_pooling_mode(p: PoolingType) -> PoolingMode:
@@ -27,19 +45,24 @@ def pooling_type_to_pooling_mode(p: PoolingType) -> PoolingMode:
 
 
 def data_type_to_sparse_type(d: DataType) -> SparseType:
-    return {DataType.FP32: SparseType.FP32, DataType.FP16: SparseType.FP16}[d]
+    return SparseType[d.name]
 
 
 def data_type_to_bits(d: DataType) -> int:
     """Bits per table element (the reference's DATA_TYPE_NUM_BITS, embedding_configs.py)."""
-    return {DataType.FP32: 32, DataType.FP16: 16}[d]
+    return DATA_TYPE_NUM_BITS[d]
 
 
 def sharded_tables_precision(sharded, replicated, what: str):
     """The one table precision of a sharded module: None when every table is FP32 (nothing is added to the fused
     parameters then), SparseType.FP16 when every sharded (table-wise / row-wise) table is FP16.  One TBE module serves a
     rank here, so a mix raises (the reference groups tables by data type into several TBEs:
-    embedding_sharding.py:412-468), and so does an FP16 DATA_PARALLEL table (dense parameters are float32)."""
+    embedding_sharding.py:412-468), and so does an FP16 DATA_PARALLEL table (dense parameters are float32).  Integer
+    (quantized inference) tables are not sharded here: they raise by name."""
+    quantized = [c.name for c in list(sharded) + list(replicated) if c.data_type in _INTEGER_DATA_TYPES]
+    if quantized:
+        raise NotImplementedError(f"{what}: tables {quantized} have an integer data type; sharded quantized collections are "
+                                  "not implemented (torchrec_amd.quant.EmbeddingBagCollection serves them unsharded)")
     bad_dp = [c.name for c in replicated if c.data_type != DataType.FP32]
     if bad_dp:
         raise NotImplementedError(f"{what}: DATA_PARALLEL tables {bad_dp} ask for {DataType.FP16.value} storage; replicated "
