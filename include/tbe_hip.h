@@ -1002,6 +1002,60 @@ int tbe_attention_backward_f32(const float* grad_out,
                                const uint8_t* key_valid, const float* lse, int64_t B, int32_t H, int32_t L, int32_t d,
                                float p, uint64_t seed, int64_t call, float* dq, float* dk, float* dv, void* stream);
 
+/* The passes of BERT4Rec's TransformerBlock around its GEMMs and its attention (examples/bert4rec/models/bert4rec.py:174-320:
+ * SublayerConnection  x + dropout(sublayer(norm(x))),  the feed-forward's dropout(relu(.)),  the block's final dropout),
+ * float32: the residual add, its dropouts and the LayerNorm of the NEXT sublayer in one launch with the row in registers.
+ * x, s, y, n, g_y, g_n, g_x, g_s are contiguous [R, N]; gamma, beta [N]; stats [R, 2] = (mean, rstd) per row.
+ *   forward   y = drop_out(x + drop_in(s))                      s may be NULL: y = drop_out(x)
+ *             mean = (sum_c y[c]) / N;  var = (sum_c (y[c] - mean)^2) / N  (two-pass);  rstd = 1 / sqrtf(var + eps)
+ *             n = ((y - mean) * rstd) * gamma + beta            wanted iff n != NULL; stats is written when n is
+ *             x and s are read once, y and n written once.  y == NULL: y is not written; allowed only when no dropout is
+ *             active and n is wanted (s == NULL then gives n = LayerNorm(x)).
+ *   backward  xhat = (y - mean) * rstd;  d = g_n * gamma;  c1 = (sum_c d) / N;  c2 = (sum_c d * xhat) / N
+ *             g   = g_y + rstd * ((d - c1) - xhat * c2)         g_y NULL = zero;  g_n NULL = no LayerNorm term: y, stats and
+ *                                                               gamma are not read (one of g_y, g_n must be given)
+ *             g_x = drop_out'(g);   g_s = drop_in'(g_x)         the forward's keep decisions and scales, drawn again
+ *             g_s is wanted iff non-NULL; with p_in == 0 it may alias g_x (written once).
+ *             grad_params[0, :] = grad_gamma = sum_r g_n * xhat;  grad_params[1, :] = grad_beta = sum_r g_n
+ *             grad_params NULL (frozen parameters): not computed, no workspace needed.  Otherwise the row blocks' sums go to
+ *             `workspace` (tbe_residual_layernorm_backward_workspace_bytes(R, N) bytes) and one launch over 2 N columns finishes
+ *             them in fixed order, as for tbe_swish_layernorm_backward_f32.
+ *   relu_dropout   forward  h = dropout(max(a, 0)) over n contiguous floats;  backward  g_a = h > 0 ? g_h * scale : 0
+ *             (scale = 1 / (1 - p), nothing multiplied with p == 0): h alone says which elements passed, since a dropped
+ *             element and a non-positive a both give h == 0.
+ * Dropout, 0 <= p < 1, beside the attention kernel's draw: the same fmix32 and c(seed, call), then
+ *        c2  = fmix32(c ^ 0x52dce729)                           a domain tag: no draw coincides with the attention's
+ *        w1  = fmix32(c2 ^ (site * 0x9e3779b1))
+ *        w2  = fmix32(w1 ^ (row * 0x85ebca6b))
+ *        r   = fmix32(w2 ^ (col * 0xc2b2ae35))
+ *   element (row, col) is kept iff r >= min(2^32 - 1, floor((double)p * 2^32)); kept elements are multiplied by the float
+ *   1 / (1 - p), dropped ones are +0.  `site` (uint32) tells the dropouts of a model apart (site_in for drop_in, site_out for
+ *   drop_out).  relu_dropout draws element i of its flat array with (row, col) = (hi32(i), lo32(i)).  p == 0 keeps
+ *   everything, multiplies by nothing, and (seed, call, site) do not matter.
+ * Each product and add is rounded on its own; no float atomics; every sum runs in an order fixed by (R, N): two runs are
+ * bit-identical.  A constant row gives var = 0, xhat = 0, rstd = 1 / sqrtf(eps): finite.
+ * Limits: N % 4 == 0, 4 <= N <= 4096, 0 <= R < 2^31, n % 4 == 0; every [R, N] / [N] / flat array and the workspace 16-B
+ * aligned (stats, grad_params 4 B); buffers do not overlap except g_s == g_x above.  Errors, before anything is launched
+ * and with no byte changed: TBE_ERR_INVALID_ARGUMENT for a bad N, R or n, p outside [0, 1), eps not finite or < 0, a null or
+ * misaligned pointer, a wanted output whose pointer is missing (y with a dropout active, both of y and n, stats with n,
+ * g_n with grad_params), a short workspace.  R == 0 / n == 0 launches nothing (the backward zeroes grad_params). */
+size_t tbe_residual_layernorm_backward_workspace_bytes(int64_t R, int32_t N);
+/* examples/bert4rec/models/bert4rec.py:217-257, 300-320 */
+int tbe_residual_layernorm_forward_f32(const float* x, const float* s, const float* gamma, const float* beta, float eps,
+                                       int64_t R, int32_t N, float p_in, uint32_t site_in, float p_out, uint32_t site_out,
+                                       uint64_t seed, int64_t call, float* y, float* n, float* stats, void* stream);
+/* the backward autograd builds for examples/bert4rec/models/bert4rec.py:217-257, 300-320 */
+int tbe_residual_layernorm_backward_f32(const float* g_y, const float* g_n, const float* y, const float* stats,
+                                        const float* gamma, int64_t R, int32_t N, float p_in, uint32_t site_in, float p_out,
+                                        uint32_t site_out, uint64_t seed, int64_t call, float* g_x, float* g_s,
+                                        float* grad_params /* [2, N]: gamma row, beta row; or NULL */, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+/* examples/bert4rec/models/bert4rec.py:201-214 */
+int tbe_relu_dropout_forward_f32(const float* a, int64_t n, float p, uint32_t site, uint64_t seed, int64_t call, float* h,
+                                 void* stream);
+/* the backward autograd builds for examples/bert4rec/models/bert4rec.py:201-214 */
+int tbe_relu_dropout_backward_f32(const float* grad_h, const float* h, int64_t n, float p, float* grad_a, void* stream);
+
 /* JaggedTensor.to_padded_dense (torchrec/sparse/jagged_tensor.py:344-363) in one launch: out [B, N] float32 from the bags
  * values[offsets[b] .. offsets[b + 1]).  A bag of at most N values is padded with padding_value: in front of the values
  * (right-aligned values) with pad_from_beginning, behind them otherwise.  A longer bag keeps its LAST N values with

@@ -17,6 +17,7 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libtbe_hip.so"))
 c_void_p = ctypes.c_void_p
 c_i32 = ctypes.c_int32
 c_i64 = ctypes.c_int64
+c_u32 = ctypes.c_uint32
 c_u64 = ctypes.c_uint64
 c_size = ctypes.c_size_t
 c_float = ctypes.c_float
@@ -263,6 +264,18 @@ SIGNATURES = {
         ctypes.c_int,
         [c_void_p] + [c_void_p, c_i64, c_i64] * 3 + [c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_float, c_u64, c_i64,
                                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tbe_residual_layernorm_backward_workspace_bytes": (c_size, [c_i64, c_i32]),
+    "tbe_residual_layernorm_forward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_i64, c_i32, c_float, c_u32, c_float, c_u32, c_u64, c_i64, c_void_p,
+         c_void_p, c_void_p, c_void_p]),
+    "tbe_residual_layernorm_backward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_float, c_u32, c_float, c_u32, c_u64, c_i64, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "tbe_relu_dropout_forward_f32": (
+        ctypes.c_int, [c_void_p, c_i64, c_float, c_u32, c_u64, c_i64, c_void_p, c_void_p]),
+    "tbe_relu_dropout_backward_f32": (ctypes.c_int, [c_void_p, c_void_p, c_i64, c_float, c_void_p, c_void_p]),
     "tbe_cross_entropy_workspace_bytes": (c_size, [c_i64]),
     "tbe_cross_entropy_forward_f32": (
         ctypes.c_int,

@@ -605,3 +605,70 @@ def attention_backward(grad_out, q, k, v, key_valid, lse, H, p=0.0, seed=0, call
             ptr(key_valid), ptr(lse), B, H, L, HD // H, p, seed, call, ptr(grads[0]), ptr(grads[1]), ptr(grads[2]),
             stream_ptr(dev)), "tbe_attention_backward_f32")
     return tuple(grads)
+
+
+# ---- BERT4Rec's residual / dropout / LayerNorm passes (csrc/residual_layernorm.hip): plain functions for the same reason —
+# optional inputs and outputs chosen per call.  `drop` = (p_in, site_in, p_out, site_out, seed, call).
+
+def _rows(name, *tensors):
+    """(device, R, N) of contiguous float32 [R, N] tensors (None entries skipped)."""
+    given = [t for t in tensors if t is not None]
+    dev = require_gpu(*given)
+    for t in given:
+        if t.dim() != 2 or t.shape != given[0].shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"{name}: want contiguous float32 [R, N] tensors of one shape, got {tuple(t.shape)} {t.dtype}")
+    return dev, given[0].shape[0], given[0].shape[1]
+
+
+def residual_layernorm_forward(x, s, gamma, beta, eps, drop, want_y=True):
+    """(y, n, stats) of tbe_residual_layernorm_forward_f32: y = drop_out(x + drop_in(s)) [R, N] (None unless want_y),
+    n = LayerNorm(y) and stats [R, 2] (None when gamma is None); s may be None."""
+    dev, R, N = _rows("residual_layernorm_forward", x, s)
+    y = torch.empty_like(x) if want_y else None
+    n = torch.empty_like(x) if gamma is not None else None
+    stats = torch.empty((R, 2), dtype=torch.float32, device=dev) if gamma is not None else None
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_residual_layernorm_forward_f32(
+            ptr(x), ptr(s), ptr(gamma), ptr(beta), eps, R, N, *drop, ptr(y), ptr(n), ptr(stats), stream_ptr(dev)),
+            "tbe_residual_layernorm_forward_f32")
+    return y, n, stats
+
+
+def residual_layernorm_backward(g_y, g_n, y, stats, gamma, drop, want_s, want_params):
+    """(g_x, g_s, grad_params [2, N]) of tbe_residual_layernorm_backward_f32; g_s is g_x itself when no input dropout is
+    active, None unless want_s; grad_params None unless want_params."""
+    dev, R, N = _rows("residual_layernorm_backward", g_y, g_n, y if g_n is not None else None)
+    g_x = torch.empty((R, N), dtype=torch.float32, device=dev)
+    g_s = (torch.empty_like(g_x) if drop[0] > 0.0 else g_x) if want_s else None
+    gp = torch.empty((2, N), dtype=torch.float32, device=dev) if want_params else None
+    with torch.cuda.device(dev):
+        lib = _lib.load()
+        wbytes = lib.tbe_residual_layernorm_backward_workspace_bytes(R, N) if want_params else 0
+        ws = workspace(wbytes, dev) if want_params else None
+        check(lib.tbe_residual_layernorm_backward_f32(
+            ptr(g_y), ptr(g_n), ptr(y), ptr(stats), ptr(gamma), R, N, *drop, ptr(g_x), ptr(g_s), ptr(gp), ptr(ws), wbytes,
+            stream_ptr(dev)), "tbe_residual_layernorm_backward_f32")
+    return g_x, g_s, gp
+
+
+def relu_dropout_forward(a, p, site, seed, call):
+    """dropout(relu(a)) of a contiguous float32 tensor whose element count is a multiple of 4."""
+    dev = require_gpu(a)
+    if a.dtype != torch.float32 or not a.is_contiguous():
+        raise RuntimeError("relu_dropout_forward: want a contiguous float32 tensor")
+    h = torch.empty_like(a)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_relu_dropout_forward_f32(ptr(a), a.numel(), p, site, seed, call, ptr(h), stream_ptr(dev)),
+              "tbe_relu_dropout_forward_f32")
+    return h
+
+
+def relu_dropout_backward(grad_h, h, p):
+    dev = require_gpu(grad_h, h)
+    if grad_h.shape != h.shape or grad_h.dtype != torch.float32 or not grad_h.is_contiguous():
+        raise RuntimeError("relu_dropout_backward: grad_h must be a contiguous float32 tensor of h's shape")
+    g = torch.empty_like(h)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_relu_dropout_backward_f32(ptr(grad_h), ptr(h), h.numel(), p, ptr(g), stream_ptr(dev)),
+              "tbe_relu_dropout_backward_f32")
+    return g

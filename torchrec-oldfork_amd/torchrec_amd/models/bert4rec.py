@@ -15,6 +15,17 @@ What runs differently:
   * The kernel's dropout mask is its own counter-based draw (include/tbe_hip.h), not torch's generator: seed =
     torch.initial_seed(), call = a per-module counter that advances once per training forward, below a high word that is
     0 for a stand-alone module and 1 + the layer index inside BERT4Rec.
+  * TransformerBlock, on a HIP device with float32 [B, L, N], N % 4 == 0, 4 <= N <= 4096 and affine LayerNorms: everything
+    between the GEMMs and the attention kernel is three launches of one kernel and one of another each way
+    (csrc/residual_layernorm.hip):  n1 = LN1(x);  x1, n2 = x + drop(attention(n1)), LN2(x1);  h = drop(relu(w_1(n2)));
+    x2 = drop(x1 + drop(w_2(h))) and, inside BERT4Rec, the next block's LN1(x2) with it (`_forward_chained`).  Autograd keeps
+    the residual streams and two floats per row: no dropout mask, no copy of a LayerNorm's input.  The dropouts draw as the
+    attention kernel's does, under a domain tag of their own, with `site` 0 = input_sublayer.dropout, 1 =
+    output_sublayer.dropout, 2 = the block's dropout, 3 = feed_forward.dropout and a per-block call counter.  Everything
+    else silently takes the torch expression: `kernel_path = False`, CPU tensors, other dtypes, other N,
+    elementwise_affine=False, p >= 1, active dropout under stream capture.  Double backward of a kernel-path forward
+    recomputes from differentiable torch operations with dropout inactive and raises RuntimeError with it active.
+    SublayerConnection and PositionwiseFeedForward called on their own are the reference's expressions.
   * BERT4Rec.forward builds the mask with .expand (stride 0 along the queries) where the reference uses .repeat, and
     HistoryArch adds `positional` by broadcasting.
   * HistoryArch and BERT4Rec take a keyword-only `fused_params` for the EmbeddingCollection (the fused ADAM of
@@ -182,6 +193,92 @@ class MultiHeadedAttention(nn.Module):
         return self.output_linear(x)
 
 
+class _ResidualLayerNorm(torch.autograd.Function):
+    """(y, n) = (drop_out(x + drop_in(s)), LayerNorm(y)) over [R, N] float32 in one launch each way
+    (csrc/residual_layernorm.hip).  s may be None; gamma None: no LayerNorm, n is None; want_y False (no dropout active, s
+    None): y is x itself and None is returned for it.  drop = (p_in, site_in, p_out, site_out, seed, call).  Kept for the
+    backward: y, two floats per row and gamma — no mask, no copy of the LayerNorm's input."""
+
+    @staticmethod
+    def forward(ctx, x, s, gamma, beta, eps, drop, want_y):
+        from ..distributed._device_ops import residual_layernorm_forward
+
+        y, n, stats = residual_layernorm_forward(x, s, gamma, beta, eps, drop, want_y)
+        ctx.save_for_backward(y if want_y else x, stats, gamma, beta)
+        ctx.eps, ctx.drop = eps, drop
+        ctx.set_materialize_grads(False)
+        return y, n
+
+    @staticmethod
+    def backward(ctx, g_y, g_n):
+        from ..distributed._device_ops import residual_layernorm_backward
+
+        y, stats, gamma, beta = ctx.saved_tensors
+        need_x, need_s, need_gamma, need_beta = ctx.needs_input_grad[:4]
+        if (g_y is None and g_n is None) or not any(ctx.needs_input_grad[:4]):
+            return (None,) * 7
+        if torch.is_grad_enabled():  # create_graph: the same gradients from differentiable torch operations on the saved y
+            if ctx.drop[0] > 0.0 or ctx.drop[2] > 0.0:
+                raise RuntimeError("TransformerBlock: double backward through the fused kernel's dropout is not supported")
+            grads = {0: g_y}
+            if g_n is not None:
+                wrt = [(i, t) for i, t in enumerate((y, gamma, beta)) if t.requires_grad]
+                n = nn.functional.layer_norm(y, y.shape[-1:], gamma, beta, ctx.eps)
+                got = torch.autograd.grad(n, [t for _, t in wrt], g_n, create_graph=True)
+                grads.update({i: v for (i, _), v in zip(wrt, got)})
+                if g_y is not None and y.requires_grad:
+                    grads[0] = g_y + grads[0]
+            g = grads.get(0)
+            return (g if need_x else None, g if need_s else None, grads.get(1) if need_gamma else None,
+                    grads.get(2) if need_beta else None, None, None, None)
+        want_params = g_n is not None and (need_gamma or need_beta)
+        g_x, g_s, gp = residual_layernorm_backward(
+            None if g_y is None else g_y.contiguous(), None if g_n is None else g_n.contiguous(), y, stats, gamma, ctx.drop,
+            need_s, want_params)
+        return (g_x if need_x else None, g_s, gp[0] if want_params and need_gamma else None,
+                gp[1] if want_params and need_beta else None, None, None, None)
+
+
+class _ReluDropout(torch.autograd.Function):
+    """dropout(relu(a)) in one launch each way (csrc/residual_layernorm.hip); the backward reads the result alone."""
+
+    @staticmethod
+    def forward(ctx, a, p, site, seed, call):
+        from ..distributed._device_ops import relu_dropout_forward
+
+        h = relu_dropout_forward(a, p, site, seed, call)
+        ctx.save_for_backward(h)
+        ctx.p = p
+        return h
+
+    @staticmethod
+    def backward(ctx, g_h):
+        from ..distributed._device_ops import relu_dropout_backward
+
+        (h,) = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            if ctx.p > 0.0:
+                raise RuntimeError("TransformerBlock: double backward through the fused kernel's dropout is not supported")
+            return g_h * (h > 0).to(g_h.dtype), None, None, None, None
+        return relu_dropout_backward(g_h.contiguous(), h, ctx.p), None, None, None, None
+
+
+def _residual_layernorm(x, s, norm, drop, want_y=True):
+    """_ResidualLayerNorm where a gradient may be wanted, the forward launch alone elsewhere (nothing is kept)."""
+    gamma, beta, eps = (norm.weight, norm.bias, norm.eps) if norm is not None else (None, None, 0.0)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, s, gamma, beta)):
+        return _ResidualLayerNorm.apply(x, s, gamma, beta, eps, drop, want_y)
+    from ..distributed._device_ops import residual_layernorm_forward
+
+    return residual_layernorm_forward(x, s, gamma, beta, eps, drop, want_y)[:2]
+
+
+def _fusable_norm(norm: nn.Module, N: int) -> bool:
+    return (isinstance(norm, nn.LayerNorm) and tuple(norm.normalized_shape) == (N,) and norm.elementwise_affine
+            and norm.bias is not None and norm.weight.is_cuda and norm.weight.dtype == torch.float32
+            and norm.weight.data_ptr() % 16 == 0 and norm.bias.data_ptr() % 16 == 0)
+
+
 class PositionwiseFeedForward(nn.Module):
     """Feed-forward block (examples/bert4rec/models/bert4rec.py:174-214).
 
@@ -240,11 +337,74 @@ class TransformerBlock(nn.Module):
         self.input_sublayer = SublayerConnection(size=hidden, dropout=dropout, device=device)
         self.output_sublayer = SublayerConnection(size=hidden, dropout=dropout, device=device)
         self.dropout = nn.Dropout(p=dropout)
+        self.kernel_path = True     # False: always the torch expression (tests and tools compare the two)
+        self.last_path = None       # "kernel" / "torch": what the last forward took
+        # the kernel dropouts' `call`, as in MultiHeadedAttention: high word 0 for a block built on its own, 1 + the layer
+        # index inside BERT4Rec; the low word counts the training forwards with active kernel dropout
+        self._dropout_salt = 0
+        self._dropout_calls = 0
+
+    def _dropout_ps(self) -> Tuple[float, float, float, float]:
+        """p of the sites 0 .. 3: input_sublayer.dropout, output_sublayer.dropout, the block's dropout, feed_forward.dropout."""
+        drops = (self.input_sublayer.dropout, self.output_sublayer.dropout, self.dropout, self.feed_forward.dropout)
+        return tuple(float(d.p) if self.training else 0.0 for d in drops)
+
+    def _kernel_ok(self, x: torch.Tensor, ps, next_norm: Optional[nn.Module]) -> bool:
+        if not (self.kernel_path and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.numel() > 0):
+            return False
+        N, ff = x.shape[-1], self.feed_forward
+        if N % 4 or not 4 <= N <= 4096 or x.numel() // N >= 2 ** 31 or (x.is_contiguous() and x.data_ptr() % 16):
+            return False
+        if not (isinstance(ff.w_1, nn.Linear) and isinstance(ff.w_2, nn.Linear) and ff.w_1.weight.dtype == torch.float32
+                and (x.numel() // N * ff.w_1.out_features) % 4 == 0):  # relu_dropout moves 16 bytes at a time
+            return False
+        if not all(_fusable_norm(m, N) for m in (self.input_sublayer.norm, self.output_sublayer.norm)):
+            return False
+        if next_norm is not None and not _fusable_norm(next_norm, N):
+            return False
+        if not all(0.0 <= p < 1.0 for p in ps):
+            return False
+        return not (max(ps) > 0.0 and torch.cuda.is_current_stream_capturing())  # the call counter is host state
 
     def forward(self, x: torch.Tensor, mask: torch.BoolTensor) -> torch.Tensor:
-        x = self.input_sublayer(x, lambda _x: self.attention.forward(_x, _x, _x, mask=mask))
-        x = self.output_sublayer(x, self.feed_forward)
-        return self.dropout(x)
+        return self._forward_chained(x, mask, None, None)[0]
+
+    def _forward_chained(self, x: torch.Tensor, mask: torch.BoolTensor, n1: Optional[torch.Tensor],
+                         next_norm: Optional[nn.Module]) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """(the block's output, LayerNorm `next_norm` of it or None).  `n1`: this block's input_sublayer.norm(x) when the
+        block before has made it already.  The second result is None whenever this call takes the torch expression."""
+        ps = self._dropout_ps()
+        if not self._kernel_ok(x, ps, next_norm):
+            self.last_path = "torch"
+            x = self.input_sublayer(x, lambda _x: self.attention.forward(_x, _x, _x, mask=mask))
+            x = self.output_sublayer(x, self.feed_forward)
+            return self.dropout(x), None
+        self.last_path = "kernel"
+        seed = call = 0
+        if max(ps) > 0.0:
+            seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
+            call = (self._dropout_salt << 32) | (self._dropout_calls & 0xFFFFFFFF)
+            self._dropout_calls += 1
+        shape, N = x.shape, x.shape[-1]
+        x = x.contiguous().view(-1, N)
+        if n1 is None:  # launch A: n1 = LN1(x); no y is written
+            n1 = _residual_layernorm(x, None, self.input_sublayer.norm, (0.0, 0, 0.0, 0, 0, 0), want_y=False)[1]
+        n1 = n1.view(shape)
+        a = self.attention.forward(n1, n1, n1, mask=mask)
+        # launch A: x1 = x + drop(a), n2 = LN2(x1)
+        x1, n2 = _residual_layernorm(x, a.contiguous().view(-1, N), self.output_sublayer.norm, (ps[0], 0, 0.0, 0, seed, call))
+        # GEMM + launch B: h = drop(relu(w_1(n2)))
+        h = self.feed_forward.w_1(n2).contiguous()
+        if torch.is_grad_enabled() and h.requires_grad:
+            h = _ReluDropout.apply(h, ps[3], 3, seed, call)
+        else:
+            from ..distributed._device_ops import relu_dropout_forward
+
+            h = relu_dropout_forward(h, ps[3], 3, seed, call)
+        # GEMM + launch A: x2 = drop_blk(x1 + drop(w_2(h))), and the next block's LN1 of it
+        f = self.feed_forward.w_2(h).contiguous()
+        x2, n_next = _residual_layernorm(x1, f, next_norm, (ps[1], 1, ps[2], 2, seed, call))
+        return x2.view(shape), None if n_next is None else n_next.view(shape)
 
 
 class HistoryArch(torch.nn.Module):
@@ -319,7 +479,7 @@ class BERT4Rec(nn.Module):
         self.transformer_blocks = nn.ModuleList(
             [TransformerBlock(emb_dim, nhead, emb_dim * 4, dropout, device=device) for _ in range(num_layers)])
         for i, block in enumerate(self.transformer_blocks):
-            block.attention._dropout_salt = 1 + i
+            block.attention._dropout_salt = block._dropout_salt = 1 + i
         # as in the reference: a linear output layer, not the paper's product with the embedding table
         self.out = nn.Linear(self.emb_dim, self.vocab_size, device=device)
 
@@ -329,6 +489,12 @@ class BERT4Rec(nn.Module):
         # [B, 1, L, L] with stride 0 along the queries (the reference materialises it with .repeat)
         mask = (dense_tensor > 0)[:, None, None, :].expand(B, 1, L, L)
         x = self.history(input)
-        for transformer in self.transformer_blocks:
-            x = transformer.forward(x, mask)
+        # the last launch of block i also makes block i + 1's first LayerNorm (None when either takes the torch expression)
+        blocks, n1 = list(self.transformer_blocks), None
+        for i, transformer in enumerate(blocks):
+            nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+            next_norm = None
+            if nxt is not None and nxt.kernel_path and _fusable_norm(nxt.input_sublayer.norm, x.shape[-1]):
+                next_norm = nxt.input_sublayer.norm
+            x, n1 = transformer._forward_chained(x, mask, n1, next_norm)
         return self.out(x)
