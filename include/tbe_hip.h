@@ -727,6 +727,31 @@ int tbe_dlrm_interaction_gather_backward_sgd_f32(const float* dense, const uint6
                                                  float* grad_sparse, int32_t* bounds_errors, const uint8_t* single,
                                                  float learning_rate, void* stream);
 
+/* tbe_dlrm_interaction_gather_forward_f32 over quantized inference tables (format: "Quantized inference tables" below), forward
+ * only: the interaction copies the INT8 / INT4 / INT2 rows as they are stored and dequantizes them where they become MFMA
+ * operands; no FP32 [B, F, D] buffer exists.  One bit rate per launch (bit_rate = 8, 4 or 2), every table of dim D.
+ *   feat_weights [F] table bases (16-byte aligned, table layout: header in bytes 0..3, data from byte 4);
+ *   feat_row_bytes [F] int32 row strides (multiples of 16, >= D / epb + 4, epb = 8 / bit_rate; a larger stride is legal: the
+ *   kernel reads the ceil((D / epb + 4) / 16) aligned 16-byte chunks that hold header and data, and interprets only header
+ *   and data bytes); feat_rows [F] int64 row counts.  The three are device arrays the library does not read on the host;
+ *   two features may name one table.  indices [F*B] int64, feature-major, one id per bag: bag (f, b) owns indices[f*B + b].
+ * X[0] = dense[b] (float32, [B, D], 16-byte aligned).  X[r][j] = fmaf(float(q_j), scale, bias) in FP32 for the row
+ * indices[(r-1)*B + b] of feature r - 1; the product is exact, so a fused or an unfused multiply-add give the same bits.
+ * An id outside [0, rows) forms no address, contributes a row of +0 and is counted once in bounds_errors (optional device
+ * int32).  out[b] = [dense[b] | <X_i, X_j>, i < j, in torch.triu_indices(F+1, F+1, 1) order], summed in the column order of
+ * tbe_dlrm_interaction_forward_f32 and stored by its rules: rows of out_stride floats (>= D + (F+1)F/2); 16-byte stores with
+ * zeros in the pad columns [D + P, D + P4) exactly when out is 16-byte aligned, out_stride % 4 == 0 and out_stride >= D + P4,
+ * else 4-byte stores of [0, D + P); nothing else is written.  For every row header with a finite scale >= 0 (the quantizer
+ * writes no other) the result is bit-identical to tbe_forward_nbit_i64 (float32 output, SUM, no weights) followed by
+ * tbe_dlrm_interaction_forward_f32, i.e. to the oracle's interaction of the dequantized rows.  A non-finite header changes
+ * its own sample only.  1 <= F <= 27, D in {64, 128}.  Errors, before any launch: F, D or bit_rate outside these, out_stride
+ * below the row, a null pointer (bounds_errors may be null), dense not 16-byte, indices / feat_weights / feat_rows not 8-byte or
+ * feat_row_bytes / out / bounds_errors not 4-byte aligned.  B == 0 launches nothing.  One launch on `stream`, no synchronisation. */
+int tbe_dlrm_interaction_gather_forward_nbit(const float* dense, const uint64_t* feat_weights, const int32_t* feat_row_bytes,
+                                             const int64_t* feat_rows, int32_t bit_rate, const int64_t* indices, int32_t B,
+                                             int32_t F, int32_t D, float* out, int64_t out_stride, int32_t* bounds_errors,
+                                             void* stream);
+
 /* ReLU backward + bias gradient of one MLP layer in one pass (torchrec/modules/mlp.py:14-170 Perceptron
  * trained through autograd: threshold_backward + sum(0)):
  *   grad_in[b, c] = act[b, c] > 0 ? grad_out[b, c] : 0;   bias_grad[c] = sum_b grad_in[b, c]

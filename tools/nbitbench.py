@@ -3,7 +3,16 @@ quantizer next to a device copy of its input bytes, at the Criteo-1TB shape (dev
 paths).  Every variant is timed once per round, the rounds alternate the variants, and the record keeps each variant's
 median, minimum and maximum over the rounds (HIP events around back-to-back C-ABI calls: `iters` of them, or as many as
 fill a window of 30 ms).
-Usage: python tools/nbitbench.py [--batch 65536,4096] [--pooling 1,20] [--cap ROWS] [--rounds 7] [--iters 20] [--json FILE]"""
+
+--gather times the dot interaction over the quantized tables instead: `fused` (tbe_dlrm_interaction_gather_forward_nbit, one
+launch) against the `pair` it replaces (tbe_forward_nbit_i64 with float32 output, then tbe_dlrm_interaction_forward_f32), one
+id per bag, rows of D + P floats, with the FP32 tbe_dlrm_interaction_gather_forward_f32 as a yardstick; same rounds and
+windows.  The two outputs must be equal bit for bit before anything is timed.  `spread_us` is the larger of the two paths'
+(max - min) over the rounds; `kernel_not_slower` says whether fused's median is within that spread of the pair's or below it.
+Bytes are counted from the shapes: ids, the rows' header + data bytes, the dense row and the output row; the pair also
+writes and reads the pooled float32 buffer.
+Usage: python tools/nbitbench.py [--gather] [--batch 65536,4096] [--pooling 1,20] [--cap ROWS] [--rounds 7] [--iters 20]
+       [--json FILE]"""
 import argparse
 import json
 import os
@@ -51,6 +60,58 @@ def rounds_of(variants, rounds, iters):
                    "calls_per_window": calls[name]} for name, t in times.items()}
 
 
+def gather_interaction(lib, st, fp32, nbit, rows, D, batches, rounds, iters, gen):
+    """The --gather records: per batch, fused / pair / fp32 times of every bit rate."""
+    F, dev = len(rows), torch.device("cuda", 0)
+    P = F * (F + 1) // 2
+    lay, records = fp32._get_layout(), []
+    for B in batches:
+        ids = torch.cat([torch.randint(0, r, (B,), generator=gen, device=dev, dtype=torch.int64) for r in rows])
+        offsets = torch.arange(F * B + 1, dtype=torch.int64, device=dev)
+        dense = torch.randn(B, D, device=dev)
+        pooled = torch.empty((B, F * D), dtype=torch.float32, device=dev)
+        out = {k: torch.empty((B, D + P), dtype=torch.float32, device=dev) for k in ("fused", "pair", "fp32")}
+        io_bytes = F * B * 8 + B * D * 4 + B * (D + P) * 4  # ids, the dense row, the output row
+
+        def run_fp32():
+            lib.tbe_dlrm_interaction_gather_forward_f32(dense.data_ptr(), lay.feat_weights.data_ptr(), lay.feat_rows.data_ptr(),
+                                                        None, ids.data_ptr(), B, F, D, out["fp32"].data_ptr(), D + P, None, st)
+
+        for name, m in nbit.items():
+            meta = [x.data_ptr() for x in m._feature_meta()]
+            fw, frb, fr, bits, _, _ = m.gather_interaction_args()
+
+            def fused(fw=fw, frb=frb, fr=fr, bits=bits):
+                rc = lib.tbe_dlrm_interaction_gather_forward_nbit(dense.data_ptr(), fw.data_ptr(), frb.data_ptr(), fr.data_ptr(),
+                                                                  bits, ids.data_ptr(), B, F, D, out["fused"].data_ptr(), D + P,
+                                                                  None, st)
+                assert rc == 0, lib.tbe_last_error()
+
+            def pair(meta=meta):
+                lib.tbe_forward_nbit_i64(*meta, None, F, B, ids.data_ptr(), F * B, offsets.data_ptr(), None, 0,
+                                         pooled.data_ptr(), 0, F * D, None, st)
+                lib.tbe_dlrm_interaction_forward_f32(dense.data_ptr(), pooled.data_ptr(), B, F, D, out["pair"].data_ptr(),
+                                                     D + P, st)
+
+            fused(), pair()
+            torch.cuda.synchronize()
+            assert torch.equal(out["fused"].view(torch.int32), out["pair"].view(torch.int32)), f"{name} B={B}: fused != pair"
+            res = rounds_of({"fused": fused, "pair": pair, "fp32": run_fp32}, rounds, iters)
+            row_bytes = F * B * (D * bits // 8 + 4)
+            bytes_of = {"fused": io_bytes + row_bytes, "pair": io_bytes + row_bytes + 2 * B * F * D * 4,
+                        "fp32": io_bytes + F * B * D * 4}
+            for key, r in res.items():
+                r["algorithmic_bytes"] = bytes_of[key]
+                r["TBps"] = bytes_of[key] / (r["median_us"] * 1e-6) / 1e12
+            spread = max(res[k]["max_us"] - res[k]["min_us"] for k in ("fused", "pair"))
+            rec = {"batch": B, "type": name, "outputs_bit_equal": True, "variants": res, "spread_us": spread,
+                   "pair_over_fused": res["pair"]["median_us"] / res["fused"]["median_us"],
+                   "kernel_not_slower": bool(res["fused"]["median_us"] <= res["pair"]["median_us"] + spread)}
+            records.append(rec)
+            print(json.dumps(rec), flush=True)
+    return records
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", default="65536,4096")
@@ -60,6 +121,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20, help="least calls per timed window")
     ap.add_argument("--json", default="")
+    ap.add_argument("--gather", action="store_true", help="time the fused gather interaction against the lookup + interaction pair")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     lib, st = _lib.load(), None
@@ -69,6 +131,23 @@ def main():
     for w, r in zip(fp32.split_embedding_weights(), rows):
         w.uniform_(-(1.0 / r) ** 0.5, (1.0 / r) ** 0.5)
     record = {"rows": rows, "dim": D, "rounds": args.rounds, "iters": args.iters, "window_ms": WINDOW_MS, "lookup": [], "quantizer": []}
+
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    if args.gather:
+        nbit = {}
+        for name, ty in TYPES.items():
+            m = nbit[name] = IntNBitTableBatchedEmbeddingBagsCodegen(
+                [(f"t{t}", r, D, ty, EmbeddingLocation.DEVICE) for t, r in enumerate(rows)], device=dev, row_alignment=16)
+            for t, w in enumerate(fp32.split_embedding_weights()):
+                m.quantize_table_(t, w)
+        record = {"rows": rows, "dim": D, "rounds": args.rounds, "iters": args.iters, "window_ms": WINDOW_MS,
+                  "gather_interaction": gather_interaction(lib, st, fp32, nbit, rows, D, [int(b) for b in args.batch.split(",")],
+                                                           args.rounds, args.iters, g)}
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(record, f, indent=1)
+        return
 
     # the quantizer on the largest table, next to a device copy of the same input bytes
     big = max(range(F), key=lambda t: rows[t])
@@ -89,8 +168,6 @@ def main():
         print(json.dumps(rec), flush=True)
     del dst
 
-    g = torch.Generator(device=dev)
-    g.manual_seed(1234)
     for B in [int(b) for b in args.batch.split(",")]:
         for L in [int(p) for p in args.pooling.split(",")]:
             ids = torch.cat([torch.randint(0, r, (B * L,), generator=g, device=dev, dtype=torch.int64) for r in rows])

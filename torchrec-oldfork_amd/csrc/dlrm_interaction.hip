@@ -23,6 +23,8 @@
 //   forward   interaction_fwd_kernel         register loads in MFMA-fragment shape, predicated straight-line stores
 //             interaction_fwd_glds_kernel    LDS-DMA copy from the pooled buffer, unrolled, per-lane offsets kept in registers
 //             interaction_gather_fwd_kernel  LDS-DMA copy from the tables, rolled, ids through an LDS slot
+//             interaction_gather_nbit_fwd_kernel  the same from INT8 / INT4 / INT2 tables: rows stay quantized in LDS and are
+//                                            dequantized into the fragments (its own section, behind the gather backward)
 //     shared: FwdWave (the wave's geometry), fwd_contract, fwd_stage_pairs; by the two LDS-DMA kernels also FwdImage (the
 //             per-wave LDS image, which the host sizes the launch from), fwd_read_fragments, fwd_read_dense / fwd_store_dense,
 //             fwd_store_pairs_counted
@@ -992,6 +994,210 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
   report_bad_ids(nbad, bounds_errors);
 }
 
+// ---- pooling factor 1, quantized inference tables: the rows stay INT8 / INT4 / INT2 until they are MFMA operands --------------
+// interaction_gather_fwd_kernel for table-layout quantized tables (include/tbe_hip.h "Quantized inference tables"): the wave
+// copies the sample's rows AS THEY ARE STORED — a (scale, bias) header of two halves and D / epb data bytes, C aligned 16-byte
+// chunks — into a raw image, and each lane dequantizes exactly the elements it feeds to the MFMA.  No FP32 [B, F, D] buffer
+// exists, in global memory or in LDS: a sample's image is 1 - 5 KB where the FP32 image has 14 KB, and the sample's global
+// traffic is the ids, F * C chunks, the dense row and the output row.
+//
+// The raw image of a wave (NbitImage, host and device).  An LDS-DMA instruction writes lane-linear (16 B per lane), so the image
+// is a chain of 16-byte slots filled by NI = copies(R) instructions; what a slot holds is decided on the SOURCE side:
+//   slots [0, D / 4)                     the dense row, FP32, unswizzled (fwd_read_dense reads it as the FP32 kernels do)
+//   slot  D / 4 + f * PC + c, c < PC     chunk min(c, C - 1) of the row of feature f
+//   slots behind the last row            a chunk of g_zero_row (whole instructions only)
+// PC = C | 1 is the row pitch in chunks.  A ds_read group is 16 consecutive rows at one offset inside the row; pitches are
+// whole chunks (4 banks), so rows fall into 8 bank classes and an odd pitch spreads 8 consecutive rows over all 8 — rows r and
+// r + 8 share banks, the floor of a 16-byte-granular image (the reads are 4 / 2 / 1 bytes: INT8 at D = 128 reads 16 dwords per
+// lane and sample where the FP32 image reads 16 x 16 bytes).  Only INT2 at D = 64 (C = 2) pays a pad chunk for it.  Lanes of
+// one row with different q that share a dword are a broadcast.
+//
+// Fragments: lane (r, q) needs columns 16 s + 4 q + e, e = 0 .. 3, of rows r and r + 16 — for a sparse row the 4 values packed
+// at data byte (16 s + 4 q) / epb, i.e. one dword / halfword / byte per segment and row at image byte 4 + (16 s + 4 q) / epb of
+// the row, plus the row's header dword once.  Element e is (v >> (e * BITS)) & mask, converted once, and the operand is
+// fmaf(float(q), scale, bias): the product is exact (8-bit q, 11-bit scale), so this IS tbe_forward_nbit's
+// fmaf(scale, q, 0) + (bias + 0) for every finite scale >= 0, and the contraction behind it is fwd_contract in its column order:
+// the output equals the quantized lookup + tbe_dlrm_interaction_forward_f32, bit for bit.  Row 0 is the dense row: the four lanes
+// with r = 0 take their tile-0 operands from its FP32 slots instead.
+//
+// Pipeline, per wave and sample (the counted waits are those of interaction_gather_fwd_kernel): the raw words (2 * NS + 2
+// registers) and the dense operands are read from the image, then the NEXT sample's rows are copied while this sample's words
+// are converted and multiplied.  Ids travel two samples ahead through the wave's id slot.  A bad id's lanes copy chunks of
+// g_zero_row: a zero header dequantizes every element to +0, no lane is masked and no stale LDS is read.
+// Workgroups per CU (= waves per SIMD).  The image is 7 KB a wave at most, so LDS would admit five; registers decide: D = 64 fits
+// the 128 VGPRs of four waves, D = 128 (64 operand registers) needs the 168 of three.
+constexpr int nbit_wgs_per_cu(int D) { return D <= 64 ? 4 : 3; }
+template <int D, int BITS>
+struct NbitImage {
+  static constexpr int EPB = 8 / BITS;                    // elements per byte
+  static constexpr int C = (D / EPB + 4 + 15) / 16;       // 16-byte chunks that hold header + data of a row
+  static constexpr int PC = C | 1;                        // LDS pitch of a raw row, in chunks
+  static constexpr int PRD = D / 4;                       // chunks of the dense row
+  static constexpr int DS = FwdImage<D>::DS;
+  static_assert(BITS == 8 || BITS == 4 || BITS == 2, "INT8 / INT4 / INT2");
+  static_assert(C * 16 <= 256 * sizeof(float), "a bad id's chunks come from g_zero_row (256 floats)");
+  static constexpr int chunks(int R) { return PRD + (R - 1) * PC; }
+  static constexpr int copies(int R) { return (chunks(R) + kWave - 1) / kWave; }
+  static constexpr int zs_offset(int R) { return copies(R) * kWave * 4; }  // floats: whole copy instructions
+  static constexpr int ids_offset(int R) { return zs_offset(R) + pad4(pair_count(R)); }
+  static constexpr int floats(int R) { return ids_offset(R) + kIdSlotFloats; }
+  static constexpr int MAXI = copies(kBwdMaxRows);
+  static constexpr int row_byte(int f) { return 16 * (PRD + f * PC); }  // where the row of feature f starts in the image
+};
+
+__device__ __forceinline__ float half_bits_to_f32(uint32_t bits) {
+  return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(bits & 0xffffu)));
+}
+
+// The raw words of one lane: per segment the 4 packed elements of row tile 0 and 1, and the two rows' headers.
+template <int NS>
+struct NbitWords {
+  uint32_t a[NS], b[NS], ha, hb;
+};
+template <int BITS>
+__device__ __forceinline__ uint32_t nbit_read_word(const uint8_t* p) {
+  if constexpr (BITS == 8) return *reinterpret_cast<const uint32_t*>(p);
+  else if constexpr (BITS == 4) return *reinterpret_cast<const uint16_t*>(p);
+  else return *p;
+}
+template <int D, int BITS>
+__device__ __forceinline__ void nbit_read_words(const uint8_t* image, const FwdWave<D>& w, NbitWords<D / 16>& r) {
+  using Image = NbitImage<D, BITS>;
+  constexpr int NS = D / 16;
+  // feature of row tile 0 / 1 (row 0 is the dense row: its lanes read feature 0 and do not use it)
+  const uint8_t* ra = image + Image::row_byte(max(w.row0 - 1, 0));
+  const uint8_t* rb = image + Image::row_byte(w.row1 - 1);  // row1 >= 1: R >= 2
+  const int col = 4 + (4 * w.kq) / Image::EPB;
+  r.ha = *reinterpret_cast<const uint32_t*>(ra);
+#pragma unroll
+  for (int s = 0; s < NS; ++s) r.a[s] = nbit_read_word<BITS>(ra + col + (16 * s) / Image::EPB);
+  if (w.R > 16) {
+    r.hb = *reinterpret_cast<const uint32_t*>(rb);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) r.b[s] = nbit_read_word<BITS>(rb + col + (16 * s) / Image::EPB);
+  } else {  // a zero header and zero data: rows of +0, as fwd_read_fragments gives
+    r.hb = 0;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) r.b[s] = 0;
+  }
+}
+template <int BITS>
+__device__ __forceinline__ float4 nbit_dequant4(uint32_t v, float scale, float bias) {
+  constexpr uint32_t MASK = (1u << BITS) - 1u;
+  return make_float4(fmaf(static_cast<float>(v & MASK), scale, bias), fmaf(static_cast<float>((v >> BITS) & MASK), scale, bias),
+                     fmaf(static_cast<float>((v >> (2 * BITS)) & MASK), scale, bias),
+                     fmaf(static_cast<float>((v >> (3 * BITS)) & MASK), scale, bias));
+}
+
+template <int D, int BITS>
+__global__ __launch_bounds__(256, nbit_wgs_per_cu(D)) void interaction_gather_nbit_fwd_kernel(
+    const float* __restrict__ dense, const uint64_t* __restrict__ feat_weights, const int32_t* __restrict__ feat_row_bytes,
+    const int64_t* __restrict__ feat_rows, const int64_t* __restrict__ indices, float* __restrict__ out,
+    int32_t* __restrict__ bounds_errors, int B, int F, int64_t out_stride) {
+  extern __shared__ float smem[];
+  using Image = NbitImage<D, BITS>;
+  constexpr int NS = D / 16;
+  const FwdWave<D> w(F, out, out_stride);
+  const int lane = w.lane;
+  const int R = w.R;
+  const int NI = Image::copies(R);
+  float* xs = smem + w.wave * Image::floats(R);  // the dense row, then the raw rows
+  const uint8_t* image = reinterpret_cast<const uint8_t*>(xs);
+  float* zs = xs + Image::zs_offset(R);
+  float* ids = xs + Image::ids_offset(R);
+  w.zero_pad(zs);
+  const int stride_b = w.stride_b;
+  // feature lane f < F: the table of feature f; the lanes behind repeat feature F - 1 and count nothing
+  const int fl = min(lane, F - 1);
+  const uint64_t table = feat_weights[fl];
+  const int64_t table_rows = feat_rows[fl];
+  const uint64_t row_bytes = static_cast<uint64_t>(feat_row_bytes[fl]);
+  const uint64_t zero_row = reinterpret_cast<uint64_t>(&g_zero_row[0]);
+  int nbad = 0;
+  // an id outside [0, rows) forms no address
+  auto row_address = [&](int64_t id) {
+    const bool inside = id >= 0 && id < table_rows;
+    if (!inside && lane < F) ++nbad;
+    return inside ? table + static_cast<uint64_t>(id) * row_bytes : zero_row;
+  };
+  const uint32_t* id_words = reinterpret_cast<const uint32_t*>(indices) +
+                             2 * static_cast<int64_t>(min(lane >> 1, F - 1)) * B + (lane & 1);
+  auto issue_ids = [&](int b) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(id_words + 2 * static_cast<int64_t>(b)),
+                                     (__attribute__((address_space(3))) void*)ids, 4, 0, 0);
+  };
+  auto read_id = [&]() { return *reinterpret_cast<const int64_t*>(ids + 2 * fl); };
+  // copy instruction i fills slots 64 i .. 64 i + 63 (see NbitImage); `row_addr` is the feature lanes' row address for sample b
+  auto issue_copy = [&](int b, uint64_t row_addr) {
+    const uint64_t dn = reinterpret_cast<uint64_t>(dense + static_cast<int64_t>(b) * D);
+#pragma unroll 1
+    for (int i = 0; i < NI; ++i) {
+      {
+        const int slot = i * kWave + lane;
+        const int u = max(slot - Image::PRD, 0);
+        const int f = u / Image::PC;
+        const int c = min(u % Image::PC, Image::C - 1);
+        uint64_t src = shflu64(row_addr, min(f, F - 1)) + 16 * c;
+        if (f >= F) src = zero_row + 16 * c;
+        if (slot < Image::PRD) src = dn + 16 * slot;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                         (__attribute__((address_space(3))) void*)(xs + i * (kWave * 4)), 16, 0, 0);
+      }
+    }
+  };
+  int stores_behind_copy = 0;
+  int b = w.first_sample();
+  if (b < B) {
+    issue_ids(b);
+    vm_wait_all_but<0>();
+    wave_lds_fence();
+    const int64_t id = read_id();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
+    issue_copy(b, row_address(id));
+    if (b + stride_b < B) issue_ids(b + stride_b);
+  }
+  for (; b < B; b += stride_b) {
+    // the copy of sample b and the ids of the next sample have landed once everything but the stores issued after them
+    // has retired
+    vm_wait_all_but(stores_behind_copy);
+    wave_lds_fence();
+    NbitWords<NS> r;
+    float4 da[NS];  // tile-0 operands of the dense row: 16 lanes read one address (a broadcast), the r = 0 lanes use it
+    float4 dpass;
+    float dscal[Image::DS];
+    nbit_read_words<D, BITS>(image, w, r);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) da[s] = *reinterpret_cast<const float4*>(xs + 16 * s + 4 * w.kq);
+    fwd_read_dense(xs, w, dpass, dscal);
+    const int64_t next_id = read_id();  // of sample b + stride_b (stale when there is none: not used then)
+    // every read of the image and of the id slot has returned before the next copies may overwrite them
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
+    if (b + stride_b < B) {
+      issue_copy(b + stride_b, row_address(next_id));
+      if (b + 2 * stride_b < B) issue_ids(b + 2 * stride_b);
+    }
+    FwdRows<NS> x;
+    const float sa = half_bits_to_f32(r.ha), ba = half_bits_to_f32(r.ha >> 16);
+    const float sb = half_bits_to_f32(r.hb), bb = half_bits_to_f32(r.hb >> 16);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      x.a[s] = w.row0 == 0 ? da[s] : nbit_dequant4<BITS>(r.a[s], sa, ba);
+      x.b[s] = nbit_dequant4<BITS>(r.b[s], sb, bb);
+    }
+    f32x4 acc00, acc01, acc11;
+    fwd_contract<NS>(x, acc00, acc01, acc11);
+    float* orow = out + static_cast<int64_t>(b) * out_stride;
+    fwd_store_dense(orow, w, dpass, dscal);
+    fwd_stage_pairs(zs, w, acc00, acc01, acc11);
+    wave_lds_fence();
+    stores_behind_copy = fwd_store_pairs_counted(orow, zs, w);
+    wave_lds_fence();  // zs is rewritten by the next sample
+  }
+  report_bad_ids(nbad, bounds_errors);
+}
+
 }  // namespace tbe
 
 using namespace tbe;
@@ -1122,6 +1328,38 @@ extern "C" int tbe_dlrm_interaction_gather_forward_f32(const float* dense, const
     rc = launch_interaction<interaction_gather_fwd_kernel<DD>>(what, B, 2, Image::floats(F + 1), Image::floats(kBwdMaxRows), stream,
                                                                dense, feat_weights, feat_rows, feat_window, indices, out,
                                                                bounds_errors, B, F, out_row_stride);
+  });
+  return rc;
+}
+
+static_assert(image_covers<NbitImage<128, 8>>(kBwdMaxRows) && image_covers<NbitImage<64, 2>>(kBwdMaxRows) &&
+                  nbit_wgs_per_cu(128) * workgroup_lds_bytes(NbitImage<128, 8>::floats(kBwdMaxRows)) <= kCuLdsBytes &&
+                  nbit_wgs_per_cu(64) * workgroup_lds_bytes(NbitImage<64, 8>::floats(kBwdMaxRows)) <= kCuLdsBytes,
+              "the largest raw images, nbit_wgs_per_cu workgroups per CU");
+
+// The gather forward over quantized tables: one bit rate per launch.  The feat_* arrays are device memory and are not read here.
+extern "C" int tbe_dlrm_interaction_gather_forward_nbit(const float* dense, const uint64_t* feat_weights,
+                                                        const int32_t* feat_row_bytes, const int64_t* feat_rows,
+                                                        int32_t bit_rate, const int64_t* indices, int32_t B, int32_t F,
+                                                        int32_t D, float* out, int64_t out_stride, int32_t* bounds_errors,
+                                                        void* stream) {
+  const char* what = "tbe_dlrm_interaction_gather_forward_nbit";
+  TBE_REQUIRE(bit_rate == 8 || bit_rate == 4 || bit_rate == 2, "%s: bit_rate=%d must be 8, 4 or 2", what, bit_rate);
+  if (int rc = check_gather_args(what, B, F, D, out_stride, {dense}, "dense", {feat_weights, feat_row_bytes, feat_rows, out},
+                                 indices))
+    return rc;
+  TBE_REQUIRE(all_aligned({feat_weights, feat_rows}, 7) && all_aligned({feat_row_bytes, out, bounds_errors}, 3),
+              "%s: feat_weights / feat_rows must be 8-B, feat_row_bytes / out / bounds_errors 4-B aligned", what);
+  if (B == 0) return TBE_OK;
+  int rc = TBE_OK;
+  dispatch_value<64, 128>(D, [&](auto d) {
+    dispatch_value<8, 4, 2>(bit_rate, [&](auto bits) {
+      constexpr int DD = decltype(d)::value;
+      using Image = NbitImage<DD, decltype(bits)::value>;
+      rc = launch_interaction<interaction_gather_nbit_fwd_kernel<DD, decltype(bits)::value>>(
+          what, B, nbit_wgs_per_cu(DD), Image::floats(F + 1), Image::floats(kBwdMaxRows), stream, dense, feat_weights, feat_row_bytes,
+          feat_rows, indices, out, bounds_errors, B, F, out_stride);
+    });
   });
   return rc;
 }

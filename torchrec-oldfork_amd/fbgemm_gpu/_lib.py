@@ -190,6 +190,9 @@ SIGNATURES = {
     "tbe_dlrm_interaction_gather_forward_f32": (
         ctypes.c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p]),
+    "tbe_dlrm_interaction_gather_forward_nbit": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p]),
     "tbe_dlrm_interaction_gather_backward_f32": (
         ctypes.c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p,

@@ -271,6 +271,22 @@ class IntNBitTableBatchedEmbeddingBagsCodegen(nn.Module):
         """Out-of-range ids and malformed bags seen so far (they contribute zero rows).  Syncs."""
         return int(self._errors().item())
 
+    def _counter_ptr(self) -> Optional[int]:
+        """The bounds counter the kernels add to, or None where the mode asks for no count."""
+        return None if self.bounds_check_mode in (BoundsCheckMode.IGNORE, BoundsCheckMode.NONE) else ptr(self._errors())
+
+    def gather_interaction_args(self) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int, int, Optional[int]]]:
+        """What tbe_dlrm_interaction_gather_forward_nbit needs of this module: the device arrays (feat_weights,
+        feat_row_bytes, feat_rows) of the lookup, the tables' common bit rate and dim, and the bounds counter's address.
+        None when the tables have mixed bit rates or dims (one of each per launch) or the mode raises on a bad id
+        (BoundsCheckMode.FATAL reads the counter after every lookup: that stays the lookup's)."""
+        bits = {ty.bit_rate() for ty in self.types_per_table}
+        dims = set(self.dims_per_table)
+        if len(bits) != 1 or len(dims) != 1 or self.bounds_check_mode == BoundsCheckMode.FATAL:
+            return None
+        feat_weights, _, _, feat_row_bytes, feat_rows, _ = self._feature_meta()
+        return feat_weights, feat_row_bytes, feat_rows, bits.pop(), dims.pop(), self._counter_ptr()
+
     def forward(self, indices: torch.Tensor, offsets: torch.Tensor,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         dev = require_gpu(indices, offsets, per_sample_weights, self.weights)

@@ -219,6 +219,27 @@ class _FusedGatherInteraction(torch.autograd.Function):
         return gd, None, None, None, None
 
 
+def _quantized_gather_interaction(dense: torch.Tensor, gather, F: int, pad_rows: bool = False) -> torch.Tensor:
+    """The dot interaction over a quantized collection's rows (csrc/dlrm_interaction.hip interaction_gather_nbit_fwd_kernel):
+    the kernel copies the INT8 / INT4 / INT2 rows of a one-id-per-bag batch itself and dequantizes them into its MFMA
+    operands; the pooled float32 [B, F, D] buffer does not exist.  `gather`: quant.EmbeddingBagCollection.gather_interaction's
+    answer.  Forward only: the entry has no backward, the caller makes sure autograd wants none."""
+    (feat_weights, feat_row_bytes, feat_rows, bits, D, counter), ids, B = gather
+    dense = dense.contiguous()
+    if dense.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("dot interaction over quantized tables: forward only, but autograd wants a gradient for `dense`")
+    if dense.shape != (B, D) or dense.dtype != torch.float32 or ids.numel() != F * B:
+        raise RuntimeError(f"dot interaction: dense {tuple(dense.shape)} and {ids.numel()} ids do not match the lookup "
+                           f"(batch {B}, {F} features, dim {D})")
+    width, stride = _interaction_row(F, D, pad_rows)
+    buf = torch.empty((B, stride), dtype=torch.float32, device=dense.device)
+    with torch.cuda.device(dense.device):
+        check(_lib.load().tbe_dlrm_interaction_gather_forward_nbit(
+            ptr(dense), ptr(feat_weights), ptr(feat_row_bytes), ptr(feat_rows), bits, ptr(ids), B, F, D, ptr(buf), stride,
+            counter, stream_ptr(dense.device)), "tbe_dlrm_interaction_gather_forward_nbit")
+    return buf if stride == width else buf[:, :width]
+
+
 def _fused_interaction_ok(dense: torch.Tensor, sparse: torch.Tensor) -> bool:
     F, D = sparse.shape[1], sparse.shape[2]
     return (dense.is_cuda and dense.dtype == torch.float32 and sparse.dtype == torch.float32
@@ -330,7 +351,32 @@ class DLRM(nn.Module):
             return None
         return ebc.compute_deferred(ebc.input_dist(sparse_features).wait())
 
+    def _quantized_gather(self, dense_features: torch.Tensor, sparse_features: KeyedJaggedTensor):
+        """A quantized collection's answer for this batch (quant.EmbeddingBagCollection.gather_interaction), or None when
+        the interaction cannot gather its rows itself: then the lookup + interaction pair runs, as for every other
+        collection."""
+        sa = self.sparse_arch
+        ebc = sa.embedding_bag_collection
+        if not (self.fused_lookup and self.inter_arch.fused and 1 <= sa.F <= 27 and sa.D in (64, 128)
+                and dense_features.is_cuda and dense_features.dtype == torch.float32
+                and hasattr(ebc, "gather_interaction")):
+            return None
+        # the entry has no backward: only where autograd records nothing for the interaction's dense input
+        if torch.is_grad_enabled() and (dense_features.requires_grad
+                                        or any(p.requires_grad for p in self.dense_arch.parameters())):
+            return None
+        gather = ebc.gather_interaction(sparse_features)
+        if gather is None or gather[1].device != dense_features.device:
+            return None
+        return gather
+
     def forward(self, dense_features: torch.Tensor, sparse_features: KeyedJaggedTensor) -> torch.Tensor:
+        gather = self._quantized_gather(dense_features, sparse_features)
+        if gather is not None:
+            embedded_dense = self.dense_arch(dense_features)
+            concatenated = _quantized_gather_interaction(embedded_dense, gather, self.sparse_arch.F, self.inter_arch.pad_rows)
+            self.fused_lookup_steps += 1
+            return self.over_arch(concatenated)
         lookup = self._deferred_lookup(dense_features, sparse_features)
         if lookup is not None:
             with _EagerFinish.enable(self.deferred_dense_finish):

@@ -67,6 +67,24 @@ class EmbeddingBagCollection(nn.Module):
         out = self._tbe(features.values(), features.offsets(), features.weights_or_none() if self._is_weighted else None)
         return KeyedTensor(keys=self._feature_names, length_per_key=self._lengths_per_embedding, values=out)
 
+    def gather_interaction(self, features: KeyedJaggedTensor):
+        """For a batch the dot interaction can gather itself (models/dlrm.py, tbe_dlrm_interaction_gather_forward_nbit):
+        (the fused module's gather_interaction_args(), the ids [F * B] feature-major, B).  None — nothing consumed, the
+        caller runs forward() — unless the collection is unweighted, its tables share one bit rate and dim, and the batch
+        has this collection's keys in order, exactly one id per bag as host-known metadata (fixed_lengths() all 1) and int64
+        values on the tables' device."""
+        if self._is_weighted or features.keys() != self._feature_names:
+            return None
+        fixed = features.fixed_lengths()
+        values = features.values()
+        if (fixed is None or any(n != 1 for n in fixed) or values.dtype != torch.int64
+                or values.device != self._tbe.weights.device):
+            return None
+        args = self._tbe.gather_interaction_args()
+        if args is None:
+            return None
+        return args, values.contiguous().view(-1), features.stride()
+
     def state_dict(self, destination: Optional[Dict[str, Any]] = None, prefix: str = "", keep_vars: bool = False):
         if destination is None:
             destination = OrderedDict()
