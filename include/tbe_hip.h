@@ -727,6 +727,26 @@ int tbe_dlrm_interaction_gather_backward_sgd_f32(const float* dense, const uint6
                                                  float* grad_sparse, int32_t* bounds_errors, const uint8_t* single,
                                                  float learning_rate, void* stream);
 
+/* tbe_dlrm_interaction_gather_forward_f32 / _gather_backward_f32 over FP16 training tables (the tables of the tbe_*_f16w
+ * entries: rows of D halves, row r of a table at base + r * D * 2 bytes).  Each takes the argument list of its _f32 twin;
+ * feat_weights [F] holds the byte addresses of the FP16 tables, every one 16-byte aligned (a device array the library does
+ * not read on the host: the caller checks it, as SplitTableBatchedEmbeddingBagsCodegen.gather_layout(half_tables=True)
+ * does).  A half converts to float32 exactly, denormals included, so each entry computes the _f32 entry's result on the
+ * up-cast tables, bit for bit: X[r] = float32(W_{r-1}[indices[(r-1)*B + b]]), ids classified with feat_rows / feat_window
+ * as there (a foreign id, TBE_ID_SKIP or a bad id gives a row of +0; bad ids are counted once in bounds_errors), sums in
+ * the same order, stores by the same rules, nothing else written and the tables only read.  The forward keeps the rows as
+ * halves in LDS and converts them where they become MFMA operands; the backward fetches 8 bytes per lane and converts
+ * when it stages a sample.  grad_dense [B, D] and grad_sparse [B, F*D] are float32: what tbe_backward_*_f16w takes.
+ * 1 <= F <= 27, D in {64, 128}; the errors, before any launch, are the _f32 twins'. */
+int tbe_dlrm_interaction_gather_forward_f16w(const float* dense, const uint64_t* feat_weights, const int64_t* feat_rows,
+                                             const int64_t* feat_window, const int64_t* indices, int32_t B, int32_t F,
+                                             int32_t D, float* out, int64_t out_row_stride, int32_t* bounds_errors,
+                                             void* stream);
+int tbe_dlrm_interaction_gather_backward_f16w(const float* dense, const uint64_t* feat_weights, const int64_t* feat_rows,
+                                              const int64_t* feat_window, const int64_t* indices, const float* grad_out,
+                                              int64_t grad_row_stride, int32_t B, int32_t F, int32_t D, float* grad_dense,
+                                              float* grad_sparse, int32_t* bounds_errors, void* stream);
+
 /* tbe_dlrm_interaction_gather_forward_f32 over quantized inference tables (format: "Quantized inference tables" below), forward
  * only: the interaction copies the INT8 / INT4 / INT2 rows as they are stored and dequantizes them where they become MFMA
  * operands; no FP32 [B, F, D] buffer exists.  One bit rate per launch (bit_rate = 8, 4 or 2), every table of dim D.

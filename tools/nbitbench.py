@@ -11,7 +11,13 @@ windows.  The two outputs must be equal bit for bit before anything is timed.  `
 (max - min) over the rounds; `kernel_not_slower` says whether fused's median is within that spread of the pair's or below it.
 Bytes are counted from the shapes: ids, the rows' header + data bytes, the dense row and the output row; the pair also
 writes and reads the pooled float32 buffer.
-Usage: python tools/nbitbench.py [--gather] [--batch 65536,4096] [--pooling 1,20] [--cap ROWS] [--rounds 7] [--iters 20]
+
+--gather-f16 times the gather interaction over FP16 training tables, forward and backward: `fused`
+(tbe_dlrm_interaction_gather_forward_f16w / _backward_f16w) against the `pair` an FP16 model runs without it
+(tbe_forward_pooled_f16w + tbe_dlrm_interaction_forward_f32; tbe_dlrm_interaction_backward_f32 on the pooled buffer) and
+against the FP32 gather kernels on FP32 tables of the same shape.  Same rounds, windows, equality check and verdict, per
+direction.
+Usage: python tools/nbitbench.py [--gather | --gather-f16] [--batch 65536,4096] [--pooling 1,20] [--cap ROWS] [--rounds 7] [--iters 20]
        [--json FILE]"""
 import argparse
 import json
@@ -112,6 +118,70 @@ def gather_interaction(lib, st, fp32, nbit, rows, D, batches, rounds, iters, gen
     return records
 
 
+def half_gather_interaction(lib, st, fp32, half, rows, D, batches, rounds, iters, gen):
+    """The --gather-f16 records: per batch and direction, fused / pair / fp32 times."""
+    F, dev = len(rows), torch.device("cuda", 0)
+    P = F * (F + 1) // 2
+    lay32, lay16, records = fp32._get_layout(), half._get_layout(), []
+    for B in batches:
+        ids = torch.cat([torch.randint(0, r, (B,), generator=gen, device=dev, dtype=torch.int64) for r in rows])
+        offsets = torch.arange(F * B + 1, dtype=torch.int64, device=dev)
+        dense, grad = torch.randn(B, D, device=dev), torch.randn(B, D + P, device=dev)
+        pooled = torch.empty((B, F * D), dtype=torch.float32, device=dev)
+        keys = ("fused", "pair", "fp32")
+        out = {k: torch.empty((B, D + P), dtype=torch.float32, device=dev) for k in keys}
+        gd = {k: torch.empty((B, D), dtype=torch.float32, device=dev) for k in keys}
+        gs = {k: torch.empty((B, F * D), dtype=torch.float32, device=dev) for k in keys}
+
+        def gather_fwd(entry, lay, k):
+            rc = entry(dense.data_ptr(), lay.feat_weights.data_ptr(), lay.feat_rows.data_ptr(), None, ids.data_ptr(), B, F, D,
+                       out[k].data_ptr(), D + P, None, st)
+            assert rc == 0, lib.tbe_last_error()
+
+        def gather_bwd(entry, lay, k):
+            rc = entry(dense.data_ptr(), lay.feat_weights.data_ptr(), lay.feat_rows.data_ptr(), None, ids.data_ptr(),
+                       grad.data_ptr(), D + P, B, F, D, gd[k].data_ptr(), gs[k].data_ptr(), None, st)
+            assert rc == 0, lib.tbe_last_error()
+
+        def pair_fwd():
+            lib.tbe_forward_pooled_f16w(lay16.feat_weights.data_ptr(), lay16.feat_D.data_ptr(), lay16.feat_out_offset.data_ptr(),
+                                        lay16.feat_rows.data_ptr(), F, B, D, ids.data_ptr(), F * B, offsets.data_ptr(), None, 0,
+                                        None, pooled.data_ptr(), F * D, None, None, st)
+            lib.tbe_dlrm_interaction_forward_f32(dense.data_ptr(), pooled.data_ptr(), B, F, D, out["pair"].data_ptr(), D + P, st)
+
+        def pair_bwd():  # reads the pooled buffer the pair's forward left
+            lib.tbe_dlrm_interaction_backward_f32(dense.data_ptr(), pooled.data_ptr(), grad.data_ptr(), D + P, B, F, D,
+                                                  gd["pair"].data_ptr(), gs["pair"].data_ptr(), st)
+
+        forward = {"fused": lambda: gather_fwd(lib.tbe_dlrm_interaction_gather_forward_f16w, lay16, "fused"), "pair": pair_fwd,
+                   "fp32": lambda: gather_fwd(lib.tbe_dlrm_interaction_gather_forward_f32, lay32, "fp32")}
+        backward = {"fused": lambda: gather_bwd(lib.tbe_dlrm_interaction_gather_backward_f16w, lay16, "fused"), "pair": pair_bwd,
+                    "fp32": lambda: gather_bwd(lib.tbe_dlrm_interaction_gather_backward_f32, lay32, "fp32")}
+        for fn in (*forward.values(), *backward.values()):
+            fn()
+        torch.cuda.synchronize()
+        for t in (out, gd, gs):
+            assert torch.equal(t["fused"].view(torch.int32), t["pair"].view(torch.int32)), f"B={B}: fused != pair"
+        io_fwd = F * B * 8 + B * D * 4 + B * (D + P) * 4                       # ids, the dense row, the output row
+        io_bwd = F * B * 8 + B * D * 4 + B * (D + P) * 4 + B * (F + 1) * D * 4  # ids, dense, grad_out, the two gradients
+        for direction, variants, io in (("forward", forward, io_fwd), ("backward", backward, io_bwd)):
+            res = rounds_of(variants, rounds, iters)
+            # per row element the pair moves: forward the half, then the pooled float written and read; backward the pooled float
+            pair_row = 2 + 4 + 4 if direction == "forward" else 4
+            bytes_of = {"fused": io + F * B * D * 2, "pair": io + F * B * D * pair_row, "fp32": io + F * B * D * 4}
+            for key, r in res.items():
+                r["algorithmic_bytes"] = bytes_of[key]
+                r["TBps"] = bytes_of[key] / (r["median_us"] * 1e-6) / 1e12
+            spread = max(res[k]["max_us"] - res[k]["min_us"] for k in ("fused", "pair"))
+            rec = {"batch": B, "direction": direction, "outputs_bit_equal": True, "variants": res, "spread_us": spread,
+                   "pair_over_fused": res["pair"]["median_us"] / res["fused"]["median_us"],
+                   "fp32_over_fused": res["fp32"]["median_us"] / res["fused"]["median_us"],
+                   "kernel_not_slower": bool(res["fused"]["median_us"] <= res["pair"]["median_us"] + spread)}
+            records.append(rec)
+            print(json.dumps(rec), flush=True)
+    return records
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", default="65536,4096")
@@ -122,6 +192,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20, help="least calls per timed window")
     ap.add_argument("--json", default="")
     ap.add_argument("--gather", action="store_true", help="time the fused gather interaction against the lookup + interaction pair")
+    ap.add_argument("--gather-f16", action="store_true",
+                    help="time the gather interaction over FP16 tables, forward and backward, against its pair and the FP32 kernels")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     lib, st = _lib.load(), None
@@ -134,6 +206,19 @@ def main():
 
     g = torch.Generator(device=dev)
     g.manual_seed(1234)
+    if args.gather_f16:
+        half = SplitTableBatchedEmbeddingBagsCodegen([(r, D, EmbeddingLocation.DEVICE, ComputeDevice.CUDA) for r in rows],
+                                                     device=dev, weights_precision=SparseType.FP16)
+        for w16, w32 in zip(half.split_embedding_weights(), fp32.split_embedding_weights()):
+            w16.copy_(w32)
+        record = {"rows": rows, "dim": D, "rounds": args.rounds, "iters": args.iters, "window_ms": WINDOW_MS,
+                  "fp16_gather_interaction": half_gather_interaction(lib, st, fp32, half, rows, D,
+                                                                     [int(b) for b in args.batch.split(",")], args.rounds,
+                                                                     args.iters, g)}
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(record, f, indent=1)
+        return
     if args.gather:
         nbit = {}
         for name, ty in TYPES.items():

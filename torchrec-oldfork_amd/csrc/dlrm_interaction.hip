@@ -18,19 +18,22 @@
 //   backward: dX = (G + G^T) X with G the strict upper-triangular matrix of d(flat),
 //             2 x D/16 tiles, K = R; d(dense) additionally receives d(out)[:, :D].
 //
-// Five kernels; a block of work they have in common is written once.  What a kernel keeps for itself is how a sample's rows ARRIVE — that is
+// Eight kernels; a block of work they have in common is written once.  What a kernel keeps for itself is how a sample's rows ARRIVE — that is
 // where their register budgets differ — and everything behind the arrival is shared:
 //   forward   interaction_fwd_kernel         register loads in MFMA-fragment shape, predicated straight-line stores
 //             interaction_fwd_glds_kernel    LDS-DMA copy from the pooled buffer, unrolled, per-lane offsets kept in registers
 //             interaction_gather_fwd_kernel  LDS-DMA copy from the tables, rolled, ids through an LDS slot
 //             interaction_gather_nbit_fwd_kernel  the same from INT8 / INT4 / INT2 tables: rows stay quantized in LDS and are
 //                                            dequantized into the fragments (its own section, behind the gather backward)
+//             interaction_gather_f16_fwd_kernel   the same from FP16 training tables: rows stay halves in LDS and are converted
+//                                            into the fragments (the last section, with its backward)
 //     shared: FwdWave (the wave's geometry), fwd_contract, fwd_stage_pairs; by the two LDS-DMA kernels also FwdImage (the
 //             per-wave LDS image, which the host sizes the launch from), fwd_read_fragments, fwd_read_dense / fwd_store_dense,
 //             fwd_store_pairs_counted
 //   backward  interaction_bwd_kernel         rows from the pooled buffer (XLoader)
 //             interaction_gather_bwd_kernel  rows from the tables (shflu64 of the feature lanes' addresses); <NT, true> also
 //                                            applies SGD to once-touched rows (its blocks have this one user and stay inline)
+//             interaction_gather_f16_bwd_kernel   rows from FP16 tables, 8 bytes per lane, converted when they are staged
 //     shared: BwdTile (the LDS tile, host and device), BwdWave, bwd_zero_tile, bwd_pair_table, bwd_load_pair_grads,
 //             bwd_load_gdense, bwd_stage, bwd_contract, bwd_store (the dense kernel spells the store loop itself, and both
 //             spell the six-line write-back of dX: see there for what the shared forms cost)
@@ -698,13 +701,14 @@ __device__ __forceinline__ GatherLane load_gather_lane(const uint64_t* feat_weig
   g.counts = lane < F;
   return g;
 }
-// Address of the row `id` selects (`miss` for a non-local or bad id); counts bad ids into nbad.
-template <int D>
+// Address of the row `id` selects in a table of ELEM-byte elements (`miss` for a non-local or bad id); counts bad ids into
+// nbad.
+template <int D, int ELEM>
 __device__ __forceinline__ uint64_t gather_row_address(const GatherLane& g, int64_t id, uint64_t miss, int& nbad) {
   int64_t local;
   const int cls = classify_id(g.win, id, local);
   if (cls == kIdBad && g.counts) ++nbad;
-  return cls == kIdLocal ? g.base + static_cast<uint64_t>(local) * (D * sizeof(float)) : miss;
+  return cls == kIdLocal ? g.base + static_cast<uint64_t>(local) * (D * ELEM) : miss;
 }
 __device__ __forceinline__ void report_bad_ids(int nbad, int32_t* bounds_errors) {
   if (bounds_errors == nullptr) return;
@@ -778,7 +782,7 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_fwd_kernel(const fl
     const int64_t id = read_id();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     wave_lds_fence();
-    issue_copy(b, gather_row_address<D>(gl, id, zero_row, nbad));
+    issue_copy(b, gather_row_address<D, sizeof(float)>(gl, id, zero_row, nbad));
     if (b + stride_b < B) issue_ids(b + stride_b);
   }
   for (; b < B; b += stride_b) {
@@ -796,7 +800,7 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_fwd_kernel(const fl
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     wave_lds_fence();
     if (b + stride_b < B) {
-      issue_copy(b + stride_b, gather_row_address<D>(gl, next_id, zero_row, nbad));
+      issue_copy(b + stride_b, gather_row_address<D, sizeof(float)>(gl, next_id, zero_row, nbad));
       if (b + 2 * stride_b < B) issue_ids(b + 2 * stride_b);
     }
     f32x4 acc00, acc01, acc11;
@@ -891,7 +895,7 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
   int b = w.first_sample();
   int64_t next_id = 0;  // this lane's id of the sample AFTER the one whose rows are in flight
   if (b < B) {
-    const uint64_t row_addr = gather_row_address<D>(gl, my_ids[b], 0, nbad);
+    const uint64_t row_addr = gather_row_address<D, sizeof(float)>(gl, my_ids[b], 0, nbad);
     if constexpr (SGD) once_in_flight = publish_once(row_addr, my_single(b), 0);
     load_x(b, row_addr);
     if (b + stride_b < B) {
@@ -907,7 +911,7 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
     const float4 gdense = bwd_load_gdense(w, grad_out, b, grad_stride);
     const int nb = b + stride_b;
     if (nb < B) {
-      const uint64_t row_addr = gather_row_address<D>(gl, next_id, 0, nbad);
+      const uint64_t row_addr = gather_row_address<D, sizeof(float)>(gl, next_id, 0, nbad);
       if constexpr (SGD) once_in_flight = publish_once(row_addr, next_single, slot ^ 1);
       load_x(nb, row_addr);
       if (nb + stride_b < B) {
@@ -1027,14 +1031,13 @@ __global__ __launch_bounds__(256, 2) void interaction_gather_bwd_kernel(const fl
 // Workgroups per CU (= waves per SIMD).  The image is 7 KB a wave at most, so LDS would admit five; registers decide: D = 64 fits
 // the 128 VGPRs of four waves, D = 128 (64 operand registers) needs the 168 of three.
 constexpr int nbit_wgs_per_cu(int D) { return D <= 64 ? 4 : 3; }
-template <int D, int BITS>
-struct NbitImage {
-  static constexpr int EPB = 8 / BITS;                    // elements per byte
-  static constexpr int C = (D / EPB + 4 + 15) / 16;       // 16-byte chunks that hold header + data of a row
+// The raw image of rows of CHUNKS 16-byte chunks (also the FP16 tables' image, further down).
+template <int D, int CHUNKS>
+struct RawImage {
+  static constexpr int C = CHUNKS;                        // 16-byte chunks of a row as stored
   static constexpr int PC = C | 1;                        // LDS pitch of a raw row, in chunks
   static constexpr int PRD = D / 4;                       // chunks of the dense row
   static constexpr int DS = FwdImage<D>::DS;
-  static_assert(BITS == 8 || BITS == 4 || BITS == 2, "INT8 / INT4 / INT2");
   static_assert(C * 16 <= 256 * sizeof(float), "a bad id's chunks come from g_zero_row (256 floats)");
   static constexpr int chunks(int R) { return PRD + (R - 1) * PC; }
   static constexpr int copies(int R) { return (chunks(R) + kWave - 1) / kWave; }
@@ -1043,6 +1046,11 @@ struct NbitImage {
   static constexpr int floats(int R) { return ids_offset(R) + kIdSlotFloats; }
   static constexpr int MAXI = copies(kBwdMaxRows);
   static constexpr int row_byte(int f) { return 16 * (PRD + f * PC); }  // where the row of feature f starts in the image
+};
+template <int D, int BITS>
+struct NbitImage : RawImage<D, (D / (8 / BITS) + 4 + 15) / 16> {  // chunks that hold header + data of a row
+  static constexpr int EPB = 8 / BITS;                            // elements per byte
+  static_assert(BITS == 8 || BITS == 4 || BITS == 2, "INT8 / INT4 / INT2");
 };
 
 __device__ __forceinline__ float half_bits_to_f32(uint32_t bits) {
@@ -1194,6 +1202,240 @@ __global__ __launch_bounds__(256, nbit_wgs_per_cu(D)) void interaction_gather_nb
     wave_lds_fence();
     stores_behind_copy = fwd_store_pairs_counted(orow, zs, w);
     wave_lds_fence();  // zs is rewritten by the next sample
+  }
+  report_bad_ids(nbad, bounds_errors);
+}
+
+// ---- pooling factor 1, FP16 training tables: the rows stay halves until they are MFMA operands (forward) or staged (backward) --
+// A half is exactly representable in FP32, denormals included (v_cvt_f32_f16 does not flush them: the FP16 / FP64 denormal
+// mode is on), so both kernels compute what their FP32 twins compute on the up-cast tables, bit for bit, while every row read
+// moves half the bytes.  Ids are classified as the FP32 training kernels classify them (load_gather_lane, classify_id: local,
+// foreign, TBE_ID_SKIP, bad), and a row is D * 2 bytes from its table's base, which must be 16-byte aligned.
+//
+// Forward.  The raw image (RawImage<D, D / 8>): the dense row, FP32, in slots [0, D / 4); the row of feature f as its C = D / 8
+// chunks of 8 halves, copied as stored by the instructions of the nbit kernel (slot D / 4 + f * PC + c holds chunk
+// min(c, C - 1); slots behind the last row and rows of bad, foreign and skipped ids hold chunks of g_zero_row, halves of +0).
+// 7.6 KB at F = 26, D = 128, where FwdImage<128> has 14 KB.
+//
+// Fragments and the pitch PC.  Lane (r, q) needs columns 16 s + 4 q + e of rows r and r + 16: the 8 bytes at row byte
+// 32 s + 8 q, one ds_read_b64 per segment and row tile, four conversions each.  A ds_read_b64 of 64 lanes moves 512 bytes,
+// four sweeps of the 32 banks at best, so the best a layout can do is to put exactly 4 lanes on each of the 16 bank PAIRS.
+// In 8-byte units lane (r, q) reads pair (2 PC r + 4 s + q + const) mod 16.  C is 8 or 16: with PC = C every row starts on
+// the same pair and the 16 rows of a q collide 16-fold.  With PC odd, 2 PC r mod 16 takes each of the 8 even values for two
+// rows (r and r + 8, the floor of a pitch in whole 16-byte chunks), and q = 0 .. 3 shifts that set by 0 .. 3: every pair gets
+// 2 rows x 2 values of q = 4 lanes, in every half-wave (q in {0, 1} or {2, 3}) exactly 2.  PC = C | 1 is the smallest odd
+// pitch; one pad chunk per row (6 %).  The four lanes with r = 0 take their tile-0 operands from the FP32 dense slots (16 lanes
+// per address: a broadcast), as in the nbit kernel.
+//
+// Pipeline: that of interaction_gather_fwd_kernel (ids two samples ahead through the id slot, rows one sample ahead, counted
+// waits); contraction, staging and stores are the shared forward blocks.
+//
+// Workgroups per CU (= waves per SIMD).  The largest image (F = 27, D = 128) is 9968 bytes a wave, so LDS admits four
+// workgroups at either D; registers decide, as for the nbit kernel.  The compiler's report: under the 128 VGPRs of four
+// waves D = 64 uses all 128, under the 168 of three D = 128 (32 registers of halves and 32 of dense operands live across the
+// copy issue, 64 operands behind it) uses all 168; no scratch and no spill in either.  The FP32 kernel runs D = 128 at 170
+// VGPRs and two waves.
+constexpr int f16_wgs_per_cu(int D) { return D <= 64 ? 4 : 3; }
+template <int D>
+using HalfImage = RawImage<D, D / 8>;
+
+__device__ __forceinline__ float4 half4_to_f32(half4 h) {
+  return make_float4(static_cast<float>(h.x), static_cast<float>(h.y), static_cast<float>(h.z), static_cast<float>(h.w));
+}
+
+template <int D>
+__global__ __launch_bounds__(256, f16_wgs_per_cu(D)) void interaction_gather_f16_fwd_kernel(
+    const float* __restrict__ dense, const uint64_t* __restrict__ feat_weights, const int64_t* __restrict__ feat_rows,
+    const int64_t* __restrict__ feat_window, const int64_t* __restrict__ indices, float* __restrict__ out,
+    int32_t* __restrict__ bounds_errors, int B, int F, int64_t out_stride) {
+  extern __shared__ float smem[];
+  using Image = HalfImage<D>;
+  constexpr int NS = D / 16;
+  const FwdWave<D> w(F, out, out_stride);
+  const int lane = w.lane;
+  const int R = w.R;
+  const int NI = Image::copies(R);
+  float* xs = smem + w.wave * Image::floats(R);  // the dense row, then the rows of halves
+  const uint8_t* image = reinterpret_cast<const uint8_t*>(xs);
+  float* zs = xs + Image::zs_offset(R);
+  float* ids = xs + Image::ids_offset(R);
+  w.zero_pad(zs);
+  const int stride_b = w.stride_b;
+  const GatherLane gl = load_gather_lane(feat_weights, feat_rows, feat_window, lane, F);
+  const uint64_t zero_row = reinterpret_cast<uint64_t>(&g_zero_row[0]);
+  int nbad = 0;
+  const uint32_t* id_words = reinterpret_cast<const uint32_t*>(indices) +
+                             2 * static_cast<int64_t>(min(lane >> 1, F - 1)) * B + (lane & 1);
+  auto issue_ids = [&](int b) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(id_words + 2 * static_cast<int64_t>(b)),
+                                     (__attribute__((address_space(3))) void*)ids, 4, 0, 0);
+  };
+  auto read_id = [&]() { return *reinterpret_cast<const int64_t*>(ids + 2 * min(lane, F - 1)); };
+  // copy instruction i fills slots 64 i .. 64 i + 63 (see above); `row_addr` is the feature lanes' row address for sample b
+  auto issue_copy = [&](int b, uint64_t row_addr) {
+    const uint64_t dn = reinterpret_cast<uint64_t>(dense + static_cast<int64_t>(b) * D);
+#pragma unroll 1
+    for (int i = 0; i < NI; ++i) {
+      const int slot = i * kWave + lane;
+      const int u = max(slot - Image::PRD, 0);
+      const int f = u / Image::PC;
+      const int c = min(u % Image::PC, Image::C - 1);
+      uint64_t src = shflu64(row_addr, min(f, F - 1)) + 16 * c;
+      if (f >= F) src = zero_row + 16 * c;
+      if (slot < Image::PRD) src = dn + 16 * slot;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                       (__attribute__((address_space(3))) void*)(xs + i * (kWave * 4)), 16, 0, 0);
+    }
+  };
+  // this lane's 8 bytes of segment 0 in row tile 0 / 1 (row 0 is the dense row: its lanes read feature 0 and do not use it)
+  const uint8_t* ra = image + Image::row_byte(max(w.row0 - 1, 0)) + 8 * w.kq;
+  const uint8_t* rb = image + Image::row_byte(w.row1 - 1) + 8 * w.kq;  // row1 >= 1: R >= 2
+  int stores_behind_copy = 0;
+  int b = w.first_sample();
+  if (b < B) {
+    issue_ids(b);
+    vm_wait_all_but<0>();
+    wave_lds_fence();
+    const int64_t id = read_id();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
+    issue_copy(b, gather_row_address<D, sizeof(_Float16)>(gl, id, zero_row, nbad));
+    if (b + stride_b < B) issue_ids(b + stride_b);
+  }
+  for (; b < B; b += stride_b) {
+    // the copy of sample b and the ids of the next sample have landed once everything but the stores issued after them
+    // has retired
+    vm_wait_all_but(stores_behind_copy);
+    wave_lds_fence();
+    half4 ha[NS], hb[NS];
+    float4 da[NS];  // tile-0 operands of the dense row, used by the r = 0 lanes
+    float4 dpass;
+    float dscal[Image::DS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) ha[s] = *reinterpret_cast<const half4*>(ra + 32 * s);
+    if (R > 16) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) hb[s] = *reinterpret_cast<const half4*>(rb + 32 * s);
+    } else {  // rows of +0, as fwd_read_fragments gives
+#pragma unroll
+      for (int s = 0; s < NS; ++s) hb[s] = half4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) da[s] = *reinterpret_cast<const float4*>(xs + 16 * s + 4 * w.kq);
+    fwd_read_dense(xs, w, dpass, dscal);
+    const int64_t next_id = read_id();  // of sample b + stride_b (stale when there is none: not used then)
+    // every read of the image and of the id slot has returned before the next copies may overwrite them
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
+    if (b + stride_b < B) {
+      issue_copy(b + stride_b, gather_row_address<D, sizeof(_Float16)>(gl, next_id, zero_row, nbad));
+      if (b + 2 * stride_b < B) issue_ids(b + 2 * stride_b);
+    }
+    FwdRows<NS> x;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      x.a[s] = w.row0 == 0 ? da[s] : half4_to_f32(ha[s]);
+      x.b[s] = half4_to_f32(hb[s]);
+    }
+    f32x4 acc00, acc01, acc11;
+    fwd_contract<NS>(x, acc00, acc01, acc11);
+    float* orow = out + static_cast<int64_t>(b) * out_stride;
+    fwd_store_dense(orow, w, dpass, dscal);
+    fwd_stage_pairs(zs, w, acc00, acc01, acc11);
+    wave_lds_fence();
+    stores_behind_copy = fwd_store_pairs_counted(orow, zs, w);
+    wave_lds_fence();  // zs is rewritten by the next sample
+  }
+  report_bad_ids(nbad, bounds_errors);
+}
+
+// Backward: interaction_gather_bwd_kernel<NT, false> with a row source of halves.  A lane fetches its four columns of a table
+// row as ONE 8-byte load and keeps them as loaded (two registers where the FP32 kernel keeps four) while they are in flight;
+// they are converted when the sample is staged, so no conversion stands between a load and the MFMA loop it flies behind.
+// Only the first load instruction can meet the dense row (v = lane < D / 4), which stays a 16-byte FP32 load of its own.
+// Tile, staging, contraction, stores and the LDS budget are the shared backward blocks.
+template <int NT>  // NT = D / 16 column tiles
+__global__ __launch_bounds__(256, 2) void interaction_gather_f16_bwd_kernel(
+    const float* __restrict__ dense, const uint64_t* __restrict__ feat_weights, const int64_t* __restrict__ feat_rows,
+    const int64_t* __restrict__ feat_window, const int64_t* __restrict__ indices, const float* __restrict__ grad_out,
+    float* __restrict__ grad_dense, float* __restrict__ grad_sparse, int32_t* __restrict__ bounds_errors, int B, int F,
+    int64_t grad_stride) {
+  extern __shared__ float smem[];
+  using T = BwdTile<NT>;
+  constexpr int D = T::D;
+  constexpr int XS = T::XS;
+  constexpr int LOG_V = T::LOG_V;
+  constexpr int MAXV = T::MAXV;
+  const BwdWave<NT> w(F);
+  const int lane = w.lane;
+  const int R = w.R;
+  const int stride_b = w.stride_b;
+  float* xs = smem + w.wave * T::kFloats;
+  float* gs = xs + T::XROWS * XS;
+  bwd_zero_tile<NT>(xs, gs, lane);
+  int pij[T::MAXP];
+  bwd_pair_table(w, pij);
+  wave_lds_fence();
+
+  const GatherLane gl = load_gather_lane(feat_weights, feat_rows, feat_window, lane, F);
+  const int64_t* my_ids = indices + static_cast<int64_t>(min(lane, F - 1)) * B;
+  int nbad = 0;
+  half4 hpre[MAXV];  // table rows in flight, as stored
+  float4 dpre = make_float4(0.f, 0.f, 0.f, 0.f);  // the dense row's piece of the lanes < D / 4
+  float gpre[T::MAXP];
+  const bool dense_lane = lane < D / 4;
+  // X of sample s: row 0 from dense, row r >= 1 from the address lane r-1 holds (0 = a zero row)
+  auto load_x = [&](int s, uint64_t row_addr) {
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+      const int v = lane + i * kWave;
+      const int r = min(v >> LOG_V, R - 1);
+      const int c = (v & ((1 << LOG_V) - 1)) * 4;
+      const uint64_t src = shflu64(row_addr, max(r - 1, 0));
+      if (v < w.nvec) {
+        if (i == 0 && dense_lane)
+          dpre = ld4(dense + static_cast<int64_t>(s) * D + c);
+        else
+          hpre[i] = src != 0 ? ldh4(reinterpret_cast<const _Float16*>(src) + c) : half4{0, 0, 0, 0};
+      }
+    }
+  };
+  int b = w.first_sample();
+  int64_t next_id = 0;  // this lane's id of the sample AFTER the one whose rows are in flight
+  if (b < B) {
+    load_x(b, gather_row_address<D, sizeof(_Float16)>(gl, my_ids[b], 0, nbad));
+    if (b + stride_b < B) next_id = my_ids[b + stride_b];
+    bwd_load_pair_grads(w, grad_out, b, grad_stride, gpre);
+  }
+  for (; b < B; b += stride_b) {
+    float4 pre[MAXV];
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) pre[i] = (i == 0 && dense_lane) ? dpre : half4_to_f32(hpre[i]);
+    bwd_stage(xs, gs, w, pre, gpre, pij);
+    const float4 gdense = bwd_load_gdense(w, grad_out, b, grad_stride);
+    const int nb = b + stride_b;
+    if (nb < B) {
+      load_x(nb, gather_row_address<D, sizeof(_Float16)>(gl, next_id, 0, nbad));
+      if (nb + stride_b < B) next_id = my_ids[nb + stride_b];
+      bwd_load_pair_grads(w, grad_out, nb, grad_stride, gpre);
+    }
+    wave_lds_fence();
+    f32x4 acc[2][NT];
+    bwd_contract(xs, gs, w, acc);
+    wave_lds_fence();  // every lane is done reading X before it is overwritten with dX
+    // the plain write-back of interaction_bwd_kernel (see there)
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int row = 16 * m + 4 * w.kq + q;
+          if (row < R) xs[row * XS + 16 * n + w.r16] = acc[m][n][q];
+        }
+    wave_lds_fence();
+    bwd_store(xs, w, gdense, grad_dense, grad_sparse, b, F);
+    wave_lds_fence();
   }
   report_bad_ids(nbad, bounds_errors);
 }
@@ -1360,6 +1602,54 @@ extern "C" int tbe_dlrm_interaction_gather_forward_nbit(const float* dense, cons
           what, B, nbit_wgs_per_cu(DD), Image::floats(F + 1), Image::floats(kBwdMaxRows), stream, dense, feat_weights, feat_row_bytes,
           feat_rows, indices, out, bounds_errors, B, F, out_stride);
     });
+  });
+  return rc;
+}
+
+static_assert(image_covers<HalfImage<128>>(kBwdMaxRows) && image_covers<HalfImage<64>>(kBwdMaxRows) &&
+                  f16_wgs_per_cu(128) * workgroup_lds_bytes(HalfImage<128>::floats(kBwdMaxRows)) <= kCuLdsBytes &&
+                  f16_wgs_per_cu(64) * workgroup_lds_bytes(HalfImage<64>::floats(kBwdMaxRows)) <= kCuLdsBytes,
+              "the largest images of halves, f16_wgs_per_cu workgroups per CU");
+
+// The gather forward over FP16 tables.  The feat_* arrays are device memory and are not read here: that every table base is
+// 16-byte aligned is the caller's to check (gather_layout(half_tables=True) does).
+extern "C" int tbe_dlrm_interaction_gather_forward_f16w(const float* dense, const uint64_t* feat_weights,
+                                                        const int64_t* feat_rows, const int64_t* feat_window,
+                                                        const int64_t* indices, int32_t B, int32_t F, int32_t D, float* out,
+                                                        int64_t out_row_stride, int32_t* bounds_errors, void* stream) {
+  const char* what = "tbe_dlrm_interaction_gather_forward_f16w";
+  if (int rc = check_gather_args(what, B, F, D, out_row_stride, {dense}, "dense", {feat_weights, feat_rows, out}, indices)) return rc;
+  if (B == 0) return TBE_OK;
+  int rc = TBE_OK;
+  dispatch_value<64, 128>(D, [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    using Image = HalfImage<DD>;
+    rc = launch_interaction<interaction_gather_f16_fwd_kernel<DD>>(what, B, f16_wgs_per_cu(DD), Image::floats(F + 1),
+                                                                   Image::floats(kBwdMaxRows), stream, dense, feat_weights,
+                                                                   feat_rows, feat_window, indices, out, bounds_errors, B, F,
+                                                                   out_row_stride);
+  });
+  return rc;
+}
+
+extern "C" int tbe_dlrm_interaction_gather_backward_f16w(const float* dense, const uint64_t* feat_weights,
+                                                         const int64_t* feat_rows, const int64_t* feat_window,
+                                                         const int64_t* indices, const float* grad_out,
+                                                         int64_t grad_row_stride, int32_t B, int32_t F, int32_t D,
+                                                         float* grad_dense, float* grad_sparse, int32_t* bounds_errors,
+                                                         void* stream) {
+  const char* what = "tbe_dlrm_interaction_gather_backward_f16w";
+  if (int rc = check_gather_args(what, B, F, D, grad_row_stride, {dense, grad_dense, grad_sparse}, "tensors",
+                                 {feat_weights, feat_rows, grad_out}, indices))
+    return rc;
+  if (B == 0) return TBE_OK;
+  int rc = TBE_OK;
+  dispatch_value<64, 128>(D, [&](auto d) {
+    constexpr int NT = decltype(d)::value / 16;
+    rc = launch_interaction<interaction_gather_f16_bwd_kernel<NT>>(what, B, 2, BwdTile<NT>::kFloats, BwdTile<NT>::kFloats, stream,
+                                                                   dense, feat_weights, feat_rows, feat_window, indices,
+                                                                   grad_out, grad_dense, grad_sparse, bounds_errors, B, F,
+                                                                   grad_row_stride);
   });
   return rc;
 }

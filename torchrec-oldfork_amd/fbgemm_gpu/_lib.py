@@ -187,16 +187,18 @@ SIGNATURES = {
         ctypes.c_int, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p]),
     "tbe_dlrm_interaction_backward_f32": (
         ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p]),
-    "tbe_dlrm_interaction_gather_forward_f32": (
+    **{f"tbe_dlrm_interaction_gather_forward{wt}": (
         ctypes.c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p]),
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p])
+       for wt in ("_f32", "_f16w")},
     "tbe_dlrm_interaction_gather_forward_nbit": (
         ctypes.c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_i64, c_void_p, c_void_p]),
-    "tbe_dlrm_interaction_gather_backward_f32": (
+    **{f"tbe_dlrm_interaction_gather_backward{wt}": (
         ctypes.c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p,
-         c_void_p, c_void_p]),
+         c_void_p, c_void_p])
+       for wt in ("_f32", "_f16w")},
     "tbe_dlrm_interaction_gather_backward_sgd_f32": (
         ctypes.c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_void_p, c_void_p,

@@ -1339,15 +1339,20 @@ class SplitTableBatchedEmbeddingBagsCodegen(_TBEBase):
         self._enforce_bounds_check_mode()
         return out
 
-    def gather_layout(self):
+    def gather_layout(self, half_tables: bool = False):
         """(feat_weights, feat_rows, feat_window) device arrays for a consumer that fetches the rows itself
         (tbe_dlrm_interaction_gather_*), or None when this module's lookup is more than one row copy per id: anything but
         SUM pooling of fp32 DEVICE tables of one dim (a multiple of 4, so every table base is 16-B aligned), a row cache,
-        or BoundsCheckMode.FATAL (which must see a lookup's bad ids before the lookup returns)."""
+        or BoundsCheckMode.FATAL (which must see a lookup's bad ids before the lookup returns).
+        half_tables: FP16 tables are served too (the consumer then calls the _f16w entries; feat_weights are byte addresses
+        either way), under the same conditions with a dim that is a multiple of 8 — 16 bytes of halves."""
+        half = self.weights_dev.dtype == torch.float16
         if (self._cache is not None or self.pooling_mode != PoolingMode.SUM or self._feature_pooling is not None
-                or any(p != "dev" for p in self.placement) or len(set(self.dims_per_table)) != 1 or self.max_D % 4 != 0
+                or any(p != "dev" for p in self.placement) or len(set(self.dims_per_table)) != 1
+                or self.max_D % (8 if half else 4) != 0
                 or self.bounds_check_mode == BoundsCheckMode.FATAL or self.current_device.type != "cuda"
-                or self.weights_dev.dtype != torch.float32 or self.weights_dev.data_ptr() % 16 != 0):
+                or not (self.weights_dev.dtype == torch.float32 or (half and half_tables))
+                or self.weights_dev.data_ptr() % 16 != 0):
             return None
         lay = self._get_layout()
         return lay.feat_weights, lay.feat_rows, lay.feat_window

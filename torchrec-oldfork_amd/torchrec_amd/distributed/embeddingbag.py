@@ -1225,11 +1225,12 @@ class ShardedEmbeddingBagCollection(nn.Module):
             raise RuntimeError("compute_explicit: not available for this configuration (explicit_step_supported())")
         return ExplicitLookupStep(self, dist_input, halves=self.half_batch_exchange, early_replicated_lookup=not prefetched)
 
-    def deferred_lookup_supported(self, features: KeyedJaggedTensor) -> bool:
+    def deferred_lookup_supported(self, features: KeyedJaggedTensor, half_tables: bool = False) -> bool:
         """Whether compute_deferred() can serve this batch: the pooled output would be a plain copy of one table row per
         (sample, feature), in the collection's feature order, on this rank — so a consumer can fetch the rows itself.
-        One rank without exchange, replicated tables or row cache; SUM-pooled fp32 DEVICE tables of one dim; no per-sample
-        weights; exactly one id per bag.  Everything is known on the host without a sync."""
+        One rank without exchange, replicated tables or row cache; SUM-pooled fp32 DEVICE tables of one dim (FP16 ones
+        too for a consumer that says `half_tables`); no per-sample weights; exactly one id per bag.  Everything is known
+        on the host without a sync."""
         m = self._emb_module
         if self._has_cw or self._variable_batch:
             # a feature's row is spread over several tables of the lookup: the consumer cannot gather it (a variable-batch
@@ -1244,16 +1245,16 @@ class ShardedEmbeddingBagCollection(nn.Module):
         if (fixed is None or len(fixed) != F or any(n != 1 for n in fixed)
                 or features.values().numel() != F * features.stride() or features.weights_or_none() is not None):
             return False
-        return m.gather_layout() is not None
+        return m.gather_layout(half_tables) is not None
 
-    def compute_deferred(self, dist_input: SparseFeaturesDist) -> "DeferredLookup":
+    def compute_deferred(self, dist_input: SparseFeaturesDist, half_tables: bool = False) -> "DeferredLookup":
         """compute_and_output_dist for a consumer that gathers the table rows itself (models/dlrm.py: the dot interaction):
         input checks and the backward's side-stream sort now, no lookup kernel, no pooled buffer.  Check
-        deferred_lookup_supported() first."""
+        deferred_lookup_supported() with the same `half_tables` first."""
         m = self._emb_module
         with label("## tbe_lookup ##"):
             rec = m.lookup_deferred(dist_input.values, dist_input.offsets)
-        return DeferredLookup(m, rec, len(self._feature_names), self._lengths_per_embedding[0])
+        return DeferredLookup(m, rec, len(self._feature_names), self._lengths_per_embedding[0], half_tables)
 
     def forward(self, features: KeyedJaggedTensor) -> Awaitable[KeyedTensor]:
         return self.compute_and_output_dist(self.input_dist(features).wait())
@@ -1263,9 +1264,14 @@ class DeferredLookup:
     """A pooling-factor-1 lookup that has not been (and will not be) materialised: the ids, the tables' layout arrays for
     tbe_dlrm_interaction_gather_* and the record its fused backward needs (ShardedEmbeddingBagCollection.compute_deferred)."""
 
-    def __init__(self, module: nn.Module, rec: Any, F: int, D: int) -> None:
+    def __init__(self, module: nn.Module, rec: Any, F: int, D: int, half_tables: bool = False) -> None:
         self.module, self.rec, self.F, self.D, self.B = module, rec, F, D, rec.B
-        self.feat_weights, self.feat_rows, self.feat_window = module.gather_layout()
+        layout = module.gather_layout(half_tables)
+        if layout is None:
+            raise RuntimeError("DeferredLookup: the module's rows cannot be gathered by a consumer (gather_layout(): pooling, "
+                               "placement, table type, or a table base that is not 16-byte aligned)")
+        self.feat_weights, self.feat_rows, self.feat_window = layout
+        self.table_dtype = module.weights_dev.dtype  # torch.float16: the consumer calls the _f16w entries
 
     def begin_single_row_sgd(self):
         """(flags, optimizer struct) when the module lets the consumer apply the exact-SGD update of the once-touched rows

@@ -50,12 +50,14 @@ class _PipelinedEBC:
         return self.sharded.compute_explicit(self._dist_input(features), prefetched=prefetched)
 
 
-    def compute_deferred(self, features):
+    def compute_deferred(self, features, half_tables: bool = False):
         """The lookup whose rows the consumer gathers itself (embeddingbag.py DeferredLookup) on this batch's queued input
-        dist, or None when the collection cannot serve it that way (nothing is consumed then)."""
-        if not hasattr(self.sharded, "compute_deferred") or not self.sharded.deferred_lookup_supported(features):
+        dist, or None when the collection cannot serve it that way (nothing is consumed then).  half_tables: the consumer
+        also gathers from FP16 tables."""
+        if (not hasattr(self.sharded, "compute_deferred")
+                or not self.sharded.deferred_lookup_supported(features, half_tables)):
             return None
-        return self.sharded.compute_deferred(self._dist_input(features))
+        return self.sharded.compute_deferred(self._dist_input(features), half_tables)
 
 
 class TrainPipelineSparseDist:

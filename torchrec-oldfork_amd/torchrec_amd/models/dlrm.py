@@ -163,6 +163,11 @@ class _FusedDotInteraction(torch.autograd.Function):
         return gd, gs, None, None
 
 
+def _table_suffix(lookup) -> str:
+    """Which gather entries serve a DeferredLookup: those of its tables' element type."""
+    return "_f16w" if lookup.table_dtype == torch.float16 else "_f32"
+
+
 class _FusedGatherInteraction(torch.autograd.Function):
     """_FusedDotInteraction with the pooling-factor-1 lookup folded in (csrc/dlrm_interaction.hip gather kernels): the
     interaction reads the table rows itself, the pooled [B, F, D] buffer is neither written nor read.  `lookup` is the
@@ -170,7 +175,8 @@ class _FusedGatherInteraction(torch.autograd.Function):
     `placeholder` (the embedding module's zero-size leaf) keeps this node in the graph when `dense` needs no gradient.
     `single_row_sgd`: where the lookup's module allows it (exact SGD on fp32 tables, sort prepared: DeferredLookup
     .begin_single_row_sgd) the backward kernel writes the updated row of every contribution that alone touches its row
-    straight into the table, and the fused backward leaves those contributions out."""
+    straight into the table, and the fused backward leaves those contributions out.
+    A lookup over FP16 tables (DeferredLookup.table_dtype) takes the _f16w entries and always the plain backward."""
 
     @staticmethod
     def forward(ctx, dense, placeholder, lookup, pad_rows=False, single_row_sgd=False):
@@ -181,11 +187,12 @@ class _FusedGatherInteraction(torch.autograd.Function):
                                f"the lookup (batch {B}, dim {D}, float32 on {lookup.module.current_device})")
         width, stride = _interaction_row(F, D, pad_rows)
         buf = torch.empty((B, stride), dtype=torch.float32, device=dense.device)
+        name = f"tbe_dlrm_interaction_gather_forward{_table_suffix(lookup)}"
         with torch.cuda.device(dense.device):
-            check(_lib.load().tbe_dlrm_interaction_gather_forward_f32(
+            check(getattr(_lib.load(), name)(
                 ptr(dense), ptr(lookup.feat_weights), ptr(lookup.feat_rows), ptr(lookup.feat_window),
                 ptr(lookup.rec.indices), B, F, D, ptr(buf), stride, lookup.module._errors_ptr(), stream_ptr(dense.device)),
-                "tbe_dlrm_interaction_gather_forward_f32")
+                name)
         ctx.save_for_backward(dense)
         ctx.lookup = lookup
         ctx.single_row_sgd = single_row_sgd
@@ -201,7 +208,9 @@ class _FusedGatherInteraction(torch.autograd.Function):
         gs = torch.empty((B, F * D), dtype=torch.float32, device=dense.device)
         with torch.cuda.device(dense.device):
             # (flags, optimizer struct), the stream waiting for the sort behind the flags; None = the plain pair of calls
-            opened = lookup.begin_single_row_sgd() if ctx.single_row_sgd else None
+            # (never for FP16 tables: their update draws its rounding inside tbe_backward_*_f16w)
+            half = _table_suffix(lookup) == "_f16w"
+            opened = lookup.begin_single_row_sgd() if ctx.single_row_sgd and not half else None
             # the ids were counted by the forward: no counter here (include/tbe_hip.h)
             if opened is not None:
                 check(_lib.load().tbe_dlrm_interaction_gather_backward_sgd_f32(
@@ -210,11 +219,12 @@ class _FusedGatherInteraction(torch.autograd.Function):
                     ptr(opened[0]), opened[1].learning_rate, stream_ptr(dense.device)),
                     "tbe_dlrm_interaction_gather_backward_sgd_f32")
             else:
-                check(_lib.load().tbe_dlrm_interaction_gather_backward_f32(
+                name = f"tbe_dlrm_interaction_gather_backward{_table_suffix(lookup)}"
+                check(getattr(_lib.load(), name)(
                     ptr(dense), ptr(lookup.feat_weights), ptr(lookup.feat_rows), ptr(lookup.feat_window),
                     ptr(lookup.rec.indices), ptr(grad_out), grad_out.stride(0), B, F, D, ptr(gd), ptr(gs), None,
                     stream_ptr(dense.device)),
-                    "tbe_dlrm_interaction_gather_backward_f32")
+                    name)
         lookup.backward(gs, opened)
         return gd, None, None, None, None
 
@@ -323,6 +333,9 @@ class DLRM(nn.Module):
         # DeferredLookup (one rank, no exchange: embeddingbag.py deferred_lookup_supported).  False = always materialise.
         self.fused_lookup = True
         self.fused_lookup_steps = 0  # forwards that took the gather path (tests)
+        # FP16 tables on the gather path (tbe_dlrm_interaction_gather_*_f16w: the rows stay halves until the interaction
+        # converts them; same bits as the lookup + interaction pair).  Opt-in: False = FP16 collections take the pair.
+        self.fused_lookup_half_tables = False
         # On the gather path with exact SGD the interaction backward also writes the updated row of every contribution
         # that alone touches its row (_FusedGatherInteraction single_row_sgd).  False = the plain pair of calls (tests).
         self.fused_single_row_update = True
@@ -345,11 +358,12 @@ class DLRM(nn.Module):
                 and list(getattr(ebc, "_feature_names", ())) == list(sa.sparse_feature_names)):
             return None
         piped = getattr(ebc, "_pipelined", None)  # a train pipeline's forward on this collection (queued input dist)
+        half = bool(self.fused_lookup_half_tables)
         if piped is not None:
-            return piped.compute_deferred(sparse_features)
-        if not ebc.deferred_lookup_supported(sparse_features):
+            return piped.compute_deferred(sparse_features, half)
+        if not ebc.deferred_lookup_supported(sparse_features, half):
             return None
-        return ebc.compute_deferred(ebc.input_dist(sparse_features).wait())
+        return ebc.compute_deferred(ebc.input_dist(sparse_features).wait(), half)
 
     def _quantized_gather(self, dense_features: torch.Tensor, sparse_features: KeyedJaggedTensor):
         """A quantized collection's answer for this batch (quant.EmbeddingBagCollection.gather_interaction), or None when
