@@ -1101,6 +1101,55 @@ int tbe_relu_dropout_forward_f32(const float* a, int64_t n, float p, uint32_t si
 /* the backward autograd builds for examples/bert4rec/models/bert4rec.py:201-214 */
 int tbe_relu_dropout_backward_f32(const float* grad_h, const float* h, int64_t n, float p, float* grad_a, void* stream);
 
+/* BERT4Rec's HistoryArch (examples/bert4rec/models/bert4rec.py:323-409) in one launch each way, float32: the item table's
+ * lookup, jagged_2d_to_dense to L rows, the positional add, LayerNorm over the whole [L, E] sample and dropout.
+ * feat_weights [1], feat_rows [1], feat_window [2] or NULL: the one feature's table base address, row count and row window
+ *   as device arrays in the form of tbe_forward_nobag_f32 / feat_window above (the base 16-B aligned: the library cannot
+ *   check an address held in device memory).  ids int64 [N], offsets int64 [B + 1] with offsets[0] = 0, offsets[B] = N;
+ *   positional, gamma, beta [L, E]; y, grad_y [B, L, E]; stats [B, 2] = (mean, rstd); grad_emb [N, E].
+ *   forward   n = min(len_b, L), the FIRST L ids of a longer history (jagged_2d_to_dense's rule)
+ *             x[l, :] = table[id_{b,l}, :] + positional[l, :]  (l < n);   x[l, :] = positional[l, :]  (l >= n)
+ *             mean = (sum x) / (L E);  var = (sum (x - mean)^2) / (L E)  (two-pass, from the on-chip copy)
+ *             rstd = 1 / sqrtf(var + eps);   y = drop(((x - mean) * rstd) * gamma + beta)
+ *             An id outside [0, global rows) reads a zero row and adds one to *bounds_errors (optional), another shard's id
+ *             (feat_window) or TBE_ID_SKIP reads a zero row silently; a malformed bag (start < 0, end > N, start > end) is
+ *             empty and counted once.  No memory is touched through either.
+ *   backward  g' = drop'(grad_y) (the forward's keep decisions, drawn again);  xhat = (x - mean) * rstd with x recomputed from
+ *             the table rows and positional: neither x nor a mask is kept;  d = g' * gamma
+ *             c1 = (sum d) / (L E);  c2 = (sum d * xhat) / (L E);  g_x = rstd * ((d - c1) - xhat * c2)
+ *             (the form of tbe_residual_layernorm_backward_f32 over L * E elements)
+ *             grad_emb[offsets[b] + l, :] = g_x[l, :] for l < n with a row of this table; +0.0 for a bad or foreign id and for
+ *             the positions >= L of an over-long history: each of the N rows is written once.
+ *             grad_params [3, L, E] = (grad positional = sum_b g_x, grad gamma = sum_b g' * xhat, grad beta = sum_b g');
+ *             `want` = 1 (positional) | 2 (gamma) | 4 (beta) selects the planes that are computed and written (frozen
+ *             parameters: the others are left alone); want == 0 takes neither grad_params nor a workspace.  Otherwise the
+ *             row blocks' sums go to `workspace` (tbe_history_backward_workspace_bytes) and one launch finishes them.
+ *             The backward reads the table: it MUST be enqueued before the update that rewrites those rows (the fused TBE
+ *             backward of the same lookup), as tbe_backward_indice_weights_f32.
+ * Dropout, 0 <= p < 1: the draw of tbe_residual_layernorm_forward_f32 (the same domain tag) with (row, col) = (b, l * E + e)
+ *   and `site` as given.  p == 0 keeps everything, multiplies by nothing, and (seed, call, site) do not matter.
+ * One workgroup holds one sample's row in registers between the passes; every table row, positional, gamma and beta element
+ * is read once per sample and direction, y / grad_y / grad_emb are touched once, all as 16-B vectors.  Each product and add
+ * is rounded on its own; no float atomics; every sum runs in an order fixed by (B, L, E): two runs are bit-identical.
+ * Supported (tbe_history_supported returns 1): E % 4 == 0, 4 <= E <= 2048, L >= 1, L * E <= 32768 — (100, 256), (200, 128),
+ *   (137, 128) are inside.  0 <= B < 2^31.  Float arrays and the workspace 16-B aligned (stats 4 B), integer arrays 8 B.
+ * Errors, before anything is launched and with no byte changed: TBE_ERR_INVALID_ARGUMENT for an unsupported (L, E), B or N
+ *   < 0, p outside [0, 1), eps not finite or < 0, a `want` outside [0, 7], a null or misaligned pointer, a short workspace.
+ *   B == 0 launches nothing in the forward; the backward then only zeroes the wanted planes of grad_params. */
+int tbe_history_supported(int64_t L, int64_t E);
+/* examples/bert4rec/models/bert4rec.py:380-409 */
+int tbe_history_forward_f32(const uint64_t* feat_weights, const int64_t* feat_rows, const int64_t* feat_window,
+                            const int64_t* ids, int64_t N, const int64_t* offsets, int64_t B, int32_t L, int32_t E,
+                            const float* positional, const float* gamma, const float* beta, float eps, float p, uint32_t site,
+                            uint64_t seed, int64_t call, float* y, float* stats, int32_t* bounds_errors, void* stream);
+size_t tbe_history_backward_workspace_bytes(int64_t B, int32_t L, int32_t E, int32_t want);
+/* the backward autograd builds for examples/bert4rec/models/bert4rec.py:380-409 */
+int tbe_history_backward_f32(const float* grad_y, const uint64_t* feat_weights, const int64_t* feat_rows,
+                             const int64_t* feat_window, const int64_t* ids, int64_t N, const int64_t* offsets, int64_t B,
+                             int32_t L, int32_t E, const float* positional, const float* gamma, const float* stats, float p,
+                             uint32_t site, uint64_t seed, int64_t call, float* grad_emb, float* grad_params, int32_t want,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* JaggedTensor.to_padded_dense (torchrec/sparse/jagged_tensor.py:344-363) in one launch: out [B, N] float32 from the bags
  * values[offsets[b] .. offsets[b + 1]).  A bag of at most N values is padded with padding_value: in front of the values
  * (right-aligned values) with pad_from_beginning, behind them otherwise.  A longer bag keeps its LAST N values with

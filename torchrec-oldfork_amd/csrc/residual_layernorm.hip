@@ -15,13 +15,12 @@
 // Each product and add is rounded on its own (-ffp-contract=off).  Threads per row and rows per workgroup by N are those of
 // swish_layernorm.hip (16 | 64 | 256 threads, 128 | 32 | 16 rows); every sum runs in an order fixed by (R, N).
 //
-// The draw (include/tbe_hip.h): c = call_hash(seed, call) as the attention kernel, c2 = fmix32(c ^ 0x52dce729) so that no draw
-// coincides with the attention's, then one word per site (host), one per row (once per row and dropout) and one fmix32 per
-// element.
+// The draw (include/tbe_hip.h) is rln_draw.hpp's.
 #include <cmath>
 
 #include "rowreg.hpp"
-#include "tbe_backward_impl.hpp"  // fmix32, call_hash
+
+#include "rln_draw.hpp"
 
 namespace tbe {
 
@@ -29,37 +28,6 @@ __host__ __device__ constexpr int rln_rows_per_block(int tpr) { return tpr == 16
 static int rln_tpr(int N) { return N <= 16 * 4 ? 16 : N <= 64 * kRowSlots * 4 ? 64 : 256; }
 template <int TPR>
 using RlnTile = RowTile<TPR, rln_rows_per_block(TPR)>;
-
-constexpr uint32_t kRlnDomain = 0x52dce729u;
-
-// One dropout of a launch: kept iff draw >= thr, kept elements times scale; `on` = p > 0.
-struct RlnDrop {
-  uint32_t w1, thr;
-  float scale;
-  int32_t on;
-};
-
-static RlnDrop rln_drop(uint64_t seed, int64_t call, float p, uint32_t site) {
-  RlnDrop d;
-  d.on = p > 0.f;
-  d.w1 = fmix32(fmix32(call_hash(seed, call) ^ kRlnDomain) ^ (site * 0x9e3779b1u));
-  const double thr = std::floor(static_cast<double>(p) * 4294967296.0);
-  d.thr = thr >= 4294967295.0 ? 4294967295u : static_cast<uint32_t>(thr);
-  d.scale = 1.f / (1.f - p);
-  return d;
-}
-
-__device__ __forceinline__ uint32_t rln_row_word(const RlnDrop& d, uint32_t row) { return fmix32(d.w1 ^ (row * 0x85ebca6bu)); }
-
-__device__ __forceinline__ float rln_keep1(float v, uint32_t w2, const RlnDrop& d, uint32_t col) {
-  return fmix32(w2 ^ (col * 0xc2b2ae35u)) >= d.thr ? v * d.scale : 0.f;
-}
-
-// the four elements of the row word w2 that start at column `col`
-__device__ __forceinline__ float4 rln_keep4(const float4 v, uint32_t w2, const RlnDrop& d, uint32_t col) {
-  return make_float4(rln_keep1(v.x, w2, d, col), rln_keep1(v.y, w2, d, col + 1), rln_keep1(v.z, w2, d, col + 2),
-                     rln_keep1(v.w, w2, d, col + 3));
-}
 
 // colsum.hpp and tbe_row.hpp both have an add4, ambiguous where both are seen
 __device__ __forceinline__ void rln_add4(float4& a, const float4 b) {
@@ -264,8 +232,6 @@ __global__ __launch_bounds__(256) void relu_dropout_bwd_kernel(const float* __re
 }
 
 // ---- host side
-static bool rln_p_ok(float p) { return p >= 0.f && p < 1.f; }  // false for NaN
-
 // The limits the row entries share; *tpr = threads per row, *nrb = row blocks (grid size).
 static int rln_limits(const char* name, int64_t R, int N, float p_in, float p_out, int* tpr, int64_t* nrb) {
   TBE_REQUIRE(N >= 4, "%s: R=%lld must be >= 0 and N=%d a positive multiple of 4", name, static_cast<long long>(R), N);

@@ -281,6 +281,16 @@ SIGNATURES = {
     "tbe_relu_dropout_forward_f32": (
         ctypes.c_int, [c_void_p, c_i64, c_float, c_u32, c_u64, c_i64, c_void_p, c_void_p]),
     "tbe_relu_dropout_backward_f32": (ctypes.c_int, [c_void_p, c_void_p, c_i64, c_float, c_void_p, c_void_p]),
+    "tbe_history_supported": (ctypes.c_int, [c_i64, c_i64]),
+    "tbe_history_forward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_float,
+         c_float, c_u32, c_u64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tbe_history_backward_workspace_bytes": (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    "tbe_history_backward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p, c_void_p,
+         c_float, c_u32, c_u64, c_i64, c_void_p, c_void_p, c_i32, c_void_p, c_size, c_void_p]),
     "tbe_cross_entropy_workspace_bytes": (c_size, [c_i64]),
     "tbe_cross_entropy_forward_f32": (
         ctypes.c_int,

@@ -731,6 +731,20 @@ class _TBEBase(nn.Module):
             raise ValueError("set_row_windows: one (first row, global rows) pair per feature")
         self._row_windows = (tuple(int(x) for x in first_rows), tuple(int(x) for x in global_rows))
 
+    def sequence_table(self):
+        """(feat_weights, feat_rows, feat_window) device arrays of a PoolingMode.NONE module for a consumer that fetches the
+        rows of its one feature itself (tbe_history_*), or None when the lookup is more than one float32 row copy per id
+        from device memory: several features, another element type or placement, a row cache, an unaligned table."""
+        if (self.pooling_mode != PoolingMode.NONE or self.F != 1 or self._cache is not None or self._fp16_tables()
+                or self.placement[self.feature_table_map[0]] != "dev" or self.current_device.type != "cuda"
+                or self.max_D % 4 != 0):
+            return None
+        w = self._flat_weights("dev")
+        if w.dtype != torch.float32 or (w.data_ptr() + 4 * self.weights_offsets[self.feature_table_map[0]]) % 16 != 0:
+            return None
+        lay = self._get_layout()
+        return lay.feat_weights, lay.feat_rows, lay.feat_window
+
     def _errors(self) -> torch.Tensor:
         if self._bounds_errors is None or self._bounds_errors.device != self.current_device:
             self._bounds_errors = torch.zeros(1, dtype=torch.int32, device=self.current_device)

@@ -672,3 +672,44 @@ def relu_dropout_backward(grad_h, h, p):
         check(_lib.load().tbe_relu_dropout_backward_f32(ptr(grad_h), ptr(h), h.numel(), p, ptr(g), stream_ptr(dev)),
               "tbe_relu_dropout_backward_f32")
     return g
+
+
+# ---- BERT4Rec's HistoryArch (csrc/history_arch.hip): plain functions for the same reason.  `table` = (feat_weights, feat_rows,
+# feat_window) of _TBEBase.sequence_table(); `drop` = (p, site, seed, call).
+
+def history_supported(L: int, E: int) -> bool:
+    """The kernel's (L, E) range: include/tbe_hip.h tbe_history_supported."""
+    return bool(_lib.load().tbe_history_supported(L, E))
+
+
+def history_forward(table, ids, offsets, positional, gamma, beta, eps, drop, bounds_errors=None):
+    """(y [B, L, E], stats [B, 2]) of tbe_history_forward_f32 for int64 ids [N] and offsets [B + 1]."""
+    dev = require_gpu(ids, offsets, positional, gamma, beta)
+    (L, E), B = positional.shape, offsets.numel() - 1
+    y = torch.empty((B, L, E), dtype=torch.float32, device=dev)
+    stats = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_history_forward_f32(
+            ptr(table[0]), ptr(table[1]), ptr(table[2]), ptr(ids), ids.numel(), ptr(offsets), B, L, E, ptr(positional),
+            ptr(gamma), ptr(beta), eps, *drop, ptr(y), ptr(stats), bounds_errors, stream_ptr(dev)), "tbe_history_forward_f32")
+    return y, stats
+
+
+def history_backward(grad_y, table, ids, offsets, positional, gamma, stats, drop, want):
+    """(grad_emb [N, E], grad_params [3, L, E] or None) of tbe_history_backward_f32; `want` = 1 (positional) | 2 (gamma) |
+    4 (beta): the other planes of grad_params are not written.  Reads the table: call it before the table's update."""
+    dev = require_gpu(grad_y, ids, offsets, positional, gamma, stats)
+    (L, E), B = positional.shape, offsets.numel() - 1
+    if grad_y.shape != (B, L, E) or grad_y.dtype != torch.float32 or not grad_y.is_contiguous():
+        raise RuntimeError("history_backward: grad_y must be a contiguous float32 [B, L, E]")
+    grad_emb = torch.empty((ids.numel(), E), dtype=torch.float32, device=dev)
+    gp = torch.empty((3, L, E), dtype=torch.float32, device=dev) if want else None
+    with torch.cuda.device(dev):
+        lib = _lib.load()
+        wbytes = lib.tbe_history_backward_workspace_bytes(B, L, E, want)
+        ws = workspace(wbytes, dev) if want else None
+        check(lib.tbe_history_backward_f32(
+            ptr(grad_y), ptr(table[0]), ptr(table[1]), ptr(table[2]), ptr(ids), ids.numel(), ptr(offsets), B, L, E,
+            ptr(positional), ptr(gamma), ptr(stats), *drop, ptr(grad_emb), ptr(gp), want, ptr(ws), wbytes, stream_ptr(dev)),
+            "tbe_history_backward_f32")
+    return grad_emb, gp

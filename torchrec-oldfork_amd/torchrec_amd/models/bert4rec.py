@@ -26,6 +26,17 @@ What runs differently:
     elementwise_affine=False, p >= 1, active dropout under stream capture.  Double backward of a kernel-path forward
     recomputes from differentiable torch operations with dropout inactive and raises RuntimeError with it active.
     SublayerConnection and PositionwiseFeedForward called on their own are the reference's expressions.
+  * HistoryArch, when the batch's keys are the collection's one feature, the item table is one float32 DEVICE table without
+    a row cache behind either TBE class, (history_len, emb_dim) is supported (emb_dim % 4 == 0, 4 <= emb_dim <= 2048,
+    history_len * emb_dim <= 32 768), `positional` and the affine LayerNorm are float32 on the device and p < 1: lookup, padding, positional add,
+    LayerNorm over [history_len, emb_dim] and dropout are one launch each way (csrc/history_arch.hip).  Autograd keeps the
+    ids, the offsets and two floats per sample; the backward hands the jagged [N, emb_dim] gradient to the table's own
+    backward (fused optimizer, or the dense gradient of `.weights`).  The dropout draws as the blocks' do, with site 4, the
+    high word 0 and a per-module call counter.  Everything else silently takes the torch expression: `kernel_path = False`,
+    FP16 tables, several features, CPU parameters, elementwise_affine=False, p >= 1, active dropout under stream capture.
+    Double backward of a kernel-path forward raises RuntimeError.  So does a backward that finds the fused table updated
+    since its forward (two forwards, then two backwards): it recomputes xhat from the live rows, and the saved statistics
+    no longer belong to them.  The torch expression keeps the embeddings and has no such limit.
   * BERT4Rec.forward builds the mask with .expand (stride 0 along the queries) where the reference uses .repeat, and
     HistoryArch adds `positional` by broadcasting.
   * HistoryArch and BERT4Rec take a keyword-only `fused_params` for the EmbeddingCollection (the fused ADAM of
@@ -407,6 +418,56 @@ class TransformerBlock(nn.Module):
         return x2.view(shape), None if n_next is None else n_next.view(shape)
 
 
+class _HistoryKernel(torch.autograd.Function):
+    """HistoryArch in one launch each way (csrc/history_arch.hip) behind either TBE class of the EmbeddingCollection.  `anchor`
+    is what the table's lookup hangs its backward on: the fused class's placeholder (the optimizer runs inside the
+    backward, no gradient comes back) or the dense class's `.weights` (its gradient is returned).  Kept for the backward:
+    the ids, the offsets and two floats per sample — no embeddings, no LayerNorm input, no mask."""
+
+    @staticmethod
+    def forward(ctx, anchor, positional, gamma, beta, tbe, ids, offsets, B, prepare, eps, drop):
+        from ..distributed._device_ops import history_forward
+
+        y, stats = history_forward(tbe.sequence_table(), ids, offsets, positional, gamma, beta, eps, drop, tbe._errors_ptr())
+        ctx.save_for_backward(ids, offsets, stats, positional, gamma)
+        ctx.tbe, ctx.B, ctx.drop = tbe, B, drop
+        ctx.iter = getattr(tbe, "iter", None)  # fused class: the updates its table has had
+        ctx.prepared = tbe._prepare_backward(ids, offsets, B) if prepare else None
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        from fbgemm_gpu.split_table_batched_embeddings_ops import _OPT_DENSE_GRAD, OptimizerArgs
+
+        from ..distributed._device_ops import history_backward
+
+        if torch.is_grad_enabled():
+            raise RuntimeError("HistoryArch: double backward through the fused kernel is not supported "
+                               "(kernel_path = False gives the torch expression)")
+        ids, offsets, stats, positional, gamma = ctx.saved_tensors
+        tbe, need = ctx.tbe, ctx.needs_input_grad
+        if getattr(tbe, "iter", None) != ctx.iter:
+            raise RuntimeError("HistoryArch: the item table has been updated since this forward (another backward of the fused "
+                               "table ran in between), and the kernel's backward recomputes from the live rows: run one "
+                               "forward per backward, or set kernel_path = False")
+        want = (1 if need[1] else 0) | (2 if need[2] else 0) | (4 if need[3] else 0)
+        # before the table's update: it reads the rows the update rewrites (same stream)
+        grad_emb, gp = history_backward(g_y.contiguous(), tbe.sequence_table(), ids, offsets, positional, gamma, stats,
+                                        ctx.drop, want)
+        grad_w = None
+        if hasattr(tbe, "placeholder_autograd_tensor"):  # as _FusedLookup.backward
+            tbe.iter += 1
+            tbe._backward_impl(grad_emb, ids, offsets, None, ctx.B, tbe._optimizer_struct(), prepared=ctx.prepared,
+                               ext=tbe._optimizer_ext())
+        elif need[0]:  # as _DenseLookup.backward
+            grad_w = torch.zeros_like(tbe.weights)
+            tbe._backward_impl(grad_emb, ids, offsets, None, ctx.B, OptimizerArgs(_OPT_DENSE_GRAD, 0.0, 0.0, 0.0, 0.0, 0.0, 1),
+                               state0_override=tbe._dense_grad_ptrs(grad_w), state0_aligned=grad_w.data_ptr() % 16 == 0)
+        ctx.prepared = None
+        return (grad_w, gp[0] if need[1] else None, gp[1] if need[2] else None, gp[2] if need[3] else None,
+                None, None, None, None, None, None, None)
+
+
 class HistoryArch(torch.nn.Module):
     """The input embedding layer of BERT4Rec (examples/bert4rec/models/bert4rec.py:323-409): an item embedding table of
     vocab_size vectors through EmbeddingCollection, padded / truncated to history_len rows by jagged_2d_to_dense, plus a
@@ -433,8 +494,34 @@ class HistoryArch(torch.nn.Module):
             name="item_embedding", embedding_dim=emb_dim, num_embeddings=vocab_size, feature_names=["item"],
             weight_init_max=1.0, weight_init_min=-1.0)
         self.ec = EmbeddingCollection(tables=[item_embedding_config], device=device, fused_params=fused_params)
+        self.kernel_path = True     # False: always the torch expression (tests and tools compare the two)
+        self.last_path = None       # "kernel" / "torch": what the last forward took
+        # the kernel dropout's `call`, as in TransformerBlock: the high word stays 0 (the blocks of a BERT4Rec use 1 + layer)
+        self._dropout_salt = 0
+        self._dropout_calls = 0
 
-    def forward(self, id_list_features: KeyedJaggedTensor) -> torch.Tensor:
+    def _kernel_inputs(self, features: KeyedJaggedTensor, p: float):
+        """(tbe, table) when this call may take the kernel, else None."""
+        tbe, ln, pos = self.ec._tbe, self.layernorm, self.positional
+        if not (self.kernel_path and list(features.keys()) == list(self.ec._feature_names) and len(self.ec._feature_names) == 1
+                and pos.is_cuda and pos.dtype == torch.float32 and pos.is_contiguous() and pos.data_ptr() % 16 == 0
+                and tuple(pos.shape) == (self.history_len, self.emb_dim) and 0.0 <= p < 1.0):
+            return None
+        if not (isinstance(ln, nn.LayerNorm) and ln.elementwise_affine and ln.bias is not None
+                and tuple(ln.normalized_shape) == tuple(pos.shape)
+                and all(t.device == pos.device and t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0
+                        for t in (ln.weight, ln.bias))):
+            return None
+        if tbe.current_device != pos.device or (p > 0.0 and torch.cuda.is_current_stream_capturing()):
+            return None  # the call counter is host state
+        from ..distributed._device_ops import history_supported
+
+        if not history_supported(self.history_len, self.emb_dim):
+            return None
+        table = tbe.sequence_table()
+        return None if table is None else (tbe, table)
+
+    def _forward_torch(self, id_list_features: KeyedJaggedTensor) -> torch.Tensor:
         jt_dict = self.ec(id_list_features)
         padded_embeddings = [
             torch.ops.fbgemm.jagged_2d_to_dense(
@@ -445,6 +532,40 @@ class HistoryArch(torch.nn.Module):
         item_output = padded_embeddings[0] if len(padded_embeddings) == 1 else torch.cat(padded_embeddings, dim=1)
         x = item_output + self.positional  # broadcast over the batch (the reference repeats it)
         return self.dropout(self.layernorm(x))
+
+    def forward(self, id_list_features: KeyedJaggedTensor) -> torch.Tensor:
+        p = float(self.dropout.p) if self.training else 0.0
+        found = self._kernel_inputs(id_list_features, p)
+        if found is None:
+            self.last_path = "torch"
+            return self._forward_torch(id_list_features)
+        self.last_path = "kernel"
+        tbe, table = found
+        fused = hasattr(tbe, "placeholder_autograd_tensor")
+        # what the lookup starts with on the plain path: the input checks and, for the fused class, whether the backward's
+        # sort goes on the side stream
+        if fused:
+            ids, offsets, _, B, prepare = tbe._begin_lookup(id_list_features.values(), id_list_features.offsets(), None,
+                                                            torch.is_grad_enabled())
+        else:
+            ids, offsets, _, B = tbe._check_inputs(id_list_features.values(), id_list_features.offsets(), None)
+            prepare = False
+        seed = call = 0
+        if p > 0.0:
+            seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
+            call = (self._dropout_salt << 32) | (self._dropout_calls & 0xFFFFFFFF)
+            self._dropout_calls += 1
+        drop, ln = (p, 4, seed, call), self.layernorm
+        anchor = tbe.placeholder_autograd_tensor if fused else tbe.weights
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (anchor, self.positional, ln.weight, ln.bias)):
+            y = _HistoryKernel.apply(anchor, self.positional, ln.weight, ln.bias, tbe, ids, offsets, B, prepare, ln.eps, drop)
+        else:
+            from ..distributed._device_ops import history_forward
+
+            y = history_forward(table, ids, offsets, self.positional, ln.weight, ln.bias, ln.eps, drop, tbe._errors_ptr())[0]
+        if fused:
+            tbe._enforce_bounds_check_mode()
+        return y
 
 
 class BERT4Rec(nn.Module):
