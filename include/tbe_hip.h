@@ -1047,6 +1047,37 @@ int tbe_attention_backward_f32(const float* grad_out,
                                const uint8_t* key_valid, const float* lse, int64_t B, int32_t H, int32_t L, int32_t d,
                                float p, uint64_t seed, int64_t call, float* dq, float* dk, float* dv, void* stream);
 
+/* The same attention for the (L, d) the entries above cannot hold in LDS: keys stream through LDS in blocks of 32, a workgroup
+ * owns 64 rows of one (b, h), the weighted sums run on MFMA as the dot products do (csrc/attention_tiled.hip).
+ * Semantics: those of tbe_attention_forward_f32 / _backward_f32 above, word for word — scores, the finite -1e9, the softmax
+ *   with its maximum subtracted, the dropout draw of element (b, h, i, j) and its scale, lse, dS = 0 at masked keys, the
+ *   sample with no valid key (uniform 1 / L; the backward counts the sample's valid keys and takes P = 1 / L), p == 0.  The
+ *   results differ from the resident entries' in rounding only: the forward normalises once at the end,
+ *   O = (sum_j keep scale exp(S_ij - m_i) V_j) / l_i, where the resident kernel divides every weight.
+ * Layout: q, k, v, key_valid, out, lse, grad_out, dq, dk, dv as above.  The backward also reads the forward's `out`
+ *   (contiguous [B, L, H * d]) for D_i = dO_i . O_i and needs a workspace D_ws of B * H * L floats (4-B aligned), which it
+ *   writes whenever it launches, also when dq is NULL; its content before the call does not matter.
+ * Launches on `stream`: forward one; backward two (rows owned by queries: D and dQ; rows owned by keys: dK and dV), the
+ *   second skipped when dk and dv are both NULL, none when all three are.  A skipped gradient changes no bit of the others.
+ * Determinism: no atomics, every sum in an order fixed by (L, d); two runs are bit-identical.
+ * Supported (tbe_attention_tiled_supported returns 1): d % 4 == 0, 4 <= d <= 128, 1 <= L <= 4096 — the resident entries'
+ *   shapes included.  At most 52 KiB of LDS per workgroup.
+ * Errors, before anything is launched and with no byte changed: those of the resident entries, and a null `out` or D_ws, and
+ *   B * H * ceil(L / 64) beyond 2^31 - 1.  B == 0 launches nothing: TBE_OK. */
+int tbe_attention_tiled_supported(int64_t L, int64_t d);
+int tbe_attention_tiled_forward_f32(const float* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                    const float* k, int64_t k_batch_stride, int64_t k_row_stride,
+                                    const float* v, int64_t v_batch_stride, int64_t v_row_stride,
+                                    const uint8_t* key_valid, int64_t B, int32_t H, int32_t L, int32_t d,
+                                    float p, uint64_t seed, int64_t call, float* out, float* lse, void* stream);
+int tbe_attention_tiled_backward_f32(const float* grad_out, const float* out,
+                                     const float* q, int64_t q_batch_stride, int64_t q_row_stride,
+                                     const float* k, int64_t k_batch_stride, int64_t k_row_stride,
+                                     const float* v, int64_t v_batch_stride, int64_t v_row_stride,
+                                     const uint8_t* key_valid, const float* lse, int64_t B, int32_t H, int32_t L, int32_t d,
+                                     float p, uint64_t seed, int64_t call, float* D_ws, float* dq, float* dk, float* dv,
+                                     void* stream);
+
 /* The passes of BERT4Rec's TransformerBlock around its GEMMs and its attention (examples/bert4rec/models/bert4rec.py:174-320:
  * SublayerConnection  x + dropout(sublayer(norm(x))),  the feed-forward's dropout(relu(.)),  the block's final dropout),
  * float32: the residual add, its dropouts and the LayerNorm of the NEXT sublayer in one launch with the row in registers.

@@ -13,7 +13,11 @@ alone, without the four projections: the two kernels, and `_attention_torch` for
 JaggedTensor.to_padded_dense is timed at B = 128 and 1024 (histories of 0 .. 150 ids, desired_length 100) against the
 reference's loop (torchrec/sparse/jagged_tensor.py:344-363), restated here.  A record: nothing is asserted.
 
-Usage: python tools/attnbench.py [--rounds 20] [--warmup 5] [--out profiles/bert4rec_attnbench.json]"""
+--tiled measures the tiled kernels (csrc/attention_tiled.hip) by the same rule and method: at (128, 200, 256, 2),
+(1024, 200, 256, 2), (128, 512, 128, 2) against the torch path, which is what those shapes took before, and at the three shapes
+above against the resident kernels through `prefer_tiled` (the row's "against" names the other path).
+
+Usage: python tools/attnbench.py [--rounds 20] [--warmup 5] [--tiled] [--out profiles/bert4rec_attnbench.json]"""
 import argparse
 import json
 import os
@@ -24,6 +28,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "torchrec-oldfork_amd"))
 
 SHAPES = [(128, 100, 256, 2), (128, 200, 128, 2), (1024, 100, 256, 2)]
+# --tiled: shapes only the tiled kernels (csrc/attention_tiled.hip) serve, against the torch path the parent took there; then
+# SHAPES again, the tiled kernels (prefer_tiled) against the resident ones
+TILED_SHAPES = [(128, 200, 256, 2), (1024, 200, 256, 2), (128, 512, 128, 2)]
 
 
 def _event_us(fn):
@@ -85,12 +92,15 @@ def reference_to_padded_dense(values, lengths, desired_length, padding_value=0.0
     return torch.stack(rows)
 
 
-def bench_attention(B, L, dim, H, dropout, rounds, warmup, dev):
+def bench_attention(B, L, dim, H, dropout, rounds, warmup, dev, tiled_against=None):
+    """tiled_against: None — the module's default kernel against the torch path; "torch" / "resident" — the tiled kernels
+    (`prefer_tiled`) as "kernel" against that path, which the row's keys then name."""
     import torch
 
-    from torchrec_amd.distributed._device_ops import attention_backward, attention_forward
+    from torchrec_amd.distributed import _device_ops as ops
     from torchrec_amd.models import bert4rec
 
+    other = tiled_against or "torch"
     torch.manual_seed(B + L + dim)
     m = bert4rec.MultiHeadedAttention(num_heads=H, dim_model=dim, dropout=dropout, device=dev).train(dropout > 0)
     x = torch.randn(B, L, dim, device=dev).requires_grad_()
@@ -101,15 +111,19 @@ def bench_attention(B, L, dim, H, dropout, rounds, warmup, dev):
     params = list(m.parameters())
 
     def step(kernel):
-        m.kernel_path = kernel
+        m.kernel_path = kernel or other == "resident"
+        m.prefer_tiled = kernel and tiled_against is not None
         x.grad = None
         for p in params:
             p.grad = None
         m(x, x, x, mask=mask).backward(g)
-        assert m.last_path == ("kernel" if kernel else "torch")
+        assert m.last_path == ("kernel" if m.kernel_path else "torch")
+        assert tiled_against is None or m.last_kernel == ("tiled" if kernel else None if other == "torch" else "resident")
         return [x.grad] + [p.grad for p in params]
 
     row = {"B": B, "L": L, "emb_dim": dim, "nhead": H, "dropout": dropout, "rounds": rounds}
+    if tiled_against is not None:
+        row["kernel"], row["against"] = "tiled", other
     if dropout == 0:
         got, want = step(True), step(False)
         # the key projection's bias has an exactly zero gradient (both paths leave rounding residue there): every tensor
@@ -119,23 +133,32 @@ def bench_attention(B, L, dim, H, dropout, rounds, warmup, dev):
         if not row["grad_rel_diff_max"] < 1e-3:
             raise SystemExit(f"attnbench: at {(B, L, dim, H)} kernel path and torch path differ: {row['grad_rel_diff_max']}")
         del got, want
-    ts = _alternate({"kernel": lambda: step(True), "torch": lambda: step(False)}, rounds, warmup)
+    ts = _alternate({"kernel": lambda: step(True), other: lambda: step(False)}, rounds, warmup)
     spread = max(max(t) - min(t) for t in ts.values())
-    med_k, med_t = statistics.median(ts["kernel"]), statistics.median(ts["torch"])
+    med_k, med_t = statistics.median(ts["kernel"]), statistics.median(ts[other])
     row.update(_stats("kernel", ts["kernel"]))
-    row.update(_stats("torch", ts["torch"]))
-    row.update({"spread_us": round(spread, 1), "torch_over_kernel": round(med_t / med_k, 3),
+    row.update(_stats(other, ts[other]))
+    row.update({"spread_us": round(spread, 1), f"{other}_over_kernel": round(med_t / med_k, 3),
                 "kernel_not_slower": bool(med_k <= med_t + spread)})
     x.grad = None
     row["kernel_peak_MiB"] = round(_peak_bytes(lambda: step(True)) / 2**20, 1)
     x.grad = None
-    row["torch_peak_MiB"] = round(_peak_bytes(lambda: step(False)) / 2**20, 1)
+    row[f"{other}_peak_MiB"] = round(_peak_bytes(lambda: step(False)) / 2**20, 1)
     row["one_score_tensor_MiB"] = round(B * H * L * L * 4 / 2**20, 1)
     # the attention alone, on the projections
     with torch.no_grad():
         q, k, v = (layer(x) for layer in m.linear_layers)
     kv = valid.to(torch.uint8).contiguous()
-    _, lse = attention_forward(q, k, v, kv, H, dropout, 1, 1)
+    fns = {}
+    if tiled_against is not None:
+        out, lse = ops.attention_tiled_forward(q, k, v, kv, H, dropout, 1, 1)
+        fns["fwd_kernel"] = lambda: ops.attention_tiled_forward(q, k, v, kv, H, dropout, 1, 1)
+        fns["bwd_kernel"] = lambda: ops.attention_tiled_backward(g, out, q, k, v, kv, lse, H, dropout, 1, 1)
+    if tiled_against != "torch":
+        pre = "resident_" if tiled_against else ""
+        _, lse_r = ops.attention_forward(q, k, v, kv, H, dropout, 1, 1)
+        fns[pre + "fwd_kernel"] = lambda: ops.attention_forward(q, k, v, kv, H, dropout, 1, 1)
+        fns[pre + "bwd_kernel"] = lambda: ops.attention_backward(g, q, k, v, kv, lse_r, H, dropout, 1, 1)
     leaves = [t.clone().requires_grad_() for t in (q, k, v)]
     drop = m.dropout if dropout > 0 else None
 
@@ -144,9 +167,9 @@ def bench_attention(B, L, dim, H, dropout, rounds, warmup, dev):
             t.grad = None
         bert4rec._attention_torch(*leaves, mask, H, drop).backward(g)
 
-    alone = _alternate({"fwd_kernel": lambda: attention_forward(q, k, v, kv, H, dropout, 1, 1),
-                        "bwd_kernel": lambda: attention_backward(g, q, k, v, kv, lse, H, dropout, 1, 1),
-                        "torch_fwd_bwd": torch_alone}, rounds, warmup)
+    if tiled_against != "resident":
+        fns["torch_fwd_bwd"] = torch_alone
+    alone = _alternate(fns, rounds, warmup)
     row["attention_alone"] = {n: _stats(n, t) for n, t in alone.items()}
     flops = 4.0 * B * H * L * L * (dim // H)  # forward: S and P V
     row["attention_alone"]["fwd_kernel_TFLOPs"] = round(flops / statistics.median(alone["fwd_kernel"]) / 1e6, 2)
@@ -187,6 +210,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--tiled", action="store_true", help="measure the tiled kernels instead: against torch on TILED_SHAPES, "
+                    "against the resident kernels on SHAPES")
     args = ap.parse_args()
     import torch
 
@@ -194,12 +219,15 @@ def main():
         raise SystemExit("attnbench: no GPU (a timing taken anywhere else says nothing)")
     dev = torch.device("cuda", 0)
     results, padded = [], []
-    for B, L, dim, H in SHAPES:
+    plan = [(s, None) for s in SHAPES]
+    if args.tiled:
+        plan = [(s, "torch") for s in TILED_SHAPES] + [(s, "resident") for s in SHAPES]
+    for (B, L, dim, H), against in plan:
         for dropout in (0.0, 0.1):
-            results.append(bench_attention(B, L, dim, H, dropout, args.rounds, args.warmup, dev))
+            results.append(bench_attention(B, L, dim, H, dropout, args.rounds, args.warmup, dev, against))
             print(json.dumps(results[-1]), flush=True)
             torch.cuda.empty_cache()
-    for B in (128, 1024):
+    for B in (() if args.tiled else (128, 1024)):
         padded.append(bench_to_padded_dense(B, args.rounds, args.warmup, dev))
         print(json.dumps(padded[-1]), flush=True)
     doc = {"tool": "tools/attnbench.py", "device": torch.cuda.get_device_name(0),

@@ -33,24 +33,18 @@
 //
 // MFMA for the dot products, vector FMA for the weighted sums: DESIGN.md (BERT4Rec) has the measurement behind the choice.
 #include <atomic>
-#include <cmath>
 
-#include "common.hpp"
-#include "tbe_backward_impl.hpp"  // fmix32, call_hash
+#include "attention_common.hpp"  // AttnArgs, attn_check, the tile vocabulary, the dropout draw
 
 namespace tbe {
 
 constexpr int kAttnThreads = 512;
 constexpr int kAttnWaves = kAttnThreads / kWave;
-constexpr int kAttnTile = 16;         // rows a wave owns at a time, and staged rows per MFMA tile
 constexpr int kAttnRows = 2;          // owned rows per weighted sum (they share every LDS read of the staged matrix)
 constexpr int kAttnMaxKeys = 4;       // L <= 64 * kAttnMaxKeys (the kernels' template parameter T counts 64 staged rows)
-using attn_f4 = float __attribute__((ext_vector_type(4)));  // one MFMA accumulator
 constexpr int kAttnMaxL = kWave * kAttnMaxKeys;
-constexpr int kAttnMaxD = 128;
 constexpr size_t kAttnLdsBudget = 160 * 1024;  // the CU's LDS
 
-__host__ __device__ constexpr int attn_ds(int d) { return d + 4; }
 __host__ __device__ constexpr int attn_lp(int L) { return (L + 3) & ~3; }
 // floats: two staged matrices, D [Lp], and per wave and owned row two weight buffers [Lp]
 static size_t attn_lds_bytes(int L, int d) {
@@ -61,41 +55,6 @@ static bool attn_supported(int64_t L, int64_t d) {
   return L >= 1 && L <= kAttnMaxL && d >= 4 && d <= kAttnMaxD && d % 4 == 0 &&
          attn_lds_bytes(static_cast<int>(L), static_cast<int>(d)) <= kAttnLdsBudget;
 }
-
-struct AttnArgs {
-  const float *q, *k, *v;            // element (b, l, h, c) at base + b * bs + l * rs + h * d + c
-  int64_t q_bs, q_rs, k_bs, k_rs, v_bs, v_rs;
-  const uint8_t* key_valid;          // [B, L] or null
-  const float* dout;                 // backward: [B, L, H * d]
-  float* lse;                        // [B, H, L]: written by the forward, read by the backward
-  float *out, *dq, *dk, *dv;         // [B, L, H * d]; forward: out; backward: dq / dk / dv, each may be null (not wanted)
-  int32_t H, L, d;
-  uint32_t callh, drop_thr;          // call_hash(seed, call); keep iff draw >= drop_thr
-  float drop_scale;                  // 1 / (1 - p)
-};
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// over the 16 lanes that share a row
-__device__ __forceinline__ float row_max(float v) {
-#pragma unroll
-  for (int o = kAttnTile / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
-}
-__device__ __forceinline__ float row_sum(float v) {
-#pragma unroll
-  for (int o = kAttnTile / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-// The dropout draw of element (b, h, i, j): three words, each the murmur3 finalizer of the one before xor an index times an
-// odd constant (include/tbe_hip.h states it for the tests).
-__device__ __forceinline__ uint32_t attn_word_bh(uint32_t callh, uint32_t bh) { return fmix32(callh ^ (bh * 0x9e3779b1u)); }
-__device__ __forceinline__ uint32_t attn_word_i(uint32_t wbh, uint32_t i) { return fmix32(wbh ^ (i * 0x85ebca6bu)); }
-__device__ __forceinline__ uint32_t attn_draw(uint32_t wi, uint32_t j) { return fmix32(wi ^ (j * 0xc2b2ae35u)); }
 
 // dst[r * ds + c] = src[r * rs + c] for r < L, c < d, by the whole workgroup
 __device__ __forceinline__ void attn_stage(float* dst, const float* __restrict__ src, int64_t rs, int L, int d) {
@@ -451,32 +410,6 @@ __global__ __launch_bounds__(kAttnThreads) void attention_bwd_kernel(const AttnA
   }
 }
 
-// The checks both entries share; fills the sizes and the dropout words of `a`.
-static int attn_check(const char* name, AttnArgs& a, int64_t B, int32_t H, int32_t L, int32_t d, float p, uint64_t seed,
-                      int64_t call) {
-  TBE_REQUIRE(B >= 0 && H >= 1 && L >= 1 && d >= 1, "%s: bad sizes B=%lld H=%d L=%d d=%d", name, static_cast<long long>(B), H,
-              L, d);
-  TBE_REQUIRE(attn_supported(L, d), "%s: (L, d) = (%d, %d) is not supported (tbe_attention_supported)", name, L, d);
-  TBE_REQUIRE(B * H <= INT32_MAX, "%s: B * H = %lld workgroups exceed the grid", name, static_cast<long long>(B * H));
-  TBE_REQUIRE(p >= 0.f && p < 1.f, "%s: dropout p=%g outside [0, 1)", name, static_cast<double>(p));
-  const int64_t row = static_cast<int64_t>(H) * d;
-  const int64_t strides[3][2] = {{a.q_bs, a.q_rs}, {a.k_bs, a.k_rs}, {a.v_bs, a.v_rs}};
-  for (const auto& s : strides) {
-    TBE_REQUIRE(s[1] >= row && s[1] % 4 == 0, "%s: row stride %lld below the row of %lld floats, or no multiple of 4", name,
-                static_cast<long long>(s[1]), static_cast<long long>(row));
-    TBE_REQUIRE(s[0] >= (L - 1) * s[1] + row && s[0] % 4 == 0,
-                "%s: batch stride %lld below the sample's extent, or no multiple of 4", name, static_cast<long long>(s[0]));
-  }
-  a.H = H;
-  a.L = L;
-  a.d = d;
-  a.callh = call_hash(seed, call);
-  const double thr = std::floor(static_cast<double>(p) * 4294967296.0);
-  a.drop_thr = thr >= 4294967295.0 ? 4294967295u : static_cast<uint32_t>(thr);
-  a.drop_scale = 1.f / (1.f - p);
-  return TBE_OK;
-}
-
 // An LDS image above 64 KiB has to be allowed per kernel; once per device and process, for all eight kernels, at the first
 // call (so a later call inside a stream capture sets nothing).
 static int attn_allow_lds(const char* name) {
@@ -561,7 +494,7 @@ extern "C" int tbe_attention_forward_f32(const float* q, int64_t q_batch_stride,
   a.q = q, a.k = k, a.v = v, a.key_valid = key_valid, a.out = out, a.lse = lse;
   a.q_bs = q_batch_stride, a.q_rs = q_row_stride, a.k_bs = k_batch_stride, a.k_rs = k_row_stride;
   a.v_bs = v_batch_stride, a.v_rs = v_row_stride;
-  int rc = attn_check(name, a, B, H, L, d, p, seed, call);
+  int rc = attn_check(name, a, B, H, L, d, p, seed, call, attn_supported(L, d), "tbe_attention_supported");
   if (rc != TBE_OK) return rc;
   rc = check_pointers(name, {q, k, v, out}, {lse});
   if (rc != TBE_OK) return rc;
@@ -586,7 +519,7 @@ extern "C" int tbe_attention_backward_f32(const float* grad_out, const float* q,
   a.dq = dq, a.dk = dk, a.dv = dv;
   a.q_bs = q_batch_stride, a.q_rs = q_row_stride, a.k_bs = k_batch_stride, a.k_rs = k_row_stride;
   a.v_bs = v_batch_stride, a.v_rs = v_row_stride;
-  int rc = attn_check(name, a, B, H, L, d, p, seed, call);
+  int rc = attn_check(name, a, B, H, L, d, p, seed, call, attn_supported(L, d), "tbe_attention_supported");
   if (rc != TBE_OK) return rc;
   rc = check_pointers(name, {q, k, v, grad_out}, {lse});
   if (rc != TBE_OK) return rc;

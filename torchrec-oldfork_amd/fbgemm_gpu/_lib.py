@@ -269,6 +269,15 @@ SIGNATURES = {
         ctypes.c_int,
         [c_void_p] + [c_void_p, c_i64, c_i64] * 3 + [c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_float, c_u64, c_i64,
                                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tbe_attention_tiled_supported": (ctypes.c_int, [c_i64, c_i64]),
+    "tbe_attention_tiled_forward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_i64, c_i64] * 3 + [c_void_p, c_i64, c_i32, c_i32, c_i32, c_float, c_u64, c_i64, c_void_p, c_void_p,
+                                        c_void_p]),
+    "tbe_attention_tiled_backward_f32": (
+        ctypes.c_int,
+        [c_void_p, c_void_p] + [c_void_p, c_i64, c_i64] * 3 + [c_void_p, c_void_p, c_i64, c_i32, c_i32, c_i32, c_float, c_u64,
+                                                               c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tbe_residual_layernorm_backward_workspace_bytes": (c_size, [c_i64, c_i32]),
     "tbe_residual_layernorm_forward_f32": (
         ctypes.c_int,

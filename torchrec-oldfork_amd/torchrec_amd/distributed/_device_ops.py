@@ -607,6 +607,50 @@ def attention_backward(grad_out, q, k, v, key_valid, lse, H, p=0.0, seed=0, call
     return tuple(grads)
 
 
+def attention_tiled_supported(L: int, d: int) -> bool:
+    """The tiled kernels' (L, d_k) range: include/tbe_hip.h tbe_attention_tiled_supported."""
+    return bool(_lib.load().tbe_attention_tiled_supported(L, d))
+
+
+def attention_tiled_forward(q, k, v, key_valid, H, p=0.0, seed=0, call=0):
+    """attention_forward through tbe_attention_tiled_forward_f32 (csrc/attention_tiled.hip): the same arguments and results."""
+    dev = require_gpu(q, k, v, key_valid)
+    B, L, HD = q.shape
+    if k.shape != q.shape or v.shape != q.shape:
+        raise RuntimeError(f"attention_tiled_forward: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} differ")
+    strides = [s for t in (q, k, v) for s in _attention_strides("attention_tiled_forward", t, H)]
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or key_valid.shape != (B, L) or not key_valid.is_contiguous()):
+        raise RuntimeError("attention_tiled_forward: key_valid must be a contiguous uint8 [B, L]")
+    out = torch.empty((B, L, HD), dtype=torch.float32, device=dev)
+    lse = torch.empty((B, H, L), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_attention_tiled_forward_f32(
+            ptr(q), strides[0], strides[1], ptr(k), strides[2], strides[3], ptr(v), strides[4], strides[5], ptr(key_valid),
+            B, H, L, HD // H, p, seed, call, ptr(out), ptr(lse), stream_ptr(dev)), "tbe_attention_tiled_forward_f32")
+    return out, lse
+
+
+def attention_tiled_backward(grad_out, out, q, k, v, key_valid, lse, H, p=0.0, seed=0, call=0, need=(True, True, True)):
+    """attention_backward through tbe_attention_tiled_backward_f32: it also takes the forward's `out`, and allocates the
+    [B, H, L] workspace of D_i = dO_i . O_i that the first launch writes and the second reads."""
+    dev = require_gpu(grad_out, out, q, k, v, lse, key_valid)
+    B, L, HD = q.shape
+    strides = [s for t in (q, k, v) for s in _attention_strides("attention_tiled_backward", t, H)]
+    for name, t in (("grad_out", grad_out), ("out", out)):
+        if t.shape != q.shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"attention_tiled_backward: {name} must be a contiguous float32 [B, L, H * d]")
+    if lse.shape != (B, H, L) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise RuntimeError("attention_tiled_backward: lse must be the forward's [B, H, L]")
+    grads = [torch.empty((B, L, HD), dtype=torch.float32, device=dev) if w else None for w in need]
+    ws = torch.empty((B, H, L), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().tbe_attention_tiled_backward_f32(
+            ptr(grad_out), ptr(out), ptr(q), strides[0], strides[1], ptr(k), strides[2], strides[3], ptr(v), strides[4],
+            strides[5], ptr(key_valid), ptr(lse), B, H, L, HD // H, p, seed, call, ptr(ws), ptr(grads[0]), ptr(grads[1]),
+            ptr(grads[2]), stream_ptr(dev)), "tbe_attention_tiled_backward_f32")
+    return tuple(grads)
+
+
 # ---- BERT4Rec's residual / dropout / LayerNorm passes (csrc/residual_layernorm.hip): plain functions for the same reason —
 # optional inputs and outputs chosen per call.  `drop` = (p_in, site_in, p_out, site_out, seed, call).
 

@@ -7,7 +7,10 @@ What runs differently:
   * MultiHeadedAttention, on a HIP device with float32 inputs, a supported (L, d_k) and no mask or a key-padding mask:
     the three projections stay torch's nn.Linear, their outputs go to one fused kernel each way (csrc/attention.hip) where
     they are, and its [B, L, H * d_k] result goes straight into output_linear.  No [B, H, L, L] tensor exists; autograd keeps
-    the three projections and one float per row.  Everything else silently takes `_attention_torch`, the reference's
+    the three projections and one float per row.  An (L, d_k) the LDS-resident kernels cannot hold — (200, 128), every L
+    above 256 up to 4096 — takes the tiled kernels of csrc/attention_tiled.hip in the same way (`last_kernel` says which;
+    `prefer_tiled = True` sends every supported shape there); their backward also reads the result that output_linear keeps
+    for its own backward.  Everything else silently takes `_attention_torch`, the reference's
     expression op for op: CPU tensors, other dtypes, an unsupported (L, d_k), a materialised or per-query mask, p >= 1,
     active dropout under stream capture (the per-call counter is host state and would freeze in a graph).  Double backward
     (create_graph=True) of a kernel-path forward recomputes the gradients from differentiable torch operations when the
@@ -115,14 +118,47 @@ class _FusedAttention(torch.autograd.Function):
         q, k, v, lse = ctx.saved_tensors
         H, p, seed, call = ctx.args
         need = ctx.needs_input_grad[:3]
-        if torch.is_grad_enabled():  # create_graph: the same gradients from differentiable torch operations
-            if p != 0.0:
-                raise RuntimeError("MultiHeadedAttention: double backward through the fused kernel's dropout is not supported")
-            mask = None if ctx.key_valid is None else ctx.key_valid[:, None, None, :]
-            wanted = [t for t, w in zip((q, k, v), need) if w]
-            grads = iter(torch.autograd.grad(_attention_torch(q, k, v, mask, H, None), wanted, G, create_graph=True))
-            return (*[next(grads) if w else None for w in need], None, None, None, None, None)
+        if torch.is_grad_enabled():
+            return (*_attention_grads_by_torch(ctx, G, q, k, v), None, None, None, None, None)
         dq, dk, dv = attention_backward(G.contiguous(), q, k, v, ctx.key_valid, lse, H, p, seed, call, need)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def _attention_grads_by_torch(ctx, G, q, k, v):
+    """create_graph: the gradients of a kernel-path forward from differentiable torch operations."""
+    H, p, _, _ = ctx.args
+    need = ctx.needs_input_grad[:3]
+    if p != 0.0:
+        raise RuntimeError("MultiHeadedAttention: double backward through the fused kernel's dropout is not supported")
+    mask = None if ctx.key_valid is None else ctx.key_valid[:, None, None, :]
+    wanted = [t for t, w in zip((q, k, v), need) if w]
+    grads = iter(torch.autograd.grad(_attention_torch(q, k, v, mask, H, None), wanted, G, create_graph=True))
+    return [next(grads) if w else None for w in need]
+
+
+class _TiledAttention(torch.autograd.Function):
+    """_FusedAttention through the tiled kernels (csrc/attention_tiled.hip).  It also keeps its result, from which the backward
+    takes D = dO . O; output_linear keeps that tensor for its own backward anyway."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, key_valid, H, p, seed, call):
+        from ..distributed._device_ops import attention_tiled_forward
+
+        out, lse = attention_tiled_forward(q, k, v, key_valid, H, p, seed, call)
+        ctx.save_for_backward(q, k, v, lse, out)
+        ctx.key_valid, ctx.args = key_valid, (H, p, seed, call)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        from ..distributed._device_ops import attention_tiled_backward
+
+        q, k, v, lse, out = ctx.saved_tensors
+        H, p, seed, call = ctx.args
+        if torch.is_grad_enabled():
+            return (*_attention_grads_by_torch(ctx, G, q, k, v), None, None, None, None, None)
+        dq, dk, dv = attention_tiled_backward(G.contiguous(), out, q, k, v, ctx.key_valid, lse, H, p, seed, call,
+                                              ctx.needs_input_grad[:3])
         return dq, dk, dv, None, None, None, None, None
 
 
@@ -157,6 +193,8 @@ class MultiHeadedAttention(nn.Module):
         self.dropout = nn.Dropout(p=dropout)
         self.kernel_path = True     # False: always `_attention_torch` (tests and tools compare the two)
         self.last_path = None       # "kernel" / "torch": what the last forward took
+        self.last_kernel = None     # "resident" / "tiled" (csrc/attention.hip / attention_tiled.hip), None on the torch path
+        self.prefer_tiled = False   # True: the tiled kernels also where the resident ones would do (tools and tests compare)
         # The high word of the kernel dropout's `call`: 0 for a module built on its own, 1 + the layer index inside BERT4Rec,
         # so that the layers of a model do not drop the same (b, h, i, j).  No process state enters: two stand-alone modules
         # under the same seed draw the same masks call for call.
@@ -164,28 +202,33 @@ class MultiHeadedAttention(nn.Module):
         self._dropout_calls = 0     # training forwards with active kernel dropout so far
 
     def _kernel_inputs(self, q, k, v, mask, p):
-        """(True, key_valid) when this call may take the kernel."""
+        """(kernel, key_valid): "resident" / "tiled" when this call may take that kernel, else None."""
         if not (self.kernel_path and q.is_cuda and q.dtype == torch.float32 and q.dim() == 3 and k.shape == q.shape
                 and v.shape == q.shape and k.dtype == q.dtype and v.dtype == q.dtype and q.shape[0] > 0 and 0.0 <= p < 1.0):
-            return False, None
-        from ..distributed._device_ops import attention_supported
+            return None, None
+        from ..distributed._device_ops import attention_supported, attention_tiled_supported
 
-        if not attention_supported(q.shape[1], self.d_k):
-            return False, None
+        if attention_supported(q.shape[1], self.d_k) and not self.prefer_tiled:
+            kernel = "resident"
+        elif attention_tiled_supported(q.shape[1], self.d_k):
+            kernel = "tiled"
+        else:
+            return None, None
         if p > 0.0 and torch.cuda.is_current_stream_capturing():
-            return False, None
+            return None, None
         ok, key_valid = key_padding_mask(mask, q.shape[0], q.shape[1])
-        if ok and key_valid is not None and key_valid.device != q.device:
-            return False, None
-        return ok, key_valid
+        if not ok or (key_valid is not None and key_valid.device != q.device):
+            return None, None
+        return kernel, key_valid
 
     def forward(self, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,
                 mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         # 1) the linear projections dim_model => num_heads x d_k, left as [B, L, H * d_k]
         q, k, v = [layer(x) for layer, x in zip(self.linear_layers, (query, key, value))]
         p = float(self.dropout.p) if self.training else 0.0
-        ok, key_valid = self._kernel_inputs(q, k, v, mask, p)
-        if not ok:
+        kernel, key_valid = self._kernel_inputs(q, k, v, mask, p)
+        self.last_kernel = kernel
+        if kernel is None:
             self.last_path = "torch"
             return self.output_linear(_attention_torch(q, k, v, mask, self.num_heads, self.dropout))
         self.last_path = "kernel"
@@ -196,11 +239,13 @@ class MultiHeadedAttention(nn.Module):
             call = (self._dropout_salt << 32) | (self._dropout_calls & 0xFFFFFFFF)
             self._dropout_calls += 1
         if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-            x = _FusedAttention.apply(q, k, v, key_valid, self.num_heads, p, seed, call)
+            fn = _TiledAttention if kernel == "tiled" else _FusedAttention
+            x = fn.apply(q, k, v, key_valid, self.num_heads, p, seed, call)
         else:
-            from ..distributed._device_ops import attention_forward
+            from ..distributed._device_ops import attention_forward, attention_tiled_forward
 
-            x = attention_forward(q, k, v, key_valid, self.num_heads, p, seed, call)[0]
+            fwd = attention_tiled_forward if kernel == "tiled" else attention_forward
+            x = fwd(q, k, v, key_valid, self.num_heads, p, seed, call)[0]
         return self.output_linear(x)
 
 
